@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Headline benchmark: images/s of 256^2 ControlVAR d24 `autoregressive_infer_cfg` (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the one JSON line (metric, value, unit, higher_is_better, dtype,
+ms_per_step = wall milliseconds of one timed step).  --dump-outputs DIR also writes what the last timed step returned, as .npy
+files (see dump_outputs).  Everything else this file measures runs only with --full (see below).
 
 N > 1 works both ways: under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` (RANK / WORLD_SIZE in the
 environment: this process IS one rank), and as plain `python bench.py --gpus N` - then bench.py starts the N ranks itself with
@@ -14,11 +18,13 @@ sampling over the 4096-way codebook, token->feature pyramid, and BOTH VQVAE deco
 Inputs (labels, condition types, synthetic weights) are resident in HBM before the timed region.
 Inference shards by sample: no data-path collective ("scaling": "weak").
 
-The JSON line also carries
+With --full the JSON line also carries
   roofline     - the dominant kernel (the MFMA GEMM / implicit-conv kernel): algorithmic FLOPs of its launches
                  divided by their HIP-event-timed duration inside the timed region, against the 2.5 PFLOP/s bf16 peak;
   cpu_baseline - the CPU oracle (this repo's restatement of the reference, validated against it) timed on the
-                 host cores of rank 0 on a bounded sample of the same workload.
+                 host cores of rank 0 on a bounded sample of the same workload;
+  side_configs - the other BASELINE.json configs, measured after the headline region (N = 1).
+The --no-* options switch parts of --full off.
 """
 from __future__ import annotations
 
@@ -47,6 +53,10 @@ def parse(argv=None):
     ap.add_argument('--cfg', type=float, default=4.0)
     ap.add_argument('--top_k', type=int, default=900)      # the reference's sampling defaults (train_control_var_hpu.py:338)
     ap.add_argument('--top_p', type=float, default=0.96)
+    ap.add_argument('--full', action='store_true', help='also measure what the headline does not need: roofline (HIP events on every GEMM-family launch of the timed '
+                                                        'region, MFMA probe, board telemetry), side configs and CPU baseline; the --no-* options switch parts of it off')
+    ap.add_argument('--dump-outputs', metavar='DIR', default='', help='after the timed steps, write what the last one returned as DIR/<name>.npy (float32, '
+                                                                      'a fixed seeded sample of the images; see dump_outputs)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--decode-chunk', type=int, default=0, help='images per VQVAE decoder pass (0 = the model default); A/B knob')
     ap.add_argument('--cpu-depth', type=int, default=0, help='depth of the CPU baseline model (0 = same as --depth)')
@@ -68,7 +78,12 @@ def parse(argv=None):
                                                              '1/world folding) on the only hardware a one-GPU lease offers; the line says so in config.parallelism')
     ap.add_argument('--stub-comm-ms', default='', help=argparse.SUPPRESS)                    # stub only: comma list of the fake step time of each channel candidate
     ap.add_argument('--stub-step-ms', type=float, default=0.0, help=argparse.SUPPRESS)      # tests/test_bench_launch.py: the launch / timing / JSON logic on
-    return ap.parse_args(argv)                                                               # CPU ranks (gloo) with a sleeping step instead of the model
+    a = ap.parse_args(argv)                                                                  # CPU ranks (gloo) with a sleeping step instead of the model
+    if a.steps < 1:
+        ap.error('--steps must be at least 1')
+    if a.dump_outputs and (a.mode != 'infer' or a.stub_step_ms > 0):
+        ap.error('--dump-outputs writes the images of --mode infer')
+    return a
 
 
 def physical_cores() -> int:
@@ -102,12 +117,12 @@ def cpu_baseline(depth: int, seed: int = 0, full: bool = False, budget_s: float 
     fp32, greedy, cfg 4, labels arange(B) % 1000, condition types arange(B) % 4, one d{depth} generation = B samples (2B CFG rows, all ten
     scales, both VQVAE decodes), 1 warm-up + 3 timed repetitions, median, for B = 1 and B = 8.
 
-    full=True  : exactly that (several minutes of CPU time: `bench.py --cpu-full`; the output of one such run is kept in profiles/).
-    full=False : the BOUNDED default so that `python bench.py` ends within minutes - B = 1 only, the warm-up is the first six scales of
+    full=True  : exactly that (several minutes of CPU time: `bench.py --full --cpu-full`; the output of one such run is kept in profiles/).
+    full=False : the BOUNDED default so that `python bench.py --full` ends within minutes - B = 1 only, the warm-up is the first six scales of
                  a generation (thread pool, allocator, oneDNN primitives), then up to 3 timed full repetitions, stopping early once
                  `budget_s` seconds are spent (at least one); median of the completed repetitions, their count is in `sample`.
-    Threads: one per PHYSICAL core, and - when the host has more than 32 of them - also 32 (torch's CPU GEMMs at B = 1 do not scale to 128
-    threads); the thread count with the faster warm-up runs the timed repetitions and is reported as `cores`."""
+    Threads: one per PHYSICAL core (at most OMP_NUM_THREADS when that is set), and - when that is more than 32 - also 32 (torch's CPU GEMMs at
+    B = 1 do not scale to 128 threads); the thread count with the faster warm-up runs the timed repetitions and is reported as `cores`."""
     from controlvar_amd.spec import DEFAULT_PATCH_NUMS as PN, VaeConfig, VarConfig, phi_index_map
     from controlvar_amd.synth import synth_vae_state, synth_var_state
     from oracle import var_ref
@@ -127,7 +142,9 @@ def cpu_baseline(depth: int, seed: int = 0, full: bool = False, budget_s: float 
         return time.time() - t0
 
     phys = physical_cores()
-    cands = [phys] + ([32] if phys > 32 else [])
+    omp = os.environ.get('OMP_NUM_THREADS', '')
+    top = min(phys, int(omp)) if omp.isdigit() and int(omp) > 0 else phys        # a thread budget set for this process (shared host) bounds the pool
+    cands = [top] + ([32] if top > 32 else [])
     warm = {}
     for th in cands:                                        # warm-up (and thread-count choice): first six scales, B = 1
         torch.set_num_threads(th)
@@ -550,6 +567,20 @@ def main_train(a):
     _finish(world)
 
 
+DUMP_IMAGES = 32          # 32 x 3 x 512 x 256 float32 = 48 MiB: the dump stays under 64 MB at any batch
+
+
+def dump_outputs(img, out_dir, seed=0):
+    """--dump-outputs: what autoregressive_infer_cfg returned in the last timed step, (B, 3, 512, 256) in [0, 1], as out_dir/images.npy in float32 -
+    the images of a fixed seeded sample of DUMP_IMAGES batch rows (all of them when B is smaller), in ascending row order.  The rows depend on B
+    and the seed only, so two builds run with the same arguments can be compared output for output."""
+    import numpy as np
+    B = img.shape[0]
+    rows = torch.randperm(B, generator=torch.Generator().manual_seed(seed))[:DUMP_IMAGES].sort().values
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, 'images.npy'), img[rows.to(img.device)].float().cpu().numpy())
+
+
 def main_infer(a):
     from controlvar_amd.launcher import dist_env, init_dist, sharded_timed_run
     rank, local, world = dist_env()
@@ -580,11 +611,11 @@ def main_infer(a):
     def step(seed):
         return var.autoregressive_infer_cfg(B, labels, g_seed=seed, cfg=a.cfg, top_k=a.top_k, top_p=a.top_p, cond_type=types)
 
-    prof = None if a.no_kernel_timing else []
+    prof = [] if a.full and not a.no_kernel_timing else None
     last = {}
 
     board = None
-    if rank == 0 and not a.no_telemetry:
+    if rank == 0 and a.full and not a.no_telemetry:
         from controlvar_amd.telemetry import BoardSampler
         board = BoardSampler(local)
 
@@ -604,6 +635,8 @@ def main_infer(a):
         sys.exit(f'[bench] the collective saw {ev["rccl_ranks"]} rank(s), the job has {world} (--gpus {a.gpus}): refusing to print a line for another job')
     img = last.pop('img')
     assert img.shape == (B, 3, 512, 256)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(img, a.dump_outputs)
     del img
 
     if rank == 0:
@@ -666,14 +699,14 @@ def main_infer(a):
                                'peak_note': 'dense bf16 MFMA peak at 2.4 GHz; this kernel is power-limited on random operands (the same instruction stream runs '
                                             '~30 % faster on constant operands: profiles/r03_gemm_power.txt), so the clock under load is ~1.85 GHz'}
         prof = None
-        if world == 1 and not a.no_extras:
+        if a.full and world == 1 and not a.no_extras:
             try:
                 box = {'var': var, 'vae': vae}
                 var = None
                 out['side_configs'] = side_configs(a, dev, box)
             except Exception as e:                                                  # a side config must never lose the headline line
                 out['side_configs'] = {'error': f'{type(e).__name__}: {e}'}
-        if not a.no_cpu_baseline and world == 1:            # reported baseline: rank 0 at N=1 only
+        if a.full and not a.no_cpu_baseline and world == 1:            # reported baseline: rank 0 at N=1 only
             out['cpu_baseline'] = cpu_baseline(a.cpu_depth or a.depth, full=a.cpu_full)
         print(json.dumps(out), flush=True)
     _finish(world)

@@ -1,10 +1,12 @@
 """`python bench.py --gpus N` must become N ranks by itself (VERDICT r2 missing #1; the reference: mp.spawn(main_worker, nprocs=ngpus_per_node),
 train_control_var_hpu.py:692-697).  CPU test of bench.py's own launch logic: two gloo ranks with a sleeping step; the one JSON line must say
-n_gpus == 2 and carry the max-over-ranks clock (rank 1 sleeps twice as long as rank 0)."""
+n_gpus == 2 and carry the max-over-ranks clock (rank 1 sleeps twice as long as rank 0).  Also: what a plain run, --full and --dump-outputs put out."""
 import json
 import os
 import subprocess
 import sys
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -59,3 +61,52 @@ def test_channel_selection_picks_the_fastest_candidate_on_every_rank():
     assert p.returncode == 0, p.stderr[-2000:]
     out = json.loads([l for l in p.stdout.splitlines() if l.startswith('{')][0])
     assert out['comm_channels'] == '8' and out['comm_channels_tried_s'] == {}
+
+
+def test_parse_validates_steps_and_dump_outputs():
+    import bench
+    a = bench.parse(['--gpus', '1', '--steps', '4', '--warmup', '2'])
+    assert a.steps == 4 and a.warmup == 2 and not a.full and a.dump_outputs == ''
+    assert bench.parse(['--full', '--dump-outputs', 'out']).full
+    for argv in (['--steps', '0'], ['--mode', 'train', '--dump-outputs', 'out']):
+        with pytest.raises(SystemExit):
+            bench.parse(argv)
+
+
+def test_dump_outputs_writes_a_fixed_float32_sample_of_the_images(tmp_path):
+    """--dump-outputs: the same seeded rows every time, float32, in ascending row order, within 64 MB at any batch"""
+    import numpy as np
+    import torch
+    import bench
+    assert bench.DUMP_IMAGES * 3 * 512 * 256 * 4 <= 64e6
+    img = torch.rand(bench.DUMP_IMAGES + 8, 3, 512, 256).to(torch.bfloat16)
+    bench.dump_outputs(img, str(tmp_path / 'a'))
+    bench.dump_outputs(img, str(tmp_path / 'b'))
+    got = np.load(tmp_path / 'a' / 'images.npy')
+    assert got.dtype == np.float32 and got.shape == (bench.DUMP_IMAGES, 3, 512, 256)
+    assert np.array_equal(got, np.load(tmp_path / 'b' / 'images.npy'))
+    full = img.float().numpy()
+    rows = [int(np.flatnonzero((full == g).all(axis=(1, 2, 3)))[0]) for g in got]
+    assert rows == sorted(set(rows))
+    small = torch.rand(3, 3, 512, 256)
+    bench.dump_outputs(small, str(tmp_path / 'c'))
+    assert np.array_equal(np.load(tmp_path / 'c' / 'images.npy'), small.numpy())
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_only_and_dumps_the_last_step(tmp_path):
+    """a plain run prints the headline keys and none of what --full adds; --dump-outputs writes the last timed step's images"""
+    import numpy as np
+    p = _run(['--gpus', '1', '--steps', '2', '--warmup', '1', '--batch', '2', '--dump-outputs', str(tmp_path / 'out')], timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    out = json.loads([l for l in p.stdout.splitlines() if l.startswith('{')][0])
+    assert out['steps'] == 2 and out['ms_per_step'] > 0 and out['unit'] == 'images/s' and out['higher_is_better'] is True and out['dtype'] == 'bf16'
+    assert not {'roofline', 'side_configs', 'cpu_baseline'} & set(out), sorted(out)
+    img = np.load(tmp_path / 'out' / 'images.npy')
+    assert img.dtype == np.float32 and img.shape == (2, 3, 512, 256)
+    assert np.isfinite(img).all() and img.min() >= 0.0 and img.max() <= 1.0
+    p = _run(['--gpus', '1', '--steps', '1', '--warmup', '1', '--batch', '2', '--full', '--no-extras', '--no-cpu-baseline', '--no-probe', '--no-telemetry'],
+             timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    out = json.loads([l for l in p.stdout.splitlines() if l.startswith('{')][0])
+    assert out['roofline']['launches'] > 0 and 'side_configs' not in out and 'cpu_baseline' not in out

@@ -263,3 +263,168 @@ def test_misc_ops_against_torch(gpu_device):
     # a bad status from the C ABI surfaces as RuntimeError
     with pytest.raises(RuntimeError):
         ns.attention(torch.zeros(1, 4, 3 * 64, device=gpu_device, dtype=torch.bfloat16), 1, 2, 5, 0.1, [], False)      # q_off + l > Lmax
+
+
+# ------------------------------------------------------------------------------------------------ slot plumbing on the host (no GPU)
+class _StubOps:
+    """torch.ops.cvar stand-in for the slot wrappers: same signatures, plain torch math on the CPU, and a call log.  The HIP kernels behind
+    the slots are tested on the GPU above; what the tests below pin is the wiring: argument plumbing, layouts, the mask -> level-table decoding
+    and its cache, and the autocast casts."""
+
+    def __init__(self):
+        self.calls = []
+
+    def linear(self, x, weight, bias=None, act=0, gate=None, gate_rows=1, residual=None, out_dtype=None):
+        from controlvar_amd._lib import ACT_GELU_TANH
+        assert x.dtype == weight.dtype, 'cvar::linear refuses mixed dtypes (torch_ops._linear)'
+        self.calls.append(('linear', x.dtype, int(act)))
+        y = F.linear(x.float(), weight.float(), bias.float() if bias is not None else None)
+        if act == ACT_GELU_TANH:
+            y = F.gelu(y, approximate='tanh')
+        return y.to(out_dtype or x.dtype)
+
+    def attention(self, qkv, H, q_off, l, scale, lvl_end, rowwise=False, holes=()):
+        R, Lk, _ = qkv.shape
+        self.calls.append(('attention', qkv.dtype, tuple(lvl_end), tuple(holes)))
+        q, k, v = qkv.float().view(R, Lk, 3, H, 64).permute(2, 0, 3, 1, 4)
+        q = q[:, :, q_off:q_off + l]
+        s = torch.einsum('rhqc,rhkc->rhqk', q, k) * scale
+        if lvl_end:
+            pos = torch.arange(q_off, q_off + l)
+            ends = torch.tensor(list(lvl_end))
+            vis = torch.arange(Lk)[None, :] < ends[torch.searchsorted(ends, pos, right=True)][:, None]
+            if holes:
+                hl = torch.tensor(list(holes)).view(-1, 2)[torch.searchsorted(ends, pos, right=True)]
+                kk = torch.arange(Lk)[None, :]
+                vis &= ~((kk >= hl[:, :1]) & (kk < hl[:, 1:]))
+            s = s.masked_fill(~vis, float('-inf'))
+        o = torch.einsum('rhqk,rhkc->rqhc', s.softmax(-1), v).reshape(R * l, H * 64)
+        return o.to(qkv.dtype), torch.logsumexp(s, dim=-1)
+
+    def ln_modulate(self, x, scale, shift, rows_per, eps, out_dtype):
+        self.calls.append(('ln_modulate', x.dtype, out_dtype))
+        C = x.shape[-1]
+        y = F.layer_norm(x.float(), (C,), eps=eps) * (1 + scale.float().reshape(-1, C)) + shift.float().reshape(-1, C)
+        return y.to(out_dtype)
+
+    def gate_residual_(self, x, f, gate, gate_rows, rowscale=None):
+        self.calls.append(('gate_residual_', f.dtype))
+        t = f.float() * gate.float().reshape(1, -1)
+        if rowscale is not None:
+            t = t * rowscale.float().reshape(-1, 1)
+        x.add_(t)
+
+
+@pytest.fixture()
+def stub_slots(monkeypatch):
+    from controlvar_amd import slots
+    stub = _StubOps()
+    monkeypatch.setattr(slots, 'cvar', stub)
+    monkeypatch.setattr(slots, '_need_cuda', lambda *a, **k: None)
+    return slots, stub
+
+
+@pytest.mark.parametrize('autocast', [False, True])
+def test_fused_mlp_slot_plumbing_on_the_host(stub_slots, autocast):
+    """fused_mlp_func called the way the reference's FFN calls it (flash-attn keywords, float32 Parameters): fc1 with the GELU epilogue, then
+    fc2; under autocast(bfloat16) both GEMMs see bf16 operands - also when the activation arrives in float32 (the adaLN path's LayerNorm
+    output) - and the result equals fc2(gelu_tanh(fc1(x))) to bf16 accuracy"""
+    slots, stub = stub_slots
+    torch.manual_seed(0)
+    fc1, fc2 = torch.nn.Linear(128, 512), torch.nn.Linear(512, 128)
+    x = torch.randn(2, 10, 128)
+    want = fc2(F.gelu(fc1(x), approximate='tanh'))
+    with torch.no_grad(), torch.autocast('cpu', dtype=torch.bfloat16, enabled=autocast):
+        got = slots.fused_mlp_func(x=x, weight1=fc1.weight, weight2=fc2.weight, bias1=fc1.bias, bias2=fc2.bias, activation='gelu_approx',
+                                   save_pre_act=False, return_residual=False, checkpoint_lvl=0, heuristic=0, process_group=None)
+    dt = torch.bfloat16 if autocast else torch.float32
+    assert stub.calls == [('linear', dt, 1), ('linear', dt, 0)]
+    assert got.dtype == dt and got.shape == want.shape
+    assert (got.float() - want).abs().max() < (3e-2 if autocast else 1e-5)
+
+
+@pytest.mark.parametrize('autocast', [False, True])
+def test_attention_slots_layouts_and_mask_decoding_on_the_host(stub_slots, autocast):
+    """slow_attn (B H L c) with the block-causal {0, -inf} bias of control_var.py:158-168 and without it, flash_attn_func (B L H c), and the
+    KV-cached form (queries = the LAST rows of the key sequence): each equals F.scaled_dot_product_attention; the mask is decoded to the level
+    ends (2, 6, 12), and the same mask buffer is decoded once, not once per call"""
+    slots, stub = stub_slots
+    torch.manual_seed(0)
+    L, H = 12, 2
+    lvl = torch.tensor([0] * 2 + [1] * 4 + [2] * 6)
+    bias = torch.where(lvl[:, None] >= lvl[None, :], 0.0, float('-inf')).view(1, 1, L, L)
+    q, k, v = (torch.randn(2, H, L, 64) for _ in range(3))
+    dt = torch.bfloat16 if autocast else torch.float32
+    tol = 3e-2 if autocast else 1e-5
+    r = lambda t: t.to(dt).float()                                   # what the slot computes on: the inputs in the autocast dtype
+    with torch.no_grad(), torch.autocast('cpu', dtype=torch.bfloat16, enabled=autocast):
+        outs = [(slots.slow_attn(q, k, v, scale=0.125, attn_mask=bias), F.scaled_dot_product_attention(r(q), r(k), r(v), attn_mask=bias, scale=0.125)),
+                (slots.slow_attn(q, k, v, scale=0.125), F.scaled_dot_product_attention(r(q), r(k), r(v), scale=0.125))]
+        fl = slots.flash_attn_func(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), dropout_p=0.0, softmax_scale=0.125)
+        outs.append((fl.transpose(1, 2), outs[1][1]))
+    for a, b in ((0, 2), (2, 6), (6, 12)):                          # KV cache: queries [a, b) against keys [0, b)
+        got = slots.slow_attn(q[:, :, a:b], k[:, :, :b], v[:, :, :b], scale=0.125)
+        outs.append((got, F.scaled_dot_product_attention(q[:, :, a:b], k[:, :, :b], v[:, :, :b], scale=0.125)))
+    for got, want in outs:
+        assert got.shape == want.shape and (got.float() - want.float()).abs().max() < tol
+    assert outs[0][0].dtype == dt and outs[2][0].dtype == dt
+    att = [c for c in stub.calls if c[0] == 'attention']
+    assert att[:3] == [('attention', dt, (2, 6, 12), ()), ('attention', dt, (), ()), ('attention', dt, (), ())]
+    assert len(att) == 6
+    n0 = len(slots._LEVELS_CACHE)
+    with torch.no_grad():
+        slots.slow_attn(q, k, v, scale=0.125, attn_mask=bias)
+        slots.slow_attn(q, k, v, scale=0.125, attn_mask=bias)
+    assert len(slots._LEVELS_CACHE) == n0
+
+
+def _torch_dropout_add_layer_norm(x0, residual, weight, bias, epsilon, rowscale=None, layerscale=None, prenorm=False, residual_in_fp32=False):
+    """flash_attn.ops.layer_norm.dropout_add_layer_norm's documented math in plain torch (dropout_p = 0):
+    residual_out = residual + x0 * rowscale * layerscale;  y = LayerNorm(residual_out) * weight + bias (dtype of x0)"""
+    t = x0.float()
+    if rowscale is not None:
+        t = t * rowscale.float().unsqueeze(-1)
+    if layerscale is not None:
+        t = t * layerscale.float()
+    res = t if residual is None else residual.float() + t
+    y = F.layer_norm(res, (x0.shape[-1],), weight.float(), bias.float(), epsilon).to(x0.dtype)
+    if not residual_in_fp32 and residual is not None:
+        res = res.to(residual.dtype)
+    return (y, res) if prenorm else y
+
+
+@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16], ids=['fp32', 'bf16'])
+def test_dropout_add_layer_norm_slot_plumbing_on_the_host(stub_slots, dtype):
+    """dropout_add_layer_norm as a fused add + norm chain calls it (prenorm, layerscale; the first block without a residual, a later one with
+    it, per-token rowscale) against flash-attn's documented math"""
+    slots, stub = stub_slots
+    torch.manual_seed(0)
+    C = 128
+    x0, res_in = torch.randn(2, 10, C).to(dtype), torch.randn(2, 10, C)
+    w, b, gamma, rs = torch.empty(C).uniform_(0.5, 1.5), torch.empty(C).uniform_(-0.2, 0.2), torch.randn(C) * 0.1, torch.rand(2, 10) + 0.5
+    cases = [dict(residual=None, layerscale=gamma, prenorm=True), dict(residual=res_in, layerscale=gamma, prenorm=True),
+             dict(residual=res_in, layerscale=gamma, rowscale=rs, prenorm=True), dict(residual=res_in, prenorm=False)]
+    tol = 4e-2 if dtype == torch.bfloat16 else 2e-5
+    for kw in cases:
+        with torch.no_grad():
+            got = slots.dropout_add_layer_norm(x0, kw['residual'], w, b, 0.0, 1e-6, rowscale=kw.get('rowscale'), layerscale=kw.get('layerscale'),
+                                               prenorm=kw['prenorm'])
+        want = _torch_dropout_add_layer_norm(x0, kw['residual'], w, b, 1e-6, rowscale=kw.get('rowscale'), layerscale=kw.get('layerscale'),
+                                             prenorm=kw['prenorm'])
+        for g, r in (zip(got, want) if kw['prenorm'] else ((got, want),)):
+            assert g.dtype == r.dtype and g.shape == r.shape
+            assert (g.float() - r.float()).abs().max() < tol
+    names = [c[0] for c in stub.calls]
+    assert names.count('gate_residual_') == 4 and names.count('ln_modulate') == 4
+
+
+def test_slot_cast_is_differentiable_for_trained_parameters_and_cached_for_frozen_ones():
+    """under autocast a parameter that needs a gradient is cast differentiably (no cache); a frozen one is cast once"""
+    from controlvar_amd import slots
+    w = torch.nn.Parameter(torch.randn(512, 128))
+    with torch.autocast('cpu', dtype=torch.bfloat16):
+        a = slots._cast(w, torch.bfloat16)
+        assert a.requires_grad and a.grad_fn is not None
+        with torch.no_grad():
+            b, c = slots._cast(w, torch.bfloat16), slots._cast(w, torch.bfloat16)
+        assert b is c and not b.requires_grad and b.dtype == torch.bfloat16

@@ -6,8 +6,8 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 TAG=${1:-r06}
 cd /tmp && export TMPDIR=/tmp
 O=$R/gpurun_out
-BENCH="python $R/bench.py --steps 2 --warmup 1 --no-extras --no-cpu-baseline --no-probe --no-telemetry"
-python $R/bench.py > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err
+BENCH="python $R/bench.py --full --steps 2 --warmup 1 --no-extras --no-cpu-baseline --no-probe --no-telemetry"
+python $R/bench.py --full > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err
 rocprofv3 --kernel-trace --stats -d $O/${TAG}_prof --output-format csv -- $BENCH > $O/${TAG}_prof.log 2>&1
 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE -d $O/pmc_mfma --output-format csv -- $BENCH > $O/pmc_mfma.log 2>&1
 rocprofv3 --pmc FETCH_SIZE -d $O/pmc_fetch --output-format csv -- $BENCH > $O/pmc_fetch.log 2>&1
