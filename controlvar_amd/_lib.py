@@ -11,7 +11,7 @@ import threading
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('CVAR_LIB') or os.path.join(HERE, 'libcvar_hip.so')      # CVAR_LIB: A/B runs against another build
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 CVAR_F32, CVAR_BF16 = 0, 1
 ACT_NONE, ACT_GELU_TANH, ACT_GELU_GRAD = 0, 1, 2
@@ -99,6 +99,12 @@ SIGNATURES = {
     'cvar_adamw': (c_i, [c_p, c_p, c_p, c_p, c_l, c_f, c_f, c_f, c_f, c_f, c_i, c_p, c_f, c_p]),
     'cvar_sumsq': (c_i, [c_p, c_l, c_p, c_p]),
     'cvar_clip_coef': (c_i, [c_p, c_l, c_f, c_f, c_p, c_p]),
+    # LoRA adapter branch (ABI 21)
+    'cvar_lora_down': (c_i, [c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_l, c_i, c_i, c_i, c_i, c_f, c_f, C.c_uint64, C.c_uint32, c_p]),
+    'cvar_lora_dx': (c_i, [c_p, c_l, c_i, c_p, c_l, c_p, c_l, c_p, c_l, c_i, c_i, c_i, c_i, c_f, c_f, C.c_uint64, C.c_uint32, c_p]),
+    'cvar_lora_wgrad_ws_floats': (c_l, [c_i, c_i]),
+    'cvar_lora_wgrad': (c_i, [c_p, c_l, c_p, c_l, c_i, c_i, c_i, c_i, c_f, c_f, C.c_uint64, C.c_uint32, c_p, c_l, c_p, c_l, c_l, c_p]),
+    'cvar_lora_dropout_mask': (c_i, [c_p, c_i, c_i, c_f, C.c_uint64, C.c_uint32, c_p]),
     # measurement aid (bench.py roofline.sustained_*)
     'cvar_probe_mfma_bf16': (c_i, [c_p, c_l, c_i, c_p, c_p]),
     'cvar_probe_mfma_bf16_32x32': (c_i, [c_p, c_l, c_i, c_p, c_p]),

@@ -736,10 +736,15 @@ class ControlVAR(nn.Module):
     # ---- plumbing
     def load_state_dict(self, state_dict, strict=True, assign=False):
         self._packed = None
+        if getattr(self, '_lora', None) is not None:        # LoRA model: peft's key layout loads too (controlvar_amd/lora.py)
+            from .lora import to_module_layout
+            self._packed_base = None
+            state_dict = to_module_layout(state_dict)
         return super().load_state_dict(state_dict, strict=strict, assign=assign)
 
     def _apply(self, fn, *a, **k):
         self._packed = None
+        self._packed_base = None
         self._arena = None
         return super()._apply(fn, *a, **k)
 
@@ -772,22 +777,50 @@ class ControlVAR(nn.Module):
         out[hw] = P['w_head'][:cfg.head_out]
         return out, tuple(keys)
 
-    def _pack(self, check: bool = False, fresh: Sequence[str] = ()):
+    def _pack(self, check: bool = False, fresh: Sequence[str] = (), base: bool = False):
         """GEMM-ready device copies of the weights (stacked per kind, compute dtype).  check=True (every public entry point and
         the training engine's forward): rebuild when any parameter changed since - torch.optim steps through the autograd bridge,
         manual in-place edits, .data swaps (the copies used to go stale on that path).
         fresh: keys of the current copies that are already up to date (the fused optimizer updated them in its own pass) - those tensors
-        are kept, everything else is rebuilt from the parameters."""
+        are kept, everything else is rebuilt from the parameters.
+        LoRA model (controlvar_amd/lora.py): the copies hold W + s B A (inference runs the adapter-free kernels; the signature covers the
+        adapters); base=True returns the copies of the frozen base weights instead - what the training engine runs (the dropout of the
+        adapter branch makes the merged form wrong there).  Without adapters ``base`` changes nothing."""
+        lora = getattr(self, '_lora', None)
+        if base and lora is not None:
+            return self._pack_lora_base()
         if not fresh and self._packed is not None and (not check or self._packed_sig == self._state_sig()):
             return self._packed
         old = self._packed if fresh else None
         if fresh and old is None:
             raise RuntimeError('_pack(fresh=...) without packed copies to keep')
+        P = self._build_pack(old, fresh, lora)
+        self._packed = P
+        self._packed_sig = self._state_sig()
+        self._pack_gen = getattr(self, '_pack_gen', 0) + 1          # consumers of derived copies (TrainEngine.WT) compare this
+        return P
+
+    def _base_sig(self):
+        return tuple((t.data_ptr(), t._version) for n, t in list(self.named_parameters()) + list(self.named_buffers()) if '.lora_' not in n)
+
+    def _pack_lora_base(self):
+        """packed copies of the frozen base weights of a LoRA model (rebuilt only when a base tensor changes)"""
+        if getattr(self, '_packed_base', None) is not None and self._packed_base_sig == self._base_sig():
+            return self._packed_base
+        self._packed_base = self._build_pack(None, (), None)
+        self._packed_base_sig = self._base_sig()
+        self._pack_base_gen = getattr(self, '_pack_base_gen', 0) + 1
+        return self._packed_base
+
+    def _build_pack(self, old, fresh: Sequence[str], lora):
         dev, T, cfg = self.device, self.compute_dtype, self.cfg
         if dev.type != 'cuda':
             raise RuntimeError('controlvar_amd models compute on the GPU only; call .to("cuda") first')
         ops.ensure_splitk_workspace(dev)
         sd = {k: v.detach() for k, v in self.state_dict().items()}
+        if getattr(self, '_lora', None) is not None:
+            from .lora import merged_state
+            sd = merged_state(sd, self._lora) if lora is not None else {k: v for k, v in sd.items() if '.lora_' not in k}
         C, depth = cfg.C, cfg.depth
         P: Dict[str, Any] = {}
         blk = lambda i, s: sd[f'blocks.{i}.{s}']
@@ -854,9 +887,6 @@ class ControlVAR(nn.Module):
         P['cond_embed'] = sd['cond_embed.weight'].float().contiguous() if 'cond_embed.weight' in sd else None
         if cfg.uses_cos_attn:
             P['scale_mul'] = torch.stack([blk(i, 'attn.scale_mul_1H11').reshape(-1) for i in range(depth)]).float().contiguous()
-        self._packed = P
-        self._packed_sig = self._state_sig()
-        self._pack_gen = getattr(self, '_pack_gen', 0) + 1          # consumers of derived copies (TrainEngine.WT) compare this
         return P
 
     def _first_tokens(self, P, labels, types, x, cond, R: int, x_rows: int, table, mask_first: bool = True):

@@ -467,3 +467,54 @@ def ignore_mask(cond: torch.Tensor, B: int, H: int, W: int, patch_nums: Sequence
 def rle_paint(run_ends: torch.Tensor, ann_offsets: torch.Tensor, colours: torch.Tensor, n_ann: int, H: int, W: int, out: torch.Tensor):
     check(_lib.load().cvar_rle_paint(_ptr(run_ends), _ptr(ann_offsets), _ptr(colours), n_ann, H, W, _ptr(out), _stream()), 'cvar_rle_paint')
     return out
+
+
+# ---- LoRA adapter branch (cvar_lora_*, ABI 21).  Offsets (*_off) in elements; the (seed, tag) pair names one target's dropout mask.
+def lora_down(x, A, u, *, M: int, K: int, r: int, scale: float, p: float = 0.0, seed: int = 0, tag: int = 0, ldx: int = 0, lda: int = 0,
+              ldu: int = 0, x_off: int = 0, u_off: int = 0, x_copy=None, ld_copy: int = 0):
+    """u[m, :r] = scale * drop(x[m]) A^T (cvar_lora_down); x_copy receives x unchanged in the same pass"""
+    if A.dtype != x.dtype or u.dtype != x.dtype:
+        raise TypeError('lora_down: x, A and u must share a dtype')
+    es = x.element_size()
+    check(_lib.load().cvar_lora_down(_ptr(x) + x_off * es, ldx or K, _ptr(A), lda or K, _ptr(u) + u_off * es, ldu or r, _ptr(x_copy), ld_copy or K,
+                                     M, K, r, dt(x), float(scale), float(p), int(seed) & (2 ** 64 - 1), int(tag) & 0xffffffff, _stream()),
+          'cvar_lora_down')
+    return u
+
+
+def lora_dx(dx, du, A, *, M: int, K: int, r: int, scale: float, p: float = 0.0, seed: int = 0, tag: int = 0, lddx: int = 0, lddu: int = 0,
+            lda: int = 0, du_off: int = 0, aux=None, ldaux: int = 0):
+    """dx = (dx + scale * drop'(du A)) * gelu'(aux) in place (cvar_lora_dx); du rows are 16 wide (lddu >= 16, a multiple of 8)"""
+    if A.dtype != du.dtype or (aux is not None and aux.dtype != du.dtype):
+        raise TypeError('lora_dx: du, A and aux must share a dtype')
+    check(_lib.load().cvar_lora_dx(_ptr(dx), lddx or K, dt(dx), _ptr(du) + du_off * du.element_size(), lddu or 16, _ptr(A), lda or K, _ptr(aux),
+                                   ldaux or K, M, K, r, dt(du), float(scale), float(p), int(seed) & (2 ** 64 - 1), int(tag) & 0xffffffff, _stream()),
+          'cvar_lora_dx')
+    return dx
+
+
+def lora_wgrad_ws_floats(M: int, N: int) -> int:
+    return int(_lib.load().cvar_lora_wgrad_ws_floats(M, N))
+
+
+def lora_wgrad(Y, Z, out, ws, *, M: int, N: int, r: int, scale: float = 1.0, p: float = 0.0, seed: int = 0, tag: int = 0, ldy: int = 0,
+               ldz: int = 0, y_off: int = 0, z_off: int = 0, out_off: int = 0, os_n: int = 0, os_j: int = 1):
+    """fp32 out[n * os_n + j * os_j] = scale * sum_m drop(Y)[m, n] Z[m, j] (cvar_lora_wgrad; os_n defaults to r: an [N][r] matrix)"""
+    if Y.dtype != Z.dtype:
+        raise TypeError('lora_wgrad: Y and Z must share a dtype')
+    if out.dtype != torch.float32 or ws.dtype != torch.float32:
+        raise TypeError('lora_wgrad: out and ws are fp32')
+    es = Y.element_size()
+    check(_lib.load().cvar_lora_wgrad(_ptr(Y) + y_off * es, ldy or N, _ptr(Z) + z_off * es, ldz or r, M, N, r, dt(Y), float(scale), float(p),
+                                      int(seed) & (2 ** 64 - 1), int(tag) & 0xffffffff, _ptr(ws), ws.numel(), _ptr(out) + 4 * out_off,
+                                      os_n or r, os_j, _stream()), 'cvar_lora_wgrad')
+    return out
+
+
+def lora_dropout_mask(M: int, K: int, p: float, seed: int, tag: int, device=None) -> torch.Tensor:
+    """(M, K) fp32 keep mask (1 / 0) of one target - exactly the bits the cvar_lora_* calls apply with the same (p, seed, tag)"""
+    dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+    out = torch.empty(M, K, device=dev, dtype=torch.float32)
+    check(_lib.load().cvar_lora_dropout_mask(_ptr(out), M, K, float(p), int(seed) & (2 ** 64 - 1), int(tag) & 0xffffffff, _stream()),
+          'cvar_lora_dropout_mask')
+    return out

@@ -73,13 +73,16 @@ def decays(name: str, ndim: int, nowd_keys: Iterable[str] = NOWD_KEYS) -> bool:
     return not (ndim == 1 or name.endswith('bias') or any(k in name for k in nowd_keys))
 
 
-def filter_params(model, nowd_keys: Iterable[str] = NOWD_KEYS):
-    """names, params, [group 'D' (wd_sc 1), group 'ND' (wd_sc 0)] in first-seen order (utils/lr_control.py:67-101)."""
+def filter_params(model, nowd_keys: Iterable[str] = NOWD_KEYS, trainable_only: bool = False):
+    """names, params, [group 'D' (wd_sc 1), group 'ND' (wd_sc 0)] in first-seen order (utils/lr_control.py:67-101).
+    trainable_only=True (LoRA, controlvar_amd/lora.py): frozen parameters are skipped instead of failing the reference's assert."""
     groups: Dict[str, dict] = {}
     names, paras = [], []
     for name, p in model.named_parameters():
         name = name.replace('_fsdp_wrapped_module.', '')
         if not p.requires_grad:
+            if trainable_only:
+                continue
             raise AssertionError(f'frozen parameter {name}')
         names.append(name)
         paras.append(p)
@@ -117,9 +120,15 @@ class TrainEngine:
         self.reducer = reducer
         self._B = None
         self._wt_gen = -1
+        self._lora = None
 
     # ---------------------------------------------------------------- buffers
     def _setup(self, B: int):
+        lora = getattr(self.var, '_lora', None)
+        if lora is not None:
+            return self._setup_lora(B, lora)
+        if self._lora is not None:                  # the adapters were merged away: back to the full path
+            self._lora, self._B = None, None
         if self._B == B:
             return
         cfg, var = self.cfg, self.var
@@ -189,8 +198,8 @@ class TrainEngine:
         self._transposed_weights()
 
     def _transposed_weights(self):
-        """W^T copies for the data-gradient GEMMs (refreshed after every optimizer step)."""
-        P, cfg = self.var._pack(), self.cfg
+        """W^T copies for the data-gradient GEMMs (refreshed after every optimizer step).  LoRA: of the frozen base weights."""
+        P, cfg = self.var._pack(base=True), self.cfg
         C, depth, V = cfg.C, cfg.depth, cfg.head_ld
         hid = P['w_fc1'].shape[1]
         T = self.var.compute_dtype
@@ -203,10 +212,15 @@ class TrainEngine:
         ops.transpose(P['w_fc2'], self.WT['fc2'], depth, C, hid, hid)
         ops.transpose(P['w_head'], self.WT['head'], 1, V, C, C)
         ops.transpose(P['w_ada'], self.WT['ada'], 1, P['n_ada'], C, C)
-        self._wt_gen = self.var._pack_gen
+        self._wt_gen = self._pack_gen()
+
+    def _pack_gen(self):
+        return self.var._pack_base_gen if getattr(self.var, '_lora', None) is not None else self.var._pack_gen
 
     def grads(self) -> Dict[str, torch.Tensor]:
-        """state_dict key -> gradient view (fp32)"""
+        """state_dict key -> gradient view (fp32); a LoRA model: the adapter keys only"""
+        if self._lora is not None:
+            return {k: self.G_lora[o:o + n].view(*shape) for k, (o, n, shape) in self.lora_off.items()}
         cfg = self.cfg
         C, depth, V, Vo = cfg.C, cfg.depth, cfg.head_ld, cfg.head_out
         hid = round(C * cfg.mlp_ratio)
@@ -287,14 +301,15 @@ class TrainEngine:
                       mask_first: bool = True):
         """teacher-forced forward that keeps every block's activations; returns logits (B*L, V) fp32"""
         cfg, var = self.cfg, self.var
-        P = var._pack(check=True)
+        P = var._pack(check=True, base=True)
         py, C, depth, V, H = cfg.pyramid, cfg.C, cfg.depth, cfg.head_ld, cfg.H
         L, fl = py.L, py.first_l
         dev, T = var.device, var.compute_dtype
         B = x_wo_first.shape[0]
         self._setup(B)
-        if self._wt_gen != var._pack_gen:          # the W^T copies follow the packed weights (any optimizer, manual edits, resume)
+        if self._wt_gen != self._pack_gen():       # the W^T copies follow the packed weights (any optimizer, manual edits, resume)
             self._transposed_weights()
+        lo = self._lora
         M, Mp = self.M, self.Mp
         hid = P['w_fc1'].shape[1]
         n_ada = P['n_ada']
@@ -324,6 +339,10 @@ class TrainEngine:
             keep = 1 - dpr
             dp1 = (torch.rand(depth, B, device=dev, generator=g) < keep).float() / keep
             dp2 = (torch.rand(depth, B, device=dev, generator=g) < keep).float() / keep
+        if lo is not None:                                            # adapter dropout: active in train() only; drop_seed seeds it too
+            self._lp = lo['dropout'] if var.training else 0.0
+            self._lseed = drop_seed if drop_seed is not None else int(torch.empty((), dtype=torch.int64).random_().item())
+            self._lora_pack()
         # ---- forward
         x0 = self.Xs[0]
         cond = torch.empty(B, C, device=dev, dtype=torch.float32)
@@ -337,7 +356,10 @@ class TrainEngine:
         cs = torch.empty(B, C, device=dev, dtype=T)
         ops.silu_cast(cond, cs)
         ada = torch.empty(B, n_ada, device=dev, dtype=torch.float32)
-        ops.gemm(cs, P['w_ada'], ada, M=B, N=n_ada, K=C, bias=P['b_ada'])
+        if lo is None:
+            ops.gemm(cs, P['w_ada'], ada, M=B, N=n_ada, K=C, bias=P['b_ada'])
+        else:
+            self._lora_ada_forward(cs, ada, P, B)
         for i in range(depth):
             a0 = i * 6 * C
             x = self.Xs[i]
@@ -346,6 +368,9 @@ class TrainEngine:
             if cfg.uses_cos_attn:
                 ops.cos_qk_norm(self.arena[i], B, H, L, 0, L, P['scale_mul'], sm_off=i * H, norms=self.NORMS[i])
             ops.attention(self.arena[i], self.O[i], B, H, L, 0, L, scale, lvl_end, lse=self.LSE[i], holes=holes)
+            if lo is not None:
+                self._lora_block_forward(i, ada, P, dp1, dp2)
+                continue
             # x1 = x + (gamma1 * keep1) * proj(o): gate / DropPath scale / residual in the GEMM epilogue; the branch output the backward
             # needs (d gamma1 = sum dx * f) is stored next to it
             ops.gemm(self.O[i], P['w_proj'], self.X1s[i], M=M, N=C, K=C, w_off=i * C * C, bias=P['b_proj'][i], gate=ada, ldg=n_ada, gate_rows=L,
@@ -382,6 +407,8 @@ class TrainEngine:
     def backward(self):
         """backward from self.dlogits (compute dtype, (B*L, V)) through head, blocks, adaLN generator and embeddings"""
         cfg, var = self.cfg, self.var
+        if self._lora is not None:
+            return self._backward_lora()
         P = var._pack()
         py, C, depth, V, H = cfg.pyramid, cfg.C, cfg.depth, cfg.head_ld, cfg.H
         L, fl = py.L, py.first_l
@@ -481,6 +508,238 @@ class TrainEngine:
         if self.reducer is not None:
             self.reducer.ready(depth + 1)
 
+    # ---------------------------------------------------------------- LoRA (controlvar_amd/lora.py; DESIGN.md "LoRA")
+    # The base weights are frozen: their gradients are neither computed nor stored.  Each target's rank-r branch enters the base
+    # GEMM - and so its fused epilogue (bias, gate, DropPath scale, residual, GELU, pre_act) - by K-augmentation: the operand [x | u]
+    # (u = s drop(x) A^T from cvar_lora_down, zero padding up to a 128-byte row step) against the packed weight [W | B | 0].  The
+    # backward runs the base data-gradient GEMM, then cvar_lora_down for du = dY B, cvar_lora_dx for the branch's share of dx, and
+    # cvar_lora_wgrad for dB = dY^T u and dA = s du^T drop(x).  Targets: tag 4 i + (0 proj, 1 fc1, 2 fc2, 3 ada_lin), head_nm 4 depth + 3.
+    def _setup_lora(self, B: int, lora):
+        key = (B, id(lora))
+        if self._B == key:
+            return
+        cfg, var = self.cfg, self.var
+        dev, T = var.device, var.compute_dtype
+        C, depth, V = cfg.C, cfg.depth, cfg.head_ld
+        L = cfg.pyramid.L
+        M = B * L
+        hid = round(C * cfg.mlp_ratio)
+        n_ada = depth * 6 * C + 2 * C
+        r = lora['r']
+        rp = 128 // torch.tensor([], dtype=T).element_size()          # augmented K step: keeps cvar_gemm on its K-multiple-of-128-bytes path
+        self._lora, self.r, self.rp = lora, r, rp
+        self.M, self.Mp, self.Bp = M, _pad8(M), _pad8(B)
+        self.Kx = -(-(depth + 1) * 16 // rp) * rp                     # [cs | u_0 ... u_depth] columns beyond C
+        f32 = dict(device=dev, dtype=torch.float32)
+        tT = dict(device=dev, dtype=T)
+        self.Xs = torch.empty(depth + 1, M, C, **f32)
+        self.X1s = torch.empty(depth, M, C, **f32)
+        self.U = torch.empty(depth, M, C, **tT); self.O = torch.empty(depth, M, C, **tT)
+        self.F1 = torch.empty(depth, M, C, **tT); self.U2 = torch.empty(M, C, **tT); self.F2 = torch.empty(depth, M, C, **tT)
+        self.Oa = torch.zeros(depth, M, C + rp, **tT)               # [o | u_proj | 0]
+        self.U2a = torch.zeros(depth, M, C + rp, **tT)              # [u2 | u_fc1 | 0]
+        self.Hha = torch.zeros(depth, M, hid + rp, **tT)            # [gelu(a) | u_fc2 | 0]
+        self.Aa = torch.empty(depth, M, hid + rp, **tT)             # fc1 pre-activation (row stride of the fc1 output)
+        self.csa = torch.zeros(B, C + self.Kx, **tT)
+        self.arena = torch.empty(depth, B, L, 3 * C, **tT)
+        self.LSE = torch.empty(depth, B, cfg.H, L, **f32)
+        self.NORMS = torch.empty(depth, B, L, cfg.H, 2, **f32) if cfg.uses_cos_attn else None
+        self.DSM = torch.empty(M, cfg.H, **f32) if cfg.uses_cos_attn else None
+        self.UH = torch.empty(M, C, **tT)
+        self.logits = torch.empty(M, V, **f32)
+        self.loss_tok = torch.empty(M, **f32)
+        self.dlogits = torch.empty(M, V, **tT)
+        self.dX = torch.empty(M, C, **f32)
+        self.DF = torch.empty(M, C, **tT); self.DU = torch.empty(M, C, **tT)
+        self.DH = torch.empty(M, hid, **tT)
+        self.DQKV = torch.empty(B, L, 3 * C, **tT)
+        self.DUr = torch.empty(M, 16, **tT)
+        self.DUa = torch.empty(B, 16, **tT)
+        self.ncode = len(cfg.pyramid.code_positions()) - cfg.pyramid.first_l
+        self.dada = torch.zeros(B, n_ada, **f32)
+        self.ws = torch.empty(max(ops.train_ws_floats(M, B, C), 64 * max(hid, 3 * C, V, n_ada), L * C, B * cfg.H * L) + 16, **f32)
+        self.lws = torch.empty(max(ops.lora_wgrad_ws_floats(M, hid), ops.lora_wgrad_ws_floats(M, C), ops.lora_wgrad_ws_floats(B, 6 * C)), **f32)
+        # adapter gradient slabs: one per layer [proj A, B | fc1 A, B | fc2 A, B], then every ada_lin adapter (the all-reduce buckets)
+        self.lora_off = {}
+        o = 0
+        dims = dict(proj=(C, C), fc1=(C, hid), fc2=(hid, C))
+        mods = (('proj', 'attn.proj'), ('fc1', 'ffn.fc1'), ('fc2', 'ffn.fc2'))
+        bounds = []
+        for i in range(depth):
+            for kind, name in mods:
+                k_in, n_out = dims[kind]
+                for ab, shape in (('A', (r, k_in)), ('B', (n_out, r))):
+                    self.lora_off[f'blocks.{i}.{name}.lora_{ab}.default.weight'] = (o, shape[0] * shape[1], shape)
+                    o += shape[0] * shape[1]
+            bounds.append(o)
+        for t in range(depth + 1):
+            n_out = 6 * C if t < depth else 2 * C
+            name = f'blocks.{t}.ada_lin.1' if t < depth else 'head_nm.ada_lin.1'
+            for ab, shape in (('A', (r, C)), ('B', (n_out, r))):
+                self.lora_off[f'{name}.lora_{ab}.default.weight'] = (o, shape[0] * shape[1], shape)
+                o += shape[0] * shape[1]
+        if set(self.lora_off) != {n for n, p in var.named_parameters() if p.requires_grad}:
+            raise RuntimeError('LoRA: the trainable parameters are not exactly the adapters of add_lora')
+        self.G_lora = torch.zeros(o, **f32)
+        starts = [0] + bounds
+        self.buckets = [self.G_lora[starts[i]:starts[i + 1]] for i in range(depth)] + [self.G_lora[bounds[-1]:]]
+        self._aug = None
+        self._B = key
+        self._transposed_weights()
+
+    def _lora_pack(self):
+        """operands of the adapter branch in the compute dtype: A (16 rows, zero beyond r), B^T (16 rows) per target, and the K-augmented
+        GEMM weights [W | B | 0] (base part copied once per base pack, the B columns at every forward)"""
+        from .lora import adapters
+        var, cfg, lo = self.var, self.cfg, self._lora
+        P = var._pack(base=True)
+        T, dev = var.compute_dtype, var.device
+        C, depth, r, rp = cfg.C, cfg.depth, self.r, self.rp
+        hid = P['w_fc1'].shape[1]
+        n_ada = P['n_ada']
+        ad = adapters(var)
+        names = dict(proj='attn.proj', fc1='ffn.fc1', fc2='ffn.fc2')
+        if self._aug is None or self._aug[0] is not P:
+            W = {}
+            for kind, (n_out, k_in) in (('proj', (C, C)), ('fc1', (hid, C)), ('fc2', (C, hid))):
+                w = torch.zeros(depth, n_out, k_in + rp, device=dev, dtype=T)
+                w[:, :, :k_in] = P['w_' + kind]
+                W[kind] = w
+            w = torch.zeros(n_ada, C + self.Kx, device=dev, dtype=T)
+            w[:, :C] = P['w_ada']
+            W['ada'] = w
+            self._aug = (P, W)
+        W = self._aug[1]
+        self.Wa = W
+        self.LA, self.LBT = {}, {}
+        for kind, (n_out, k_in) in (('proj', (C, C)), ('fc1', (hid, C)), ('fc2', (C, hid))):
+            As = torch.stack([ad[f'blocks.{i}.{names[kind]}'][0] for i in range(depth)])          # (depth, r, k_in)
+            Bs = torch.stack([ad[f'blocks.{i}.{names[kind]}'][1] for i in range(depth)])          # (depth, n_out, r)
+            self.LA[kind] = torch.zeros(depth, 16, k_in, device=dev, dtype=T)
+            self.LA[kind][:, :r] = As
+            self.LBT[kind] = torch.zeros(depth, 16, n_out, device=dev, dtype=T)
+            self.LBT[kind][:, :r] = Bs.transpose(1, 2)
+            W[kind][:, :, k_in:k_in + r] = Bs
+        tn = [f'blocks.{t}.ada_lin.1' for t in range(depth)] + ['head_nm.ada_lin.1']
+        self.LA['ada'] = torch.zeros(depth + 1, 16, C, device=dev, dtype=T)
+        self.LA['ada'][:, :r] = torch.stack([ad[n][0] for n in tn])
+        self.LBT['ada'] = torch.zeros(depth + 1, 16, 6 * C, device=dev, dtype=T)
+        for t, n in enumerate(tn):
+            Bt = ad[n][1]
+            self.LBT['ada'][t, :r, :Bt.shape[0]] = Bt.t()
+            W['ada'][t * 6 * C:t * 6 * C + Bt.shape[0], C + 16 * t:C + 16 * t + r] = Bt
+
+    def _tag(self, i: int, kind: str) -> int:
+        return 4 * i + ('proj', 'fc1', 'fc2', 'ada').index(kind)
+
+    def _lora_ada_forward(self, cs, ada, P, B):
+        C, depth, lo = self.cfg.C, self.cfg.depth, self._lora
+        ld = C + self.Kx
+        for t in range(depth + 1):
+            ops.lora_down(cs, self.LA['ada'][t], self.csa, M=B, K=C, r=self.r, scale=lo['scale'], p=self._lp, seed=self._lseed,
+                          tag=self._tag(t, 'ada'), ldu=ld, u_off=C + 16 * t, x_copy=self.csa if t == 0 else None, ld_copy=ld)
+        ops.gemm(self.csa, self.Wa['ada'], ada, M=B, N=P['n_ada'], K=ld, lda=ld, ldw=ld, bias=P['b_ada'])
+
+    def _lora_block_forward(self, i, ada, P, dp1, dp2):
+        cfg, lo = self.cfg, self._lora
+        C, M, L, r, rp = cfg.C, self.M, cfg.pyramid.L, self.r, self.rp
+        hid = P['w_fc1'].shape[1]
+        n_ada = P['n_ada']
+        eps = cfg.norm_eps
+        s, p, seed = lo['scale'], self._lp, self._lseed
+        a0 = i * 6 * C
+        x = self.Xs[i]
+        kc, kh = C + rp, hid + rp
+        ops.lora_down(self.O[i], self.LA['proj'][i], self.Oa[i], M=M, K=C, r=r, scale=s, p=p, seed=seed, tag=self._tag(i, 'proj'), ldu=kc, u_off=C,
+                      x_copy=self.Oa[i], ld_copy=kc)
+        ops.gemm(self.Oa[i], self.Wa['proj'], self.X1s[i], M=M, N=C, K=kc, lda=kc, ldw=kc, w_off=i * C * kc, bias=P['b_proj'][i], gate=ada, ldg=n_ada,
+                 gate_rows=L, gate_off=a0, gate_scale=dp1[i].contiguous() if dp1 is not None else None, residual=x, pre_act=self.F1[i])
+        ops.ln_modulate(self.X1s[i], ada, a0 + 3 * C, a0 + 5 * C, n_ada, L, self.U2, M, C, eps)
+        ops.lora_down(self.U2, self.LA['fc1'][i], self.U2a[i], M=M, K=C, r=r, scale=s, p=p, seed=seed, tag=self._tag(i, 'fc1'), ldu=kc, u_off=C,
+                      x_copy=self.U2a[i], ld_copy=kc)
+        ops.gemm(self.U2a[i], self.Wa['fc1'], self.Hha[i], M=M, N=hid, K=kc, lda=kc, ldw=kc, ldc=kh, w_off=i * hid * kc, bias=P['b_fc1'][i],
+                 act=ACT_GELU_TANH, pre_act=self.Aa[i])
+        ops.lora_down(self.Hha[i], self.LA['fc2'][i], self.Hha[i], M=M, K=hid, r=r, scale=s, p=p, seed=seed, tag=self._tag(i, 'fc2'), ldx=kh, ldu=kh,
+                      u_off=hid)
+        ops.gemm(self.Hha[i], self.Wa['fc2'], self.Xs[i + 1], M=M, N=C, K=kh, lda=kh, ldw=kh, w_off=i * C * kh, bias=P['b_fc2'][i], gate=ada, ldg=n_ada,
+                 gate_rows=L, gate_off=a0 + C, gate_scale=dp2[i].contiguous() if dp2 is not None else None, residual=self.X1s[i], pre_act=self.F2[i])
+
+    def _lora_grads_of(self, i, kind, name, dY, n_out, x, k_in, ldx, x_off_u, aux=None, ldaux=0):
+        """du = dY B; dx (self.DU / self.DH, in place) += branch share (* gelu'(aux)); dB = dY^T u; dA = s du^T drop(x).  x: the augmented
+        saved input [x | u] with row stride ldx, u at column x_off_u"""
+        lo, M, r = self._lora, self.M, self.r
+        s, p, seed, tag = lo['scale'], self._lp, self._lseed, self._tag(i, kind)
+        G = self.G_lora
+        oA = self.lora_off[f'{name}.lora_A.default.weight'][0]
+        oB = self.lora_off[f'{name}.lora_B.default.weight'][0]
+        ops.lora_down(dY, self.LBT[kind][i], self.DUr, M=M, K=n_out, r=r, scale=1.0, ldu=16)
+        dx = self.DH if kind == 'fc2' else self.DU
+        ops.lora_dx(dx, self.DUr, self.LA[kind][i], M=M, K=k_in, r=r, scale=s, p=p, seed=seed, tag=tag, lddu=16, aux=aux, ldaux=ldaux)
+        ops.lora_wgrad(dY, x, G, self.lws, M=M, N=n_out, r=r, ldz=ldx, z_off=x_off_u, out_off=oB)
+        ops.lora_wgrad(x, self.DUr, G, self.lws, M=M, N=k_in, r=r, scale=s, p=p, seed=seed, tag=tag, ldy=ldx, ldz=16, out_off=oA, os_n=1, os_j=k_in)
+
+    def _backward_lora(self):
+        """backward of a LoRA model: data gradients through the frozen base (no weight-gradient GEMMs, no embedding gradients) plus
+        the adapter gradients into self.G_lora"""
+        cfg, var = self.cfg, self.var
+        P = var._pack(base=True)
+        py, C, depth, V, H = cfg.pyramid, cfg.C, cfg.depth, cfg.head_ld, cfg.H
+        L = py.L
+        T = var.compute_dtype
+        sv = self._saved
+        ada, dp1, dp2, B = (sv[k] for k in ('ada', 'dp1', 'dp2', 'B'))
+        M, r, rp = self.M, self.r, self.rp
+        hid = P['w_fc1'].shape[1]
+        n_ada = P['n_ada']
+        eps = cfg.norm_eps
+        from .spec import attention_levels
+        lvl_end, holes = attention_levels(cfg)
+        scale = float(cfg.attn_scale)
+        ah = depth * 6 * C
+        ws = self.ws
+        kc, kh = C + rp, hid + rp
+        self.dada.zero_()
+        ops.gemm(self.dlogits, self.WT['head'], self.DU, M=M, N=C, K=V)
+        ops.ln_modulate_bwd(self.Xs[depth], self.DU, ada, ah, n_ada, L, None, self.dX, self.dada, ah, ah + C, n_ada, M, C, eps, ws)
+        for i in reversed(range(depth)):
+            a0 = i * 6 * C
+            p_ = f'blocks.{i}.'
+            # FFN branch: fc2's data-gradient GEMM runs without its GELU' - cvar_lora_dx applies it after adding the branch's share
+            ops.gated_grad(self.dX, self.F2[i], ada, a0 + C, n_ada, dp2[i].contiguous() if dp2 is not None else None, self.DF, self.dada, a0 + C, n_ada, B, L, C, ws)
+            ops.gemm(self.DF, self.WT['fc2'], self.DH, M=M, N=hid, K=C, w_off=i * hid * C)
+            self._lora_grads_of(i, 'fc2', p_ + 'ffn.fc2', self.DF, C, self.Hha[i], hid, kh, hid, aux=self.Aa[i], ldaux=kh)
+            ops.gemm(self.DH, self.WT['fc1'], self.DU, M=M, N=C, K=hid, w_off=i * C * hid)
+            self._lora_grads_of(i, 'fc1', p_ + 'ffn.fc1', self.DH, hid, self.U2a[i], C, kc, C)
+            ops.ln_modulate_bwd(self.X1s[i], self.DU, ada, a0 + 3 * C, n_ada, L, self.dX, self.dX, self.dada, a0 + 3 * C, a0 + 5 * C, n_ada, M, C, eps, ws)
+            # attention branch
+            ops.gated_grad(self.dX, self.F1[i], ada, a0, n_ada, dp1[i].contiguous() if dp1 is not None else None, self.DF, self.dada, a0, n_ada, B, L, C, ws)
+            ops.gemm(self.DF, self.WT['proj'], self.DU, M=M, N=C, K=C, w_off=i * C * C)
+            self._lora_grads_of(i, 'proj', p_ + 'attn.proj', self.DF, C, self.Oa[i], C, kc, C)
+            ops.attention_bwd(self.arena[i], self.O[i], self.DU, self.LSE[i], self.DQKV, ws, B, H, L, L, scale, lvl_end, holes=holes)
+            if cfg.uses_cos_attn:
+                ops.cos_qk_norm_bwd(self.arena[i], self.DQKV, B, H, L, L, P['scale_mul'], self.NORMS[i], self.DSM, sm_off=i * H)
+            ops.gemm(self.DQKV, self.WT['qkv'], self.DU, M=M, N=C, K=3 * C, w_off=i * C * 3 * C)
+            ops.ln_modulate_bwd(self.Xs[i], self.DU, ada, a0 + 2 * C, n_ada, L, self.dX, self.dX, self.dada, a0 + 2 * C, a0 + 4 * C, n_ada, M, C, eps, ws)
+            if self.reducer is not None:
+                self.reducer.ready(i)
+        # adaLN generator adapters: dY = d ada (B rows), u_t in the columns of [cs | u_0 ... u_depth]
+        lo = self._lora
+        s, p, seed = lo['scale'], self._lp, self._lseed
+        dada_T = self.dada.to(T)
+        ld = C + self.Kx
+        for t in range(depth + 1):
+            n_out = 6 * C if t < depth else 2 * C
+            name = f'blocks.{t}.ada_lin.1' if t < depth else 'head_nm.ada_lin.1'
+            oA = self.lora_off[f'{name}.lora_A.default.weight'][0]
+            oB = self.lora_off[f'{name}.lora_B.default.weight'][0]
+            ops.lora_down(dada_T, self.LBT['ada'][t], self.DUa, M=B, K=n_out, r=r, scale=1.0, ldx=n_ada, x_off=t * 6 * C, lda=6 * C, ldu=16)
+            ops.lora_wgrad(dada_T, self.csa, self.G_lora, self.lws, M=B, N=n_out, r=r, ldy=n_ada, y_off=t * 6 * C, ldz=ld, z_off=C + 16 * t, out_off=oB)
+            ops.lora_wgrad(self.csa, self.DUa, self.G_lora, self.lws, M=B, N=C, r=r, scale=s, p=p, seed=seed, tag=self._tag(t, 'ada'), ldy=ld, ldz=16,
+                           out_off=oA, os_n=1, os_j=C)
+        if self.reducer is not None:
+            self.reducer.ready(depth)
+
+
     def _word_embed_grads(self, tok, B, L, fl, C, Mt, Mtp, src=None, src_has_first=True):
         """src: gradient rows of the word-embedded tokens - self.dX with L rows per sample of which the first fl are skipped, or a compact
         (B, L - fl, C) gather of them (separator models)"""
@@ -556,7 +815,8 @@ class FusedAdamW:
     def __init__(self, var, lr: float, betas=(0.9, 0.95), eps: float = 1e-8, weight_decay: float = 0.0, nowd_keys=NOWD_KEYS):
         self.var = var
         self.betas, self.eps = betas, eps
-        self.named = [(n, p) for n, p in var.named_parameters()]
+        self.lora = getattr(var, '_lora', None) is not None        # LoRA: the adapters only (the frozen base has no state and no step)
+        self.named = [(n, p) for n, p in var.named_parameters() if p.requires_grad or not self.lora]
         self.state = {n: (torch.zeros_like(p.data), torch.zeros_like(p.data)) for n, p in self.named}
         groups: Dict[str, dict] = {}                             # first-seen order, as filter_params (utils/lr_control.py:67-101)
         for n, p in self.named:
@@ -584,7 +844,8 @@ class FusedAdamW:
         group_of = {name: gi for gi, g in enumerate(self.param_groups) for name in g['names']}
         # bf16 compute: the update kernel also writes the rounded value of every weight MATRIX into its slot of the stacked GEMM-ready
         # copies (models.VAR._matrix_copies), so the step does not re-read the fp32 masters to rebuild them (stack + cast were 3.4 ms)
-        copies, fresh = self.var._matrix_copies() if self.fuse_copies and hasattr(self.var, '_matrix_copies') else ({}, ())
+        copies, fresh = (self.var._matrix_copies() if self.fuse_copies and hasattr(self.var, '_matrix_copies') and not self.lora
+                         else ({}, ()))
         if not set(copies) <= {name for name, _ in self.named}:
             copies, fresh = {}, ()
         sig = (tuple(p.data_ptr() for _, p in self.named) + tuple(grads[name].data_ptr() for name, _ in self.named) +
@@ -602,7 +863,7 @@ class FusedAdamW:
         if fresh:
             self.var._pack(fresh=fresh)                          # the matrices are current; biases / tables are rebuilt from the parameters
         else:
-            self.var._packed = None                              # GEMM-ready copies are refreshed lazily
+            self.var._packed = None                              # GEMM-ready copies are refreshed lazily (LoRA: re-merged with the new adapters)
         return self._out2
 
     # ---- wire format of torch.optim.AdamW.state_dict() (what train_control_var_hpu.py:420-447 saves and resumes)
@@ -725,7 +986,8 @@ class Trainer:
         if self.engine.reducer is not None:
             self.engine.reducer.wait()
         norm_coef = self.opt.step(self.engine.grads(), self.clip, self.world)
-        self.engine._transposed_weights()
+        if self.engine._lora is None:                # LoRA: the base weights (and their W^T copies) do not move
+            self.engine._transposed_weights()
         self.it += 1
         return dict(loss=loss, grad_norm=norm_coef[0], clip_coef=norm_coef[1], lr=max_lr, wd=max_wd, mask_first=mask_first)
 
@@ -750,7 +1012,7 @@ class _TeacherForcedFn(torch.autograd.Function):
         eng.dlogits[:, :eng.cfg.head_out].copy_(dlogits.reshape(eng.M, -1))
         eng.backward()
         g = eng.grads()
-        return (None, None, None, None, None) + tuple(g[n].clone() for n, _ in eng.var.named_parameters())
+        return (None, None, None, None, None) + tuple(g[n].clone() if n in g else None for n, _ in eng.var.named_parameters())
 
 
 def teacher_forced_with_grad(var, label_B, x, cond_type, mask_first: bool = True):

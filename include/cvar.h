@@ -341,6 +341,30 @@ int cvar_adamw_multi(const void* table_dev, int n_tensors, const float* lr_by_gr
                      float beta1, float beta2, float eps, int step, const float* gscale_dev, float gscale, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * LoRA adapter branch (ABI 21; peft's LoRA Linear as train_control_var.py:337-353 configures it; controlvar_amd/lora.py).  A target
+ * computes y = x W^T + b + s * (drop(x) A^T) B^T with A [r][K], B [N][r], r <= 16.  The base GEMM with its fused epilogue is cvar_gemm over
+ * the K-augmented operands [x | u] and [W | B]; these calls produce and consume the skinny M x r tensors.  drop: inverted dropout with
+ * keep probability 1 - p; the keep bit of (seed, tag, row, column) is a counter-based hash (forward and backward regenerate it, so it
+ * does not depend on launch order or tiling).  p = 0: no mask.  x, A, dx, aux: 16-byte aligned, leading dimensions multiples of 8, K % 8 == 0.
+ *   cvar_lora_down   u[m,j] = scale * sum_k drop(x)[m,k] A[j,k] (element type dtype, row stride ldu); x_copy (may be NULL) receives
+ *                    x unchanged in the same pass (the [x | u] operand of a producer that cannot write a wider row)
+ *   cvar_lora_dx     dx[m,k] = (dx[m,k] + scale * drop'(m,k) * sum_j du[m,j] A[j,k]) * (aux ? gelu_tanh'(aux[m,k]) : 1), in place;
+ *                    drop' = keep / (1 - p); dx has dx_dtype (bf16 needs dtype bf16), du / A / aux have dtype; du rows are 16 wide
+ *                    (lddu >= 16, 16-byte aligned; columns >= r are ignored)
+ *   cvar_lora_wgrad  out[n * os_n + j * os_j] = scale * sum_m drop(Y)[m,n] Z[m,j], j < r: dB = dY^T u (p = 0), dA = s du^T drop(x).
+ *                    Split-M fp32 partials in ws (cvar_lora_wgrad_ws_floats(M, N) floats; ws_floats = what the caller allocated)
+ *                    summed in a fixed order: bit-identical on every run.  N, ldy even
+ *   cvar_lora_dropout_mask  out[m,k] = keep bit as 1.0 / 0.0 (fp32, M x K) - the mask the three calls above apply */
+int cvar_lora_down(const void* x, int64_t ldx, const void* A, int64_t lda, void* u, int64_t ldu, void* x_copy, int64_t ld_copy, int M, int K,
+                   int r, int dtype, float scale, float p, uint64_t seed, uint32_t tag, void* stream);
+int cvar_lora_dx(void* dx, int64_t lddx, int dx_dtype, const void* du, int64_t lddu, const void* A, int64_t lda, const void* aux, int64_t ldaux,
+                 int M, int K, int r, int dtype, float scale, float p, uint64_t seed, uint32_t tag, void* stream);
+int64_t cvar_lora_wgrad_ws_floats(int M, int N);
+int cvar_lora_wgrad(const void* Y, int64_t ldy, const void* Z, int64_t ldz, int M, int N, int r, int dtype, float scale, float p, uint64_t seed,
+                    uint32_t tag, float* ws, int64_t ws_floats, float* out, int64_t os_n, int64_t os_j, void* stream);
+int cvar_lora_dropout_mask(float* out, int M, int K, float p, uint64_t seed, uint32_t tag, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Input pipeline of the tokenizer: what datasets/imagenetC.py:128-188 and
  * datasets/transforms_image.py:103-121 do on the CPU with PIL / torchvision.
  *

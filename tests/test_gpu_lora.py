@@ -1,0 +1,273 @@
+"""LoRA fine-tuning on the GPU (controlvar_amd/lora.py, csrc/lora.hip): adapter gradients against the fp32 oracle by the chain rule,
+the dropout branch op by op against torch autograd, the fused optimizer on the adapters, resume, and generation through merged weights."""
+import pytest
+import torch
+
+from controlvar_amd import lora, models, ops  # noqa: E402
+from controlvar_amd import train as T  # noqa: E402
+from controlvar_amd.spec import DEFAULT_PATCH_NUMS as PN, VaeConfig, VarConfig, phi_index_map  # noqa: E402
+from controlvar_amd.synth import synth_images, synth_vae_state  # noqa: E402
+from oracle import train_ref, var_ref  # noqa: E402
+from oracle.vqvae_ref import MSQuant  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+CFGS = {'control': VarConfig(depth=2), 'var': VarConfig(depth=2, mask_factor=1, control=False, multi_cond=False),
+        'cos': VarConfig(depth=30, embed_dim=128, num_heads=2)}
+
+
+def make(cfg, dtype, dev, seed=0):
+    vae = models.build_vae(ch=32, compute_dtype=dtype).to(dev)
+    if cfg.control:
+        m = models.ControlVAR(vae, depth=cfg.depth, embed_dim=cfg.C, num_heads=cfg.H, mask_factor=2, multi_cond=True, patch_nums=PN,
+                              compute_dtype=dtype, cond_drop_rate=0.0, init_seed=seed)
+    else:
+        m = models.VAR(vae, depth=cfg.depth, embed_dim=cfg.C, num_heads=cfg.H, patch_nums=PN, compute_dtype=dtype, cond_drop_rate=0.0, init_seed=seed)
+    return vae, m.to(dev)
+
+
+def make_lora(cfg, dtype, dev, dropout=0.0, b_seed=3, b_std=0.05):
+    """LoRA model with random non-zero B (B = 0 would make every dA zero and hide the branch)"""
+    vae, m = make(cfg, dtype, dev)
+    lora.add_lora(m, dropout=dropout, seed=1)
+    g = torch.Generator().manual_seed(b_seed)
+    with torch.no_grad():
+        for _, (_, B) in lora.adapters(m).items():
+            B.copy_(torch.randn(B.shape, generator=g) * b_std)
+    return vae, m
+
+
+def cpu_state(m):
+    return {k: v.detach().cpu() for k, v in m.state_dict().items()}
+
+
+def expected_adapter_grads(m, grads_eff):
+    """chain rule through W_eff = W + s B A: dB = s dW_eff A^T, dA = s B^T dW_eff"""
+    s = m._lora['scale']
+    out = {}
+    for t, (A, B) in lora.adapters(m).items():
+        dW = grads_eff[t + '.weight'].double()
+        out[t + '.lora_B.default.weight'] = s * dW @ A.detach().cpu().double().t()
+        out[t + '.lora_A.default.weight'] = s * B.detach().cpu().double().t() @ dW
+    return out
+
+
+def batch(cfg, seed=5):
+    B, L, fl = 2, cfg.pyramid.L, cfg.pyramid.first_l
+    gen = torch.Generator().manual_seed(seed)
+    x = torch.randn(B, L - fl, 32, generator=gen)
+    tg = torch.randint(0, 4096, (B, L), generator=gen)
+    im = (torch.rand(B, L, generator=gen) > 0.3).float()
+    return x, tg, im, torch.tensor([5, 999]), torch.tensor([1, 3])
+
+
+@pytest.mark.parametrize('kind', ['control', 'var', 'cos', 'control_ignore'])
+def test_adapter_gradients_match_the_oracle_fp32(gpu_device, kind):
+    cfg = CFGS[kind.split('_')[0]]
+    vae, m = make_lora(cfg, torch.float32, gpu_device)
+    x, tg, im, cls, ty = batch(cfg)
+    im = im if kind.endswith('ignore') else None
+    sd_eff = lora.merged_state(cpu_state(m), m._lora)
+    loss_r, _, grads_r = train_ref.loss_and_grads(sd_eff, cfg, cls, x, ty if cfg.control else None, tg, im)
+    want = expected_adapter_grads(m, grads_r)
+    eng = T.TrainEngine(m, drop_path=False)
+    loss, _ = eng.forward_backward(cls, x.to(gpu_device), ty, tg.to(gpu_device), im.to(gpu_device) if im is not None else None)
+    assert abs(loss.item() - loss_r.item()) < 2e-5
+    grads = eng.grads()
+    assert set(grads) == set(want) == {n for n, p in m.named_parameters() if p.requires_grad}       # no frozen gradient
+    for n, w in want.items():
+        got = grads[n].cpu().double()
+        scale = max(1e-3, w.abs().max().item())
+        assert (got - w).abs().max().item() < 2e-3 * scale, (n, (got - w).abs().max().item(), scale)
+
+
+def test_adapter_gradients_bf16_close_to_the_fp32_oracle(gpu_device):
+    cfg = CFGS['control']
+    vae, m = make_lora(cfg, torch.bfloat16, gpu_device)
+    x, tg, _, cls, ty = batch(cfg)
+    sd_eff = lora.merged_state(cpu_state(m), m._lora)
+    loss_r, _, grads_r = train_ref.loss_and_grads(sd_eff, cfg, cls, x, ty, tg)
+    want = expected_adapter_grads(m, grads_r)
+    eng = T.TrainEngine(m, drop_path=False)
+    loss, _ = eng.forward_backward(cls, x.to(gpu_device), ty, tg.to(gpu_device))
+    assert abs(loss.item() - loss_r.item()) < 1e-2
+    for n, w in want.items():
+        got = eng.grads()[n].cpu().flatten().double()
+        ref = w.flatten()
+        cos = (got @ ref) / (got.norm() * ref.norm() + 1e-30)
+        assert cos > 0.99, (n, float(cos))
+
+
+def test_dropout_branch_op_level_against_autograd(gpu_device):
+    """down -> K-augmented GEMM -> dx -> wgrad of one target with p = 0.3, against torch autograd on the mask of ops.lora_dropout_mask"""
+    torch.manual_seed(0)
+    dev = gpu_device
+    M, K, N, r, rp = 1003, 256, 192, 16, 32
+    s, p, seed, tag = 2.0, 0.3, 1234, 7
+    x = torch.randn(M, K, device=dev)
+    A = torch.randn(r, K, device=dev) / 16
+    Bw = torch.randn(N, r, device=dev) / 4
+    W = torch.randn(N, K, device=dev) / 16
+    bias = torch.randn(N, device=dev)
+    dY = torch.randn(M, N, device=dev)
+    # forward through the kernels
+    xa = torch.zeros(M, K + rp, device=dev)
+    ops.lora_down(x, A, xa, M=M, K=K, r=r, scale=s, p=p, seed=seed, tag=tag, ldu=K + rp, u_off=K, x_copy=xa, ld_copy=K + rp)
+    Wa = torch.zeros(N, K + rp, device=dev)
+    Wa[:, :K], Wa[:, K:K + r] = W, Bw
+    y = torch.empty(M, N, device=dev)
+    ops.gemm(xa, Wa, y, M=M, N=N, K=K + rp, lda=K + rp, ldw=K + rp, bias=bias)
+    # backward through the kernels
+    dx = torch.empty(M, K, device=dev)
+    ops.gemm(dY, W.t().contiguous(), dx, M=M, N=K, K=N)
+    du = torch.empty(M, 16, device=dev)
+    BT = torch.zeros(16, N, device=dev)
+    BT[:r] = Bw.t()
+    ops.lora_down(dY, BT, du, M=M, K=N, r=r, scale=1.0, ldu=16)
+    ops.lora_dx(dx, du, A, M=M, K=K, r=r, scale=s, p=p, seed=seed, tag=tag, lddu=16)
+    ws = torch.empty(max(ops.lora_wgrad_ws_floats(M, N), ops.lora_wgrad_ws_floats(M, K)), device=dev)
+    dB = torch.empty(N, r, device=dev)
+    dA = torch.empty(r, K, device=dev)
+    ops.lora_wgrad(dY, xa, dB, ws, M=M, N=N, r=r, ldz=K + rp, z_off=K)
+    ops.lora_wgrad(xa, du, dA, ws, M=M, N=K, r=r, scale=s, p=p, seed=seed, tag=tag, ldy=K + rp, ldz=16, os_n=1, os_j=K)
+    # torch autograd on the same mask
+    mask = ops.lora_dropout_mask(M, K, p, seed, tag)
+    xt, At, Bt = (t.clone().double().requires_grad_(True) for t in (x, A, Bw))
+    yt = xt @ W.double().t() + bias.double() + s * ((xt * mask.double() / (1 - p)) @ At.t()) @ Bt.t()
+    yt.backward(dY.double())
+    rel = lambda a, b: ((a.double() - b).abs().max() / b.abs().max()).item()
+    assert rel(y, yt.detach()) < 1e-5
+    assert rel(dx, xt.grad) < 1e-5
+    assert rel(dA, At.grad) < 1e-5
+    assert rel(dB, Bt.grad) < 1e-5
+
+
+def test_dropout_mask_statistics_and_independence(gpu_device):
+    m0 = ops.lora_dropout_mask(1024, 1024, 0.05, 11, 0, device=gpu_device)
+    assert set(m0.unique().tolist()) <= {0.0, 1.0}
+    assert abs(m0.mean().item() - 0.95) < 2e-3
+    assert torch.equal(m0, ops.lora_dropout_mask(1024, 1024, 0.05, 11, 0, device=gpu_device))
+    for other in (ops.lora_dropout_mask(1024, 1024, 0.05, 11, 1, device=gpu_device),          # another target of the layer
+                  ops.lora_dropout_mask(1024, 1024, 0.05, 11, 4, device=gpu_device),          # the same target one layer on
+                  ops.lora_dropout_mask(1024, 1024, 0.05, 12, 0, device=gpu_device)):         # another seed
+        agree = (other == m0).float().mean().item()
+        assert agree < 0.95 * 0.95 + 0.05 * 0.05 + 5e-3                                      # independent masks agree by chance only
+
+
+def test_same_seed_gives_a_bit_identical_step(gpu_device):
+    cfg = CFGS['control']
+    vae, m = make_lora(cfg, torch.bfloat16, gpu_device, dropout=0.05)
+    m.train()
+    x, tg, _, cls, ty = batch(cfg)
+    eng = T.TrainEngine(m, drop_path=True)
+    run = lambda seed: (eng.forward_backward(cls, x.to(gpu_device), ty, tg.to(gpu_device), drop_seed=seed)[0].item(),
+                        {k: v.clone() for k, v in eng.grads().items()})
+    l1, g1 = run(21)
+    l2, g2 = run(21)
+    l3, g3 = run(22)
+    assert l1 == l2 and all(torch.equal(g1[k], g2[k]) for k in g1)
+    assert any(not torch.equal(g1[k], g3[k]) for k in g1)
+
+
+def test_trainer_step_updates_only_the_adapters(gpu_device):
+    cfg = CFGS['control']
+    vae, m = make_lora(cfg, torch.float32, gpu_device)
+    m.eval()
+    tr = T.Trainer(m, vae, peak_lr=2e-3, weight_decay=0.05, weight_decay_end=0.01, sche='lin0', warmup_it=20, max_it=1000, clip=2.0,
+                   wp0=0.005, wpe=0.01, drop_path=False)
+    tr.it = 7
+    images, masks = synth_images(2, 256, seed=6).to(gpu_device), synth_images(2, 256, seed=7).to(gpu_device)
+    cls, types = torch.tensor([17, 403]), torch.tensor([2, 0])
+    x, labels = tr.tokenize(images, masks, True)
+    before = cpu_state(m)
+    sd_eff = lora.merged_state(before, m._lora)
+    loss_r, _, grads_r = train_ref.loss_and_grads(sd_eff, cfg, cls, x.cpu(), types, labels.cpu())
+    want_g = expected_adapter_grads(m, grads_r)
+    out = tr.step(images, masks, cls, types, mask_first=True)
+    assert abs(out['loss'].item() - loss_r.item()) < 2e-5
+    assert len(tr.opt.named) == len(want_g) and [len(g['names']) for g in tr.opt.param_groups] == [len(want_g)]      # all adapters: group 'D'
+    norm = torch.sqrt(sum((g.double() ** 2).sum() for g in want_g.values())).item()
+    assert abs(out['grad_norm'].item() - norm) < 2e-3 * norm
+    coef = min(1.0, 2.0 / (norm + 1e-6))
+    after = cpu_state(m)
+    for k, v in before.items():
+        if k not in want_g:
+            assert torch.equal(after[k], v), k                                  # the frozen base stays bit for bit
+    for k, g in want_g.items():
+        p, _, _ = train_ref.adamw_update(before[k].double(), g * coef, torch.zeros_like(g), torch.zeros_like(g), 1, out['lr'], out['wd'])
+        assert (after[k].double() - p).abs().max().item() < 0.02 * out['lr'], k
+    sd = tr.opt.state_dict()
+    assert len(sd['state']) == len(want_g)
+
+
+def test_lora_resume_continues_bit_identically_in_both_layouts(gpu_device, tmp_path):
+    from controlvar_amd import checkpoint as ckpt
+    cfg = CFGS['control']
+    images, masks = synth_images(2, 256, seed=6).to(gpu_device), synth_images(2, 256, seed=7).to(gpu_device)
+    cls, types = torch.tensor([17, 403]), torch.tensor([2, 0])
+    kw = dict(peak_lr=2e-3, weight_decay=0.05, weight_decay_end=0.01, sche='lin0', warmup_it=2, max_it=50, clip=2.0, drop_path=False)
+    vae, m = make_lora(cfg, torch.bfloat16, gpu_device, dropout=0.05)
+    m.train()
+    tr = T.Trainer(m, vae, **kw)
+    for s in range(2):
+        tr.step(images, masks, cls, types, drop_seed=s, mask_first=True)
+    path = ckpt.save_checkpoint(m, tr.opt, epoch=0, step=tr.it, save_dir=str(tmp_path), latest=True)
+    peft = str(tmp_path / 'peft_layout.pth')                      # the same snapshot in the reference's peft key layout
+    torch.save({'model_state_dict': lora.lora_state_dict(m, 'peft'), 'optimizer_state_dict': tr.opt.state_dict(), 'epoch': 0, 'step': tr.it}, peft)
+    want = tr.step(images, masks, cls, types, drop_seed=2, mask_first=True)
+    want_sd = {k: v.clone() for k, v in m.state_dict().items()}
+    for src in (path, peft):
+        vae2, m2 = make_lora(cfg, torch.bfloat16, gpu_device, dropout=0.05, b_seed=9)
+        m2.train()
+        with torch.no_grad():
+            for p in m2.parameters():
+                p.add_(0.01)
+        tr2 = T.Trainer(m2, vae2, **kw)
+        steps, epoch = ckpt.resume(m2, tr2.opt, src)
+        assert steps == 2, src
+        tr2.it = steps
+        got = tr2.step(images, masks, cls, types, drop_seed=2, mask_first=True)
+        assert got['loss'].item() == want['loss'].item()
+        for k, v in m2.state_dict().items():
+            assert torch.equal(v, want_sd[k]), k
+
+
+def _greedy_tokens(m, labels, types):
+    m.autoregressive_infer_cfg(2, labels, g_seed=0, cfg=4.0, top_k=1, cond_type=types, _trace=True)
+    torch.cuda.synchronize()
+    return torch.cat(m.last_trace['idx'], dim=1).cpu().long()
+
+
+def _merged_copy(m, cfg, dev):
+    _, m2 = make(cfg, torch.float32, dev)
+    lora.add_lora(m2, dropout=m._lora['dropout'])
+    lora.load_lora(m2, lora.lora_state_dict(m, 'peft'))
+    lora.merge_lora(m2)
+    return m2.eval()
+
+
+def test_generation_runs_through_merged_weights(gpu_device):
+    cfg = CFGS['control']
+    vae, m = make_lora(cfg, torch.float32, gpu_device, dropout=0.05, b_std=0.2)
+    m.eval()
+    labels, types = torch.tensor([3, 7]), torch.tensor([0, 1])
+    ids = _greedy_tokens(m, labels, types)
+    assert torch.equal(ids, _greedy_tokens(_merged_copy(m, cfg, gpu_device), labels, types))
+    sd_eff = lora.merged_state(cpu_state(m), m._lora)
+    trace = {}
+    with torch.no_grad():
+        var_ref.generate(sd_eff, cfg, MSQuant(synth_vae_state(VaeConfig(ch=32)), PN, phi_index_map(10)), 2, labels, 4.0, top_k=1, cond_type=types,
+                         trace=trace)
+    assert torch.equal(ids, torch.cat(trace['idx'], dim=1).long())
+    # one optimizer step: the packed weights are re-merged with the new adapters
+    w_before = m._pack()['w_fc1'].clone()
+    tr = T.Trainer(m, vae, peak_lr=5e-2, weight_decay=0.0, sche='lin0', warmup_it=0, max_it=10, clip=0.0, drop_path=False)
+    images, masks = synth_images(2, 256, seed=6).to(gpu_device), synth_images(2, 256, seed=7).to(gpu_device)
+    tr.step(images, masks, torch.tensor([17, 403]), torch.tensor([2, 0]), mask_first=True)
+    m.eval()
+    assert not torch.equal(m._pack(check=True)['w_fc1'], w_before)
+    assert torch.equal(_greedy_tokens(m, labels, types), _greedy_tokens(_merged_copy(m, cfg, gpu_device), labels, types))
+    # the pixel-conditional branch runs on the LoRA model too
+    c_mask = vae.img_to_idxBl(masks)
+    img = m.conditional_infer_cfg(2, labels, g_seed=0, cfg=(4.0, 4.0, 4.0), top_k=1, cond_type=types, c_mask=c_mask)
+    assert img.shape[0] == 2 and torch.isfinite(img).all()
