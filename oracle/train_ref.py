@@ -22,10 +22,16 @@ def trainable_keys(cfg: VarConfig) -> List[str]:
 
 
 def loss_and_grads(sd: SD, cfg: VarConfig, cls: torch.Tensor, x_wo_first: torch.Tensor, cond_type: Optional[torch.Tensor],
-                   targets: torch.Tensor, ignore_mask: Optional[torch.Tensor] = None, prec=var_ref.FP32, mask_first: bool = True):
-    """-> (loss, per-token loss (B*L,), {key: grad}) with the reduction of train_control_var_hpu.py:228-239."""
-    leaf = {k: (v.detach().clone().requires_grad_(True) if k in set(trainable_keys(cfg)) else v) for k, v in sd.items()}
-    logits = var_ref.forward_logits(leaf, cfg, cls, x_wo_first, cond_type, prec, mask_first)
+                   targets: torch.Tensor, ignore_mask: Optional[torch.Tensor] = None, prec=var_ref.FP32, mask_first: bool = True,
+                   lora=None):
+    """-> (loss, per-token loss (B*L,), {key: grad}) with the reduction of train_control_var_hpu.py:228-239.
+    lora (oracle.lora_ref.LoraTerm): LoRA fine-tuning - the base in sd is frozen and the gradients are those of the adapters, by autograd."""
+    keys = set(trainable_keys(cfg)) if lora is None else set()
+    leaf = {k: (v.detach().clone().requires_grad_(True) if k in keys else v) for k, v in sd.items()}
+    if lora is not None:
+        for v in lora.params().values():
+            v.grad = None
+    logits = var_ref.forward_logits(leaf, cfg, cls, x_wo_first, cond_type, prec, mask_first, lora)
     loss_tok = F.cross_entropy(logits.view(-1, logits.size(-1)), targets.view(-1), reduction='none')
     if ignore_mask is not None:
         m = ignore_mask.view(-1).float()
@@ -33,7 +39,7 @@ def loss_and_grads(sd: SD, cfg: VarConfig, cls: torch.Tensor, x_wo_first: torch.
     else:
         loss = loss_tok.mean()
     loss.backward()
-    grads = {k: leaf[k].grad for k in trainable_keys(cfg)}
+    grads = {k: leaf[k].grad for k in trainable_keys(cfg)} if lora is None else lora.grads()
     return loss.detach(), loss_tok.detach(), grads
 
 
