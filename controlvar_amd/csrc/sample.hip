@@ -3,7 +3,8 @@
 //            control_var.py:295-298 / 501-502, so the combined logits are bit-identical to the reference's.
 //   greedy : argmax, lowest index on ties, plus the top1-top2 margin (used for margin-aware parity checks).
 //   sample : radix-select thresholds for top-k (ties kept, helpers.py:9-10) and the nucleus cut on the ascending
-//            cumulative mass (helpers.py:12-15), inverse-CDF draw from a counter-based generator (no sort).
+//            cumulative mass (helpers.py:12-15), inverse-CDF draw from a counter-based generator (no sort); or, with caller-drawn
+//            Exp(1) noise q, torch.multinomial's draw for one sample per row: argmax(p / q) over the softmax p of the masked logits.
 #include "cvar_common.h"
 
 struct SampleParams {
@@ -27,6 +28,9 @@ struct SampleParams {
     float smooth_mul, smooth_tau;
     const float* gumbel;                    // optional injected Gumbel noise [n_draw*B][l][V] (tests); NULL: drawn from the counter generator
     float* soft_out;
+    // ABI 22: caller-drawn Exp(1) noise [n_draw*B][l][V] (row stride V).  Non-NULL: the draw is torch.multinomial's one-sample path,
+    // argmax_v(softmax(masked)_v / expo_v) (the race), instead of the counter generator's inverse-CDF lookup
+    const float* expo;
 };
 
 __device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
@@ -120,9 +124,17 @@ __device__ __forceinline__ TV block_excl_scan(TV v, TV* wsum /*[4]*/, TV& total)
     return base + inc - v;
 }
 
+// argmax order of torch (first index on ties; a NaN beats every number, the first NaN wins): does (a, ia) come before (b, ib)?
+__device__ __forceinline__ bool race_before(float a, int ia, float b, int ib) {
+    const bool na = a != a, nb = b != b;
+    if (na || nb) return na && (!nb || ia < ib);
+    return a > b || (a == b && ia < ib);
+}
+
 // SOFT = false (every launch without more_smooth): the soft-embedding block and its registers compile away (146 -> ~90 VGPRs: the kernel is
-// bound by memory and LDS latency, and went 44 % slower when the block cost it two of its five waves per SIMD)
-template <bool SOFT>
+// bound by memory and LDS latency, and went 44 % slower when the block cost it two of its five waves per SIMD).
+// RACE = true (expo != NULL): the draw is torch.multinomial's one-sample path on the caller's noise; RACE = false compiles the counter draw only.
+template <bool SOFT, bool RACE>
 __global__ __launch_bounds__(256) void cfg_sample_kernel(const SampleParams p) {
     constexpr int EPT = 16;
     typedef unsigned long long u64;
@@ -255,21 +267,68 @@ __global__ __launch_bounds__(256) void cfg_sample_kernel(const SampleParams p) {
         (void)block_excl_scan<int>(nkeep, wsum32, tot);
         if (tid == 0) p.kept[bt] = tot;
     }
-    for (int d = 0; d < p.n_draw; ++d) {
-        unsigned long long h = splitmix64((p.seed + (p.seed_dev ? p.seed_dev[0] : 0ull)) ^ 0xC0FFEE1234ull);
-        h = splitmix64(h ^ ((unsigned long long)p.stage << 48) ^ ((unsigned long long)((long)d * p.B + b) << 16) ^ (unsigned long long)t);
-        const double u = (double)(h >> 11) * (1.0 / 9007199254740992.0);       // 53 bits -> [0,1)
-        u64 target = (u64)(u * (double)Zk);
-        if (target >= Zk) target = Zk > 0 ? Zk - 1 : 0;
-        if (excl <= target && target < excl + keepsum) {                        // exactly one thread
-            u64 run = excl;
-            int pick = tid;
+    if constexpr (RACE) {
+        // torch.multinomial(softmax(masked), 1, generator) = argmax_v(p_v / q_v) with q = empty_like(p).exponential_(generator) (ATen's
+        // one-sample path): the same IEEE fp32 steps as softmax then div - p_v = expf(x_v - m) / S over the kept v, 0 elsewhere (the -inf
+        // of the masked logits), then p_v / q_v over ALL V columns, so that 0 / 0 (a masked v meeting q_v = 0) is a NaN and wins as in torch.
+        // m = vmax (the maximum is always kept).  The kept set is the value threshold above: top-k ties kept, top_k == 1 keeps every maximum.
+        __shared__ float red_s[4], rmax[4];
+        __shared__ int ridx[4];
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < EPT; ++i)
+            if (i * 256 + tid < p.V && key[i] >= thr) s = __fadd_rn(s, expf(__fsub_rn(v[i], vmax)));
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s = __fadd_rn(s, __shfl_xor(s, o, 64));
+        if ((tid & 63) == 0) red_s[tid >> 6] = s;
+        __syncthreads();
+        const float S = __fadd_rn(__fadd_rn(red_s[0], red_s[1]), __fadd_rn(red_s[2], red_s[3]));
+        for (int d = 0; d < p.n_draw; ++d) {
+            const long row = (long)d * p.B + b;
+            const float* q = p.expo + (row * p.l + t) * (long)p.V;
+            float best_r = -INFINITY;
+            int best_i = 0x7fffffff;
 #pragma unroll
             for (int i = 0; i < EPT; ++i) {
-                run += wq[i];
-                if (run > target) { pick = i * 256 + tid; break; }
+                const int e = i * 256 + tid;
+                if (e < p.V) {
+                    const float pv = key[i] >= thr ? __fdiv_rn(expf(__fsub_rn(v[i], vmax)), S) : 0.f;
+                    const float r = __fdiv_rn(pv, q[e]);
+                    if (race_before(r, e, best_r, best_i)) { best_r = r; best_i = e; }
+                }
             }
-            p.idx_out[((long)d * p.B + b) * p.l + t] = pick;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const float orr = __shfl_xor(best_r, o, 64);
+                const int oi = __shfl_xor(best_i, o, 64);
+                if (race_before(orr, oi, best_r, best_i)) { best_r = orr; best_i = oi; }
+            }
+            __syncthreads();                               // rmax / ridx of the previous draw are read
+            if ((tid & 63) == 0) { rmax[tid >> 6] = best_r; ridx[tid >> 6] = best_i; }
+            __syncthreads();
+            if (tid == 0) {
+                for (int w = 1; w < 4; ++w)
+                    if (race_before(rmax[w], ridx[w], best_r, best_i)) { best_r = rmax[w]; best_i = ridx[w]; }
+                p.idx_out[row * p.l + t] = best_i;
+            }
+        }
+    } else {
+        for (int d = 0; d < p.n_draw; ++d) {
+            unsigned long long h = splitmix64((p.seed + (p.seed_dev ? p.seed_dev[0] : 0ull)) ^ 0xC0FFEE1234ull);
+            h = splitmix64(h ^ ((unsigned long long)p.stage << 48) ^ ((unsigned long long)((long)d * p.B + b) << 16) ^ (unsigned long long)t);
+            const double u = (double)(h >> 11) * (1.0 / 9007199254740992.0);       // 53 bits -> [0,1)
+            u64 target = (u64)(u * (double)Zk);
+            if (target >= Zk) target = Zk > 0 ? Zk - 1 : 0;
+            if (excl <= target && target < excl + keepsum) {                        // exactly one thread
+                u64 run = excl;
+                int pick = tid;
+#pragma unroll
+                for (int i = 0; i < EPT; ++i) {
+                    run += wq[i];
+                    if (run > target) { pick = i * 256 + tid; break; }
+                }
+                p.idx_out[((long)d * p.B + b) * p.l + t] = pick;
+            }
         }
     }
     if constexpr (SOFT) {
@@ -344,13 +403,14 @@ extern "C" int cvar_cfg_sample(const float* logits, int B, int nrep, int l, int 
                                int top_k, float top_p, uint64_t seed, const uint64_t* seed_dev, int stage, int n_draw,
                                int32_t* idx_out, float* combined, float* margin, int32_t* kept, int ldv,
                                const float* codebook, int Cvae, float smooth_mul, float smooth_tau, const float* gumbel, float* soft_out,
-                               void* stream) {
+                               const float* expo, void* stream) {
     if (!logits || !coef_host || !idx_out || B <= 0 || l <= 0 || V <= 1) return CVAR_EINVAL;
     if (nrep < 1 || nrep > 4 || n_draw < 1 || n_draw > 4 || V > 4096) return CVAR_EUNSUPPORTED;
     if (ldv != 0 && ldv < V) return CVAR_EINVAL;
     if (soft_out && (!codebook || Cvae < 1 || Cvae > 32 || !(smooth_tau > 0.f))) return CVAR_EINVAL;
     if (soft_out && top_k == 1) return CVAR_EUNSUPPORTED;          // greedy: the masked softmax is one-hot, the soft embedding IS codebook[idx]
     SampleParams p;
+    p.expo = expo;
     p.ldv = ldv ? ldv : V;
     p.codebook = codebook; p.Cvae = Cvae; p.smooth_mul = smooth_mul; p.smooth_tau = smooth_tau; p.gumbel = gumbel; p.soft_out = soft_out;
     p.logits = logits; p.B = B; p.nrep = nrep; p.l = l; p.V = V;
@@ -358,9 +418,12 @@ extern "C" int cvar_cfg_sample(const float* logits, int B, int nrep, int l, int 
     p.top_k = top_k; p.top_p = top_p; p.seed = seed; p.seed_dev = (const unsigned long long*)seed_dev; p.stage = stage; p.n_draw = n_draw;
     p.idx_out = idx_out; p.combined = combined; p.margin = margin; p.kept = kept;
     dim3 grid((unsigned)((long)B * l)), block(256);
-    if (top_k == 1) hipLaunchKernelGGL(cfg_greedy_kernel, grid, block, 0, as_stream(stream), p);
-    else if (soft_out) hipLaunchKernelGGL(cfg_sample_kernel<true>, grid, block, 0, as_stream(stream), p);
-    else hipLaunchKernelGGL(cfg_sample_kernel<false>, grid, block, 0, as_stream(stream), p);
+    if (expo) {                                                    // the race, top_k == 1 included: every tied maximum is kept and drawn among
+        if (soft_out) hipLaunchKernelGGL((cfg_sample_kernel<true, true>), grid, block, 0, as_stream(stream), p);
+        else hipLaunchKernelGGL((cfg_sample_kernel<false, true>), grid, block, 0, as_stream(stream), p);
+    } else if (top_k == 1) hipLaunchKernelGGL(cfg_greedy_kernel, grid, block, 0, as_stream(stream), p);
+    else if (soft_out) hipLaunchKernelGGL((cfg_sample_kernel<true, false>), grid, block, 0, as_stream(stream), p);
+    else hipLaunchKernelGGL((cfg_sample_kernel<false, false>), grid, block, 0, as_stream(stream), p);
     CVAR_CHECK_LAUNCH();
     return CVAR_OK;
 }

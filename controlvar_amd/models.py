@@ -657,6 +657,82 @@ class VQVAE(nn.Module):
 FUSE_LN_BELOW = 4097       # passes with fewer rows ask proj / fc2 for the next op's adaLN (see _blocks_and_head); 2048 -> 4097: B = 8 63.0 -> 62.3 ms, B = 16 106.7 -> 106.0
 
 
+SAMPLERS = ('counter', 'torch')
+
+
+def torch_draw_schedule(cfg: VarConfig, B: int, *, label_B_none: bool, cond_type_none: bool, four_way: bool, more_smooth: bool
+                        ) -> List[Tuple[str, Tuple[int, ...]]]:
+    """Every call one generation of the reference makes on its generator, in its order, as (kind, shape) - sampler='torch' makes the same
+    calls, so the generator's state after a call equals the reference's:
+      ('labels', (B,))        label_B=None: multinomial(selecting_idx (1, num_classes), B, replacement=True)     control_var.py:248,377; var.py:164
+      ('cond_type', (B,))     autoregressive_infer_cfg of a multi_cond model, cond_type=None, B != 4: multinomial((1, 4) uniform, B, True)
+                              (control_var.py:392; the conditional form takes cond_type as given and draws none)
+      ('expo', (rows*l, V))   each sampling call: torch.multinomial's Exp(1) noise (its one-sample path), rows = B, or 4B after the
+                              conditional form's .repeat (control_var.py:306); l counts separator positions                helpers.py:19
+      ('gumbel', (rows, l, V))  more_smooth, after each sample (also at top_k == 1): exponential_ of gumbel_softmax_with_rng    helpers.py:26
+    The two-pass branch (separate_decoding without indep, control_var.py:428-485) samples the control half, then the image half, per scale."""
+    py = cfg.pyramid
+    out: List[Tuple[str, Tuple[int, ...]]] = []
+    if label_B_none:
+        out.append(('labels', (B,)))
+    if cfg.mask_factor == 2 and not four_way and cond_type_none and B != 4:
+        out.append(('cond_type', (B,)))
+    if cfg.separate_decoding and not cfg.indep and not four_way:
+        passes = [(B, pn * pn) for pn in py.patch_nums for _ in (0, 1)]
+    else:
+        passes = [(4 * B if four_way else B, l) for l in py.l]
+    for rows, l in passes:
+        out.append(('expo', (rows * l, cfg.vocab)))
+        if more_smooth:
+            out.append(('gumbel', (rows, l, cfg.vocab)))
+    return out
+
+
+def torch_draw(kind: str, shape: Tuple[int, ...], generator: Optional[torch.Generator], device, num_classes: int) -> torch.Tensor:
+    """One entry of torch_draw_schedule, drawn as the reference draws it (generator None: the device's default generator)"""
+    if kind in ('labels', 'cond_type'):
+        n = num_classes if kind == 'labels' else 4
+        probs = torch.full((1, n), fill_value=1 / n, dtype=torch.float32, device=device)
+        return torch.multinomial(probs, num_samples=shape[0], replacement=True, generator=generator).reshape(shape[0])
+    e = torch.empty(shape, dtype=torch.float32, device=device).exponential_(generator=generator)
+    if kind == 'expo':
+        return e
+    if kind == 'gumbel':
+        return -e.log()
+    raise ValueError(f'unknown draw kind {kind!r}')
+
+
+def _check_generator_device(gdev: torch.device, dev: torch.device):
+    """sampler='torch' draws on the model's device or on the CPU (then copies the noise over)"""
+    def norm(d):
+        d = torch.device(d)
+        return torch.device(d.type, torch.cuda.current_device()) if d.type == 'cuda' and d.index is None else d
+    if norm(gdev).type != 'cpu' and norm(gdev) != norm(dev):
+        raise ValueError(f"model.rng is a generator on {gdev}: sampler='torch' needs one on the model's device ({dev}) or on the CPU")
+
+
+class _TorchDraws:
+    """Hands out the draws of a torch_draw_schedule in order, on the model's device; a request out of order is a bug and raises."""
+
+    def __init__(self, schedule, generator, gdev, dev, num_classes):
+        self.schedule, self.generator, self.gdev, self.dev, self.num_classes = schedule, generator, gdev, dev, num_classes
+        self.pos = 0
+
+    def next_kind(self) -> Optional[str]:
+        return self.schedule[self.pos][0] if self.pos < len(self.schedule) else None
+
+    def take(self, kind: str, shape: Tuple[int, ...]) -> torch.Tensor:
+        want = self.schedule[self.pos] if self.pos < len(self.schedule) else None
+        if want != (kind, tuple(shape)):
+            raise RuntimeError(f'torch sampler: draw {self.pos} is {(kind, tuple(shape))}, the schedule has {want}')
+        self.pos += 1
+        return torch_draw(kind, tuple(shape), self.generator, self.gdev, self.num_classes).to(self.dev).contiguous()
+
+    def finish(self):
+        if self.pos != len(self.schedule):
+            raise RuntimeError(f'torch sampler: {len(self.schedule) - self.pos} scheduled draws were not taken')
+
+
 class ControlVAR(nn.Module):
     """Joint (control, image) next-scale transformer (reference: models/control_var.py:23-689).
 
@@ -678,13 +754,25 @@ class ControlVAR(nn.Module):
                  drop_path_rate=0., layer_scale=-1., tau=4, cos_attn=False, patch_nums=DEFAULT_PATCH_NUMS,
                  flash_if_available=True, fused_if_available=True, mask_factor=2, bidirectional=False, separate_decoding=False,
                  separator=False, type_pos=False, indep=True, multi_cond=False,
-                 compute_dtype=None, init_seed: int = 0, deterministic_plan: bool = False):
+                 compute_dtype=None, init_seed: int = 0, deterministic_plan: bool = False, sampler: str = 'counter'):
         """deterministic_plan (an addition of this library): every transformer GEMM runs on the unsliced tile kernels whatever its row count - no small-M weight-streaming
         kernel, no K slices - so the fp32 summation order of a row does not depend on how many rows ride beside it, and one (label, condition, g_seed) in batch row 0 gives
         the same logits and tokens BIT FOR BIT at any batch size (default False: the small-M plans are 2.0x / 1.24x / 1.05x faster at B = 1 / 8 / 32 and move bf16 logits by ~5e-3 of
-        max|logit| between batch sizes; tests/test_gpu_configs.py).  Can also be flipped on a built model: ``model.deterministic_plan = True``."""
+        max|logit| between batch sizes; tests/test_gpu_configs.py).  Can also be flipped on a built model: ``model.deterministic_plan = True``.
+
+        sampler (an addition of this library; also settable: ``model.sampler = 'torch'``) picks where a sampled draw (top_k != 1) comes from:
+          'counter' (default): the library's own counter-based generator keyed by (g_seed, scale, row) - no host work, capturable by
+                     graphed_generator, a sample's draw independent of the batch it rides in;
+          'torch':   the reference's generator calls (torch_draw_schedule): torch.multinomial's Exp(1) noise and more_smooth's Gumbel noise are
+                     drawn with torch on ``model.rng`` (reseeded by g_seed; g_seed=None: the device's default generator) and the HIP
+                     sampler races argmax(p / q) on them - the same tokens as the reference given the same logits and generator state.
+                     As upstream, a sample's draw then depends on the batch it rides in (deterministic_plan's batch independence covers
+                     the logits and greedy ids only); graphed_generator refuses this mode."""
         super().__init__()
         self.deterministic_plan = bool(deterministic_plan)
+        self.sampler = sampler
+        self._rng: Optional[torch.Generator] = None
+        self._rng_assigned = False
         if separator and not (self._control and mask_factor == 2):
             raise NotImplementedError('separator needs the joint (control, image) sequence')
         if separator and len(patch_nums) != 10:
@@ -751,6 +839,30 @@ class ControlVAR(nn.Module):
     @property
     def device(self):
         return self.pos_1LC.device
+
+    @property
+    def sampler(self) -> str:
+        return self._sampler
+
+    @sampler.setter
+    def sampler(self, value: str):
+        if value not in SAMPLERS:
+            raise ValueError(f'sampler must be one of {SAMPLERS}, got {value!r}')
+        self._sampler = value
+
+    @property
+    def rng(self) -> torch.Generator:
+        """The generator of sampler='torch' (control_var.py:68), created on the model's device when first used.  A generator assigned by the
+        user stays as given; a CPU one is allowed (the noise is drawn on the CPU and copied over: CPU recordings, small batches)."""
+        if self._rng is None or (not self._rng_assigned and self._rng.device != self.device):
+            self._rng = torch.Generator(device=self.device)
+        return self._rng
+
+    @rng.setter
+    def rng(self, generator: torch.Generator):
+        if not isinstance(generator, torch.Generator):
+            raise TypeError(f'model.rng must be a torch.Generator, got {type(generator).__name__}')
+        self._rng, self._rng_assigned = generator, True
 
     def _state_sig(self):
         return _tensor_sig(self)
@@ -1047,7 +1159,24 @@ class ControlVAR(nn.Module):
                   force_idx=None, trace: bool = False, gumbel=None):
         if top_k > self.cfg.vocab:                     # helpers.py:8-10: torch.topk raises on k > V; top_k <= 0 means no top-k filter
             raise RuntimeError(f'selected index k out of range (top_k={top_k} > vocabulary {self.cfg.vocab})')
-        seed = int(g_seed) if g_seed is not None else int(torch.empty((), dtype=torch.int64).random_().item())
+        draws = None
+        if self.sampler == 'torch':
+            # the reference's generator calls, in its order (torch_draw_schedule); g_seed=None: the device's default generator, as rng=None upstream
+            gen, gdev = None, self.device
+            if g_seed is not None:
+                gen = self.rng
+                _check_generator_device(gen.device, self.device)
+                gen.manual_seed(int(g_seed))
+                gdev = gen.device
+            draws = _TorchDraws(torch_draw_schedule(self.cfg, B, label_B_none=label_B is None, cond_type_none=cond_type is None, four_way=four_way,
+                                                    more_smooth=bool(more_smooth)), gen, gdev, self.device, self.num_classes)
+            if draws.next_kind() == 'labels':
+                label_B = draws.take('labels', (B,))
+            if draws.next_kind() == 'cond_type':
+                cond_type = draws.take('cond_type', (B,))
+            seed = int(g_seed) if g_seed is not None else 0          # the counter generator's key: unused by the race
+        else:
+            seed = int(g_seed) if g_seed is not None else int(torch.empty((), dtype=torch.int64).random_().item())
         self._pack(check=True); self.vae_proxy[0]._pack(check=True)
         for name, ids in (('c_mask', c_mask), ('c_img', c_img), ('_force_idx', force_idx)):
             if ids is not None:
@@ -1064,14 +1193,20 @@ class ControlVAR(nn.Module):
                                       'shape error (:481) and more_smooth slices the soft embeddings at shifted positions upstream; only forward(), training '
                                       'and the joint autoregressive_infer_cfg branch are built')
         if self.cfg.separate_decoding and not self.cfg.indep and not four_way:              # control_var.py:428-485
-            return self._generate_two_pass(B, labels_all, types_all, seed, cfg_scale, top_k, top_p, bool(more_smooth), force_idx, trace, mask_first, gumbel)
-        return self._generate_core(B, labels_all, types_all, seed, None, cfg_scale, top_k, top_p, four_way, c_mask, c_img, force_idx, trace,
-                                   mask_first=mask_first, more_smooth=bool(more_smooth), gumbel=gumbel)
+            f_hat = self._generate_two_pass(B, labels_all, types_all, seed, cfg_scale, top_k, top_p, bool(more_smooth), force_idx, trace, mask_first,
+                                            gumbel, draws=draws)
+        else:
+            f_hat = self._generate_core(B, labels_all, types_all, seed, None, cfg_scale, top_k, top_p, four_way, c_mask, c_img, force_idx, trace,
+                                        mask_first=mask_first, more_smooth=bool(more_smooth), gumbel=gumbel, draws=draws)
+        if draws is not None:
+            draws.finish()
+        return f_hat
 
     @torch.no_grad()
     def _generate_core(self, B, labels_all, types_all, seed, seed_dev, cfg_scale, top_k, top_p, four_way, c_mask=None, c_img=None,
-                       force_idx=None, trace: bool = False, mask_first: bool = True, more_smooth: bool = False, gumbel=None):
-        """the 10-scale loop on device-resident inputs only (capturable in a HIP graph: no host sync, static shapes)"""
+                       force_idx=None, trace: bool = False, mask_first: bool = True, more_smooth: bool = False, gumbel=None, draws=None):
+        """the 10-scale loop on device-resident inputs only (capturable in a HIP graph: no host sync, static shapes).
+        draws (sampler='torch'): the noise of each sampling call comes from the caller's torch generator (_TorchDraws)"""
         cfg, P = self.cfg, self._pack()
         vae: VQVAE = self.vae_proxy[0]
         py, mf, C = cfg.pyramid, cfg.mask_factor, cfg.C
@@ -1107,15 +1242,18 @@ class ControlVAR(nn.Module):
             idx = torch.empty(n_draw * B, l, device=dev, dtype=torch.int32)
             comb = torch.empty(B, l, cfg.vocab, device=dev, dtype=torch.float32) if trace else None
             mg = torch.empty(B, l, device=dev, dtype=torch.float32) if trace else None
+            expo, g_si = self._torch_noise(draws, n_draw * B, l, more_smooth)
             soft = None
-            if more_smooth and top_k != 1:          # greedy: the in-place masked softmax is one-hot, i.e. exactly E[idx] (control_var.py:511-515)
+            if more_smooth and top_k != 1:
+                if gumbel is not None:
+                    g_si = gumbel[si].to(device=dev, dtype=torch.float32).contiguous()          # greedy: the in-place masked softmax is one-hot, i.e. exactly E[idx] (control_var.py:511-515)
                 soft = torch.empty(n_draw * B, l, cfg.cvae, device=dev, dtype=torch.float32)
                 ops.cfg_sample(logits, B, nrep, l, cfg.vocab, coef, top_k, top_p, seed, si, n_draw, idx, comb, mg, seed_dev=seed_dev, codebook=Pv['E'],
-                               smooth_mul=1.0 + ratio, smooth_tau=max(0.27 * (1 - ratio * 0.95), 0.005),
-                               gumbel=gumbel[si].to(device=dev, dtype=torch.float32).contiguous() if gumbel is not None else None, soft_out=soft,
-                               ldv=cfg.head_ld)
+                               smooth_mul=1.0 + ratio, smooth_tau=max(0.27 * (1 - ratio * 0.95), 0.005), gumbel=g_si, soft_out=soft,
+                               ldv=cfg.head_ld, expo=expo)
             else:
-                ops.cfg_sample(logits, B, nrep, l, cfg.vocab, coef, top_k, top_p, seed, si, n_draw, idx, comb, mg, seed_dev=seed_dev, ldv=cfg.head_ld)
+                ops.cfg_sample(logits, B, nrep, l, cfg.vocab, coef, top_k, top_p, seed, si, n_draw, idx, comb, mg, seed_dev=seed_dev, ldv=cfg.head_ld,
+                               expo=expo)
             if trace:
                 tr['idx'].append(idx.clone()); tr['margin'].append(mg); tr['logits'].append(comb)
             if force_idx is not None:
@@ -1151,7 +1289,7 @@ class ControlVAR(nn.Module):
         return f_hat[:B]
 
     @torch.no_grad()
-    def _generate_two_pass(self, B, labels_all, types_all, seed, cfg_scale, top_k, top_p, more_smooth, force_idx, trace, mask_first, gumbel):
+    def _generate_two_pass(self, B, labels_all, types_all, seed, cfg_scale, top_k, top_p, more_smooth, force_idx, trace, mask_first, gumbel, draws=None):
         """separate_decoding without indep (control_var.py:428-485): 2 x 10 passes over the same KV arena - per scale first the control
         tokens, then the image tokens, which see their scale's control tokens through the cache (attn_bias=None upstream).  The inputs
         cross over as upstream's do: the image pass of scale k is fed the CONTROL f_hat pooled to pn_k (:467-468), the control pass of
@@ -1187,14 +1325,16 @@ class ControlVAR(nn.Module):
             idx = torch.empty(B, l, device=dev, dtype=torch.int32)
             comb = torch.empty(B, l, cfg.vocab, device=dev, dtype=torch.float32) if trace else None
             mg = torch.empty(B, l, device=dev, dtype=torch.float32) if trace else None
+            expo, g_si = self._torch_noise(draws, B, l, more_smooth)
             soft = None
             if more_smooth and top_k != 1:
+                if gumbel is not None:
+                    g_si = gumbel[si].to(device=dev, dtype=torch.float32).contiguous()
                 soft = torch.empty(B, l, cfg.cvae, device=dev, dtype=torch.float32)
                 ops.cfg_sample(logits, B, 2, l, cfg.vocab, [1 + t, -t], top_k, top_p, seed, si, 1, idx, comb, mg, codebook=Pv['E'], smooth_mul=1.0 + ratio,
-                               smooth_tau=max(0.27 * (1 - ratio * 0.95), 0.005),
-                               gumbel=gumbel[si].to(device=dev, dtype=torch.float32).contiguous() if gumbel is not None else None, soft_out=soft)
+                               smooth_tau=max(0.27 * (1 - ratio * 0.95), 0.005), gumbel=g_si, soft_out=soft, expo=expo)
             else:
-                ops.cfg_sample(logits, B, 2, l, cfg.vocab, [1 + t, -t], top_k, top_p, seed, si, 1, idx, comb, mg)
+                ops.cfg_sample(logits, B, 2, l, cfg.vocab, [1 + t, -t], top_k, top_p, seed, si, 1, idx, comb, mg, expo=expo)
             if trace:
                 tr['idx'].append(idx.clone()); tr['margin'].append(mg); tr['logits'].append(comb)
             if force_idx is not None:
@@ -1211,6 +1351,15 @@ class ControlVAR(nn.Module):
             self.last_trace = tr
         return f_hat
 
+    def _torch_noise(self, draws: Optional[_TorchDraws], rows: int, l: int, more_smooth: bool):
+        """sampler='torch': (Exp(1) noise of the id draw, Gumbel noise of more_smooth) of one sampling call, drawn in that order as
+        helpers.py:19 then :26 draw them (the Gumbel noise also at top_k == 1, where it is dropped); (None, None) otherwise"""
+        if draws is None:
+            return None, None
+        expo = draws.take('expo', (rows * l, self.cfg.vocab))
+        g = draws.take('gumbel', (rows, l, self.cfg.vocab)) if more_smooth else None
+        return expo, g
+
     @torch.no_grad()
     def graphed_generator(self, B: int, cfg=1.5, top_k: int = 0, top_p: float = 0.0):
         """Capture one full `autoregressive_infer_cfg` (10 scales x depth blocks + both VQVAE decodes, ~2.5k launches) in a
@@ -1219,6 +1368,9 @@ class ControlVAR(nn.Module):
         Removes the host launch cost that dominates small batches (the reference's loop is host-launched op by op)."""
         dev = self.device
         four_way = False
+        if self.sampler == 'torch':
+            raise NotImplementedError("graphed_generator captures the counter sampler only: sampler='torch' draws its noise with torch on model.rng "
+                                      "between the launches; set model.sampler = 'counter' to capture, or call autoregressive_infer_cfg")
         if self.bidirectional:
             raise NotImplementedError('the captured generator fixes the (control, image) order; bidirectional models draw it per call')
         lab0 = torch.zeros(B, dtype=torch.int64)
@@ -1341,13 +1493,15 @@ class VAR(ControlVAR):
     def __init__(self, vae_local: VQVAE, num_classes=1000, norm_eps=1e-6, aln=1, aln_gamma_init=1e-3, shared_aln=False,
                  cond_drop_rate=0.1, depth=16, embed_dim=1024, num_heads=16, mlp_ratio=4., drop_rate=0., attn_drop_rate=0.,
                  drop_path_rate=0., layer_scale=-1., tau=4, cos_attn=False, patch_nums=DEFAULT_PATCH_NUMS,
-                 flash_if_available=True, fused_if_available=True, compute_dtype=None, init_seed: int = 0, deterministic_plan: bool = False):
+                 flash_if_available=True, fused_if_available=True, compute_dtype=None, init_seed: int = 0, deterministic_plan: bool = False,
+                 sampler: str = 'counter'):
         super().__init__(vae_local, num_classes=num_classes, norm_eps=norm_eps, aln=aln, aln_gamma_init=aln_gamma_init,
                          shared_aln=shared_aln, cond_drop_rate=cond_drop_rate, depth=depth, embed_dim=embed_dim, num_heads=num_heads,
                          mlp_ratio=mlp_ratio, drop_rate=drop_rate, attn_drop_rate=attn_drop_rate, drop_path_rate=drop_path_rate,
                          layer_scale=layer_scale, tau=tau, cos_attn=cos_attn, patch_nums=patch_nums,
                          flash_if_available=flash_if_available, fused_if_available=fused_if_available, mask_factor=1,
-                         multi_cond=False, compute_dtype=compute_dtype, init_seed=init_seed, deterministic_plan=deterministic_plan)
+                         multi_cond=False, compute_dtype=compute_dtype, init_seed=init_seed, deterministic_plan=deterministic_plan,
+                         sampler=sampler)
 
     @torch.no_grad()
     def autoregressive_infer_cfg(self, B: int, label_B, g_seed: Optional[int] = None, cfg=1.5, top_k=0, top_p=0.0,

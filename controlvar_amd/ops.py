@@ -239,12 +239,17 @@ def cfg_sample(logits: torch.Tensor, B: int, nrep: int, l: int, V: int, coef: Se
                seed: int, stage: int, n_draw: int, idx_out: torch.Tensor, combined: Optional[torch.Tensor] = None,
                margin: Optional[torch.Tensor] = None, kept: Optional[torch.Tensor] = None, seed_dev: Optional[torch.Tensor] = None,
                ldv: int = 0, codebook: Optional[torch.Tensor] = None, smooth_mul: float = 1.0, smooth_tau: float = 1.0,
-               gumbel: Optional[torch.Tensor] = None, soft_out: Optional[torch.Tensor] = None):
+               gumbel: Optional[torch.Tensor] = None, soft_out: Optional[torch.Tensor] = None, expo: Optional[torch.Tensor] = None):
+    """expo: Exp(1) noise (n_draw*B, l, V) fp32 contiguous, drawn by the caller (``torch.empty(...).exponential_(generator=g)``); the draw is
+    then torch.multinomial's on the same noise, argmax(softmax(masked) / expo) (include/cvar.h)"""
+    if expo is not None and (expo.dtype != torch.float32 or not expo.is_contiguous() or expo.numel() != n_draw * B * l * V
+                             or expo.device != logits.device):
+        raise ValueError(f'cfg_sample: expo must be a contiguous float32 ({n_draw * B}, {l}, {V}) tensor on {logits.device}')
     arr = (C.c_float * 4)(*(list(coef) + [0.0] * (4 - len(coef))))
     check(_lib.load().cvar_cfg_sample(_ptr(logits), B, nrep, l, V, arr, top_k, float(top_p), int(seed) & (2 ** 64 - 1), _ptr(seed_dev), stage, n_draw,
                                       _ptr(idx_out), _ptr(combined), _ptr(margin), _ptr(kept), int(ldv), _ptr(codebook),
                                       codebook.shape[1] if codebook is not None else 0, float(smooth_mul), float(smooth_tau), _ptr(gumbel), _ptr(soft_out),
-                                      _stream()), 'cvar_cfg_sample')
+                                      _ptr(expo), _stream()), 'cvar_cfg_sample')
     return idx_out
 
 

@@ -359,18 +359,22 @@ _define('cos_qk_norm_', '(Tensor(a!) qkv, int H, int q_off, int l, Tensor scale_
 
 
 # ------------------------------------------------------------------------------------------------------------------- sampler
-def _cfg_sample(logits, B, nrep, coef, top_k, top_p, seed, stage, n_draw=1):
-    """logits (nrep*B, l, V) fp32 -> ids (n_draw*B, l) int32 (control_var.py:295-307,501-505; helpers.py:6-19)"""
+def _cfg_sample(logits, B, nrep, coef, top_k, top_p, seed, stage, n_draw=1, expo=None):
+    """logits (nrep*B, l, V) fp32 -> ids (n_draw*B, l) int32 (control_var.py:295-307,501-505; helpers.py:6-19).
+    expo (optional, (n_draw*B*l, V) or (n_draw*B, l, V) fp32): Exp(1) noise drawn by the caller on its torch generator; the draw is then
+    torch.multinomial's on that noise (include/cvar.h) instead of the counter generator's"""
     if logits.dtype != torch.float32 or logits.dim() != 3 or logits.shape[0] != nrep * B:
         raise ValueError('cfg_sample: logits must be float32 (nrep*B, l, V)')
     _, l, V = logits.shape
     idx = torch.empty(n_draw * B, l, device=logits.device, dtype=torch.int32)
-    K.cfg_sample(logits.contiguous(), B, nrep, l, V, list(coef), top_k, top_p, seed, stage, n_draw, idx)
+    K.cfg_sample(logits.contiguous(), B, nrep, l, V, list(coef), top_k, top_p, seed, stage, n_draw, idx,
+                 expo=expo.contiguous() if expo is not None else None)
     return idx
 
 
-_define('cfg_sample', '(Tensor logits, int B, int nrep, float[] coef, int top_k, float top_p, int seed, int stage, int n_draw=1) -> Tensor', _cfg_sample,
-        lambda logits, B, nrep, coef, top_k, top_p, seed, stage, n_draw=1: logits.new_empty(n_draw * B, logits.shape[1], dtype=torch.int32))
+_define('cfg_sample', '(Tensor logits, int B, int nrep, float[] coef, int top_k, float top_p, int seed, int stage, int n_draw=1, Tensor? expo=None) -> Tensor',
+        _cfg_sample,
+        lambda logits, B, nrep, coef, top_k, top_p, seed, stage, n_draw=1, expo=None: logits.new_empty(n_draw * B, logits.shape[1], dtype=torch.int32))
 
 
 # ------------------------------------------------------------------------------------------------------------------- quantizer pyramid

@@ -205,12 +205,19 @@ int cvar_cos_qk_norm_bwd(const void* qkv, void* dqkv, int dtype, int R, int H, i
  * more_smooth (control_var.py:326-330,459-463,511-515; helpers.py:22-36), sampling mode only: with soft_out != NULL also
  *   soft_out[d*B + b][t][:] = softmax_v((combined_v * smooth_mul + g_v) / smooth_tau) . codebook[v][:]  over the top-k / top-p KEPT v
  * (the reference masks its logits in place before the Gumbel softmax); g = Gumbel noise, injected ([n_draw*B][l][V]) or drawn from
- * the counter-based generator. */
+ * the counter-based generator.
+ * expo (ABI 22, optional): caller-drawn Exp(1) noise q [n_draw*B][l][V] fp32, row stride V (torch's exponential_ on the caller's
+ *   generator).  Non-NULL replaces the counter-based draw by torch.multinomial's one-sample path (helpers.py:19):
+ *     p_v = expf(x_v - m) / S over the top-k / top-p kept v (m = max, S = sum of expf(x_v - m) over the kept v), p_v = 0 otherwise;
+ *     idx = argmax_v (p_v / q_v) over all V columns, first index on ties, a NaN wins (the first NaN: 0 / 0 where a masked v meets q_v = 0).
+ *   Every step is one IEEE fp32 operation (accurate expf, rounded division), as torch's softmax then div.  top_k == 1 also takes this
+ *   path: every value tied with the maximum is kept and drawn among (kept = the number of tied maxima).  combined, margin, kept and
+ *   soft_out are computed as without expo; expo == NULL leaves every existing path unchanged. */
 int cvar_cfg_sample(const float* logits, int B, int nrep, int l, int V, const float* coef_host,
                     int top_k, float top_p, uint64_t seed, const uint64_t* seed_dev /* optional, added to seed */, int stage, int n_draw,
                     int32_t* idx_out, float* combined, float* margin, int32_t* kept, int ldv,
                     const float* codebook /* [V][Cvae] */, int Cvae, float smooth_mul, float smooth_tau, const float* gumbel, float* soft_out,
-                    void* stream);
+                    const float* expo /* optional [n_draw*B][l][V] */, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Token-pyramid helpers of VectorQuantizer2 (models/quant.py).
