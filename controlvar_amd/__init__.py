@@ -6,8 +6,9 @@ Heavy imports (torch, the HIP library) happen lazily so that ``import controlvar
 and the pure-host modules (spec, synth) work everywhere.
 """
 from . import spec  # noqa: F401
+from .spec import DEFAULT_PATCH_NUMS, PATCH_NUMS_512  # noqa: F401  (the 256 x 256 and the 512 x 512 scale lists)
 
-__all__ = ['VQVAE', 'VAR', 'ControlVAR', 'build_var', 'build_control_var', 'build_vae', 'spec', 'register_torch_ops']
+__all__ = ['VQVAE', 'VAR', 'ControlVAR', 'build_var', 'build_control_var', 'build_vae', 'spec', 'register_torch_ops', 'DEFAULT_PATCH_NUMS', 'PATCH_NUMS_512']
 
 
 def register_torch_ops():

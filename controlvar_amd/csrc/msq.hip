@@ -10,6 +10,11 @@
 constexpr int MS_C = 32;       // Cvae
 constexpr int MS_S = 16;       // largest scale
 constexpr int MS_MAP = MS_C * MS_S * MS_S;   // floats per map
+constexpr int M32_S = 32;      // the second latent size (512 x 512 images): kernels of their own further down
+struct MsEncodeParams;
+static int ms32_next_input(const int* idx, const float* E, const float* phi_w, const float* phi_b, const float* up, const float* down, float* f_hat,
+                           float* tok_out, int nb, int nmaps, int pn, int pn_next, hipStream_t st);
+static int ms32_encode(const MsEncodeParams& p, int B, hipStream_t st);
 
 // u <- bicubic_up(E[idx]) (or the plain gather when pn == S).  hs / u alias is handled by the caller passing
 // distinct buffers: gather -> bufA ([C][pn][pn]); rows -> tmp ([C][S][pn]); cols -> bufA ([C][S][S]).
@@ -134,9 +139,10 @@ extern "C" int cvar_ms_next_input(const int32_t* idx, const float* codebook, con
                                   const float* up_mat, const float* down_mat, float* f_hat, float* tok_out,
                                   int nb, int nmaps, int pn, int pn_next, int S, int Cvae, void* stream) {
     if (!idx || !codebook || !phi_w || !phi_b || !f_hat || nb <= 0 || nmaps <= 0 || pn <= 0 || pn > S) return CVAR_EINVAL;
-    if (S != MS_S || Cvae != MS_C) return CVAR_EUNSUPPORTED;
+    if ((S != MS_S && S != M32_S) || Cvae != MS_C) return CVAR_EUNSUPPORTED;
     if (pn != S && !up_mat) return CVAR_EINVAL;
     if (tok_out && (pn_next <= 0 || pn_next > S || (pn_next != S && !down_mat))) return CVAR_EINVAL;
+    if (S == M32_S) return ms32_next_input(idx, codebook, phi_w, phi_b, up_mat, down_mat, f_hat, tok_out, nb, nmaps, pn, pn_next, as_stream(stream));
     const size_t lds = (3 * MS_MAP + MS_C * 9 * MS_C) * sizeof(float);        // three maps + the phi weights
     (void)hipFuncSetAttribute((const void*)ms_next_input_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(ms_next_input_kernel, dim3((unsigned)((long)nb * nmaps)), dim3(MS_NI_THREADS), lds, as_stream(stream), idx, codebook, phi_w, phi_b,
@@ -329,7 +335,7 @@ extern "C" int cvar_ms_encode(const float* f, const float* codebook, int V, cons
                               int B, int S, int Cvae, void* stream) {
     if (!f || !codebook || !phi_w || !phi_b || !phi_map_host || !patch_nums_host || !up_mats || !down_mats || !idx_out) return CVAR_EINVAL;
     if (B <= 0 || V <= 1 || nscale <= 0 || nscale > 16) return CVAR_EINVAL;
-    if (S != MS_S || Cvae != MS_C || patch_nums_host[nscale - 1] != S) return CVAR_EUNSUPPORTED;
+    if ((S != MS_S && S != M32_S) || Cvae != MS_C || patch_nums_host[nscale - 1] != S) return CVAR_EUNSUPPORTED;
     MsEncodeParams p;
     p.f = f; p.E = codebook; p.V = V; p.phi_w = phi_w; p.phi_b = phi_b; p.up = up_mats; p.down = down_mats;
     p.idx_out = idx_out; p.f_hat_out = f_hat_out; p.margin_out = margin_out; p.nscale = nscale;
@@ -342,6 +348,7 @@ extern "C" int cvar_ms_encode(const float* f, const float* codebook, int V, cons
         uo += S * pn; io += pn * pn;
     }
     p.Ltot = io;
+    if (S == M32_S) return ms32_encode(p, B, as_stream(stream));
     const size_t lds = 4 * MS_MAP * sizeof(float);
 #ifndef MS_ENCODE_W8
 #define MS_ENCODE_W8 1
@@ -355,6 +362,368 @@ extern "C" int cvar_ms_encode(const float* f, const float* codebook, int V, cons
     }
     (void)hipFuncSetAttribute((const void*)ms_encode_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(ms_encode_kernel<256>, dim3(B), dim3(256), lds, as_stream(stream), p);
+    CVAR_CHECK_LAUNCH();
+    return CVAR_OK;
+}
+
+// ================================================================================================
+// S = 32 (512 x 512 images): one [32][32][32] fp32 map is 128 KiB, so the S = 16 layout (three / four maps in LDS) does not carry over.
+// Still one workgroup per map, but only ONE map-sized LDS buffer ("M": z token-major during the search, u channel-major from the gather to phi)
+// and a 16 KiB staging area; everything else is owned by the thread that owns the pixel:
+//   next input (1 024 threads, one pixel each): phi accumulators (32) in registers, f_hat read / added / written in HBM by the owning thread;
+//   encode     (512 threads, two pixels each) : f_rest (2 x 32) in registers for the whole call, f_hat accumulated in f_hat_out by the owning thread
+//                                               (not kept at all when the caller does not ask for it: the ids depend on f_rest alone).
+// The separable passes run per group of two channels through the staging area ([2][pn][pn] + [2][S][pn] <= 15.3 KiB at pn = 31), the phi weights
+// come through it in chunks of 8 input channels (9 KiB).  Every output value is the fma chain of the S = 16 kernels (ascending source index;
+// bias, ci-major, tap-minor; ascending c) - a different split over threads, the same arithmetic.  DESIGN.md section 4b has the budget.
+constexpr int M32_PIX = M32_S * M32_S;           // 1 024 pixels
+constexpr int M32_MAP = MS_C * M32_PIX;          // 32 768 floats = 128 KiB
+constexpr int M32_STG = 4096;                    // staging floats (16 KiB)
+constexpr int M32_G = 2;                         // channels per separable-pass group
+constexpr int M32_WCI = 8;                       // input channels per staged phi weight chunk
+
+// M <- bicubic_up(E[idx]) as [C][S][S] (the plain gather when pn == S).  idx: global or LDS.
+template <int NTH>
+__device__ void m32_gather_up(const int* idx, const float* __restrict__ E, const float* __restrict__ up, float* M, float* stg, int pn) {
+    const int tid = threadIdx.x;
+    const int n = pn * pn;
+    if (pn == M32_S) {
+        for (int i = tid; i < M32_MAP; i += NTH) {
+            const int t = i / MS_C, c = i % MS_C;
+            M[c * M32_PIX + t] = E[(long)idx[t] * MS_C + c];
+        }
+        __syncthreads();
+        return;
+    }
+    float* g = stg;                      // [G][pn][pn]
+    float* r = stg + M32_G * n;          // [G][S][pn]
+    for (int c0 = 0; c0 < MS_C; c0 += M32_G) {
+        for (int i = tid; i < M32_G * n; i += NTH) {
+            const int c = i % M32_G, t = i / M32_G;
+            g[c * n + t] = E[(long)idx[t] * MS_C + c0 + c];
+        }
+        __syncthreads();
+        // rows: r[c][i][x] = sum_j up[i][j] * g[c][j][x]
+        for (int o = tid; o < M32_G * M32_S * pn; o += NTH) {
+            const int x = o % pn, i = (o / pn) % M32_S, c = o / (pn * M32_S);
+            float a = 0.f;
+            for (int j = 0; j < pn; ++j) a = fmaf(up[i * pn + j], g[c * n + j * pn + x], a);
+            r[o] = a;
+        }
+        __syncthreads();
+        // cols: u[c][i][i2] = sum_j up[i2][j] * r[c][i][j]   (the next group's gather / rows are fenced by its own two barriers)
+        for (int o = tid; o < M32_G * M32_PIX; o += NTH) {
+            const int i2 = o % M32_S, ci = o / M32_S;
+            float a = 0.f;
+            for (int j = 0; j < pn; ++j) a = fmaf(up[i2 * pn + j], r[ci * pn + j], a);
+            M[c0 * M32_PIX + o] = a;
+        }
+    }
+    __syncthreads();
+}
+
+// acc[q][co] = bias[co] + conv3x3(u)[co] at the thread's pixels tid + q * NTH, ci-major, tap-minor.  The weights ([ci][tap][co]) pass through stg in chunks.
+template <int NTH>
+__device__ __forceinline__ void m32_phi(const float* u, const float* __restrict__ w, const float* __restrict__ bias, float* stg,
+                                        float (&acc)[M32_PIX / NTH][MS_C]) {
+    constexpr int PPT = M32_PIX / NTH;
+    int y[PPT], x[PPT];
+#pragma unroll
+    for (int q = 0; q < PPT; ++q) {
+        const int pix = threadIdx.x + q * NTH;
+        y[q] = pix / M32_S; x[q] = pix % M32_S;
+#pragma unroll
+        for (int co = 0; co < MS_C; ++co) acc[q][co] = bias[co];
+    }
+    for (int ci0 = 0; ci0 < MS_C; ci0 += M32_WCI) {
+        __syncthreads();                                     // the staging area is free (previous chunk / the separable passes)
+        for (int o = threadIdx.x * 4; o < M32_WCI * 9 * MS_C; o += NTH * 4) *(f32x4_t*)(stg + o) = *(const f32x4_t*)(w + ci0 * 9 * MS_C + o);
+        __syncthreads();
+        for (int ci = 0; ci < M32_WCI; ++ci) {
+#pragma unroll 1                                              // unrolled, the 9 x 8 weight reads are hoisted and spill
+            for (int tap = 0; tap < 9; ++tap) {
+                float v[PPT];
+#pragma unroll
+                for (int q = 0; q < PPT; ++q) {
+                    const int yy = y[q] + tap / 3 - 1, xx = x[q] + tap % 3 - 1;
+                    v[q] = (yy >= 0 && yy < M32_S && xx >= 0 && xx < M32_S) ? u[(ci0 + ci) * M32_PIX + yy * M32_S + xx] : 0.f;
+                }
+                const float* wr = stg + (ci * 9 + tap) * MS_C;
+#pragma unroll
+                for (int c4 = 0; c4 < MS_C; c4 += 4) {
+                    const f32x4_t w4 = *(const f32x4_t*)(wr + c4);
+#pragma unroll
+                    for (int q = 0; q < PPT; ++q) {
+                        acc[q][c4] = fmaf(v[q], w4[0], acc[q][c4]);
+                        acc[q][c4 + 1] = fmaf(v[q], w4[1], acc[q][c4 + 1]);
+                        acc[q][c4 + 2] = fmaf(v[q], w4[2], acc[q][c4 + 2]);
+                        acc[q][c4 + 3] = fmaf(v[q], w4[3], acc[q][c4 + 3]);
+                    }
+                }
+            }
+        }
+    }
+    __syncthreads();                                         // the staging area may be reused
+}
+
+// area-pool the two channels src2 ([G][S][S], LDS) to pn x pn (pn < S), token-major: dst[t][c0 + c].  tmp: [G][pn][S] in LDS.  Ends on a barrier.
+template <int NTH>
+__device__ __forceinline__ void m32_area_group(const float* src2, const float* __restrict__ down /*[pn][S]*/, float* tmp, float* dst, int c0, int pn) {
+    const int tid = threadIdx.x;
+    for (int o = tid; o < M32_G * pn * M32_S; o += NTH) {
+        const int x = o % M32_S, i = (o / M32_S) % pn, c = o / (M32_S * pn);
+        float a = 0.f;
+        for (int yy = 0; yy < M32_S; ++yy) a = fmaf(down[i * M32_S + yy], src2[c * M32_PIX + yy * M32_S + x], a);
+        tmp[o] = a;
+    }
+    __syncthreads();
+    for (int o = tid; o < pn * pn * M32_G; o += NTH) {
+        const int c = o % M32_G, t = o / M32_G;
+        const int i = t / pn, j = t % pn;
+        float a = 0.f;
+        for (int xx = 0; xx < M32_S; ++xx) a = fmaf(down[j * M32_S + xx], tmp[(c * pn + i) * M32_S + xx], a);
+        dst[t * MS_C + c0 + c] = a;
+    }
+    __syncthreads();
+}
+
+constexpr int M32_LDS_NI = (M32_MAP + M32_STG) * (int)sizeof(float);                      // 144 KiB
+__global__ __launch_bounds__(1024) void ms32_next_input_kernel(const int* __restrict__ idx, const float* __restrict__ E,
+                                                              const float* __restrict__ phi_w, const float* __restrict__ phi_b,
+                                                              const float* __restrict__ up, const float* __restrict__ down,
+                                                              float* __restrict__ f_hat, float* __restrict__ tok_out, int nmaps, int pn, int pn_next) {
+    constexpr int NTH = 1024;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float* M = lds;
+    float* stg = lds + M32_MAP;
+    const long m = blockIdx.x;                               // = b * nmaps + map
+    const int pix = threadIdx.x;
+    float* fg = f_hat + m * (long)M32_MAP;
+    m32_gather_up<NTH>(idx + m * (long)(pn * pn), E, up, M, stg, pn);
+    float acc[1][MS_C];
+    m32_phi<NTH>(M, phi_w, phi_b, stg, acc);
+#pragma unroll
+    for (int co = 0; co < MS_C; ++co) {
+        const float h = M[co * M32_PIX + pix] * 0.5f + acc[0][co] * 0.5f;
+        acc[0][co] = fg[co * M32_PIX + pix] + h;
+        fg[co * M32_PIX + pix] = acc[0][co];
+    }
+    if (!tok_out) return;
+    __syncthreads();                                         // every neighbour has read u
+#pragma unroll
+    for (int co = 0; co < MS_C; ++co) M[co * M32_PIX + pix] = acc[0][co];
+    __syncthreads();
+    float* dst = tok_out + m * (long)(pn_next * pn_next) * MS_C;
+    if (pn_next == M32_S) {
+        for (int o = threadIdx.x; o < M32_MAP; o += NTH) { const int c = o % MS_C, t = o / MS_C; dst[o] = M[c * M32_PIX + t]; }
+        return;
+    }
+    for (int c0 = 0; c0 < MS_C; c0 += M32_G) m32_area_group<NTH>(M + c0 * M32_PIX, down, stg, dst, c0, pn_next);
+}
+
+// encode: 512 threads, thread owns pixels tid and tid + 512.  LDS: M | stg | sidx[1024] | zzs[1024] = 152 KiB.
+constexpr int M32_ENC_NTH = 512;
+constexpr int M32_LDS_ENC = (M32_MAP + M32_STG + 2 * M32_PIX) * (int)sizeof(float);
+__global__ __launch_bounds__(M32_ENC_NTH) void ms32_encode_kernel(const MsEncodeParams p) {
+    constexpr int NTH = M32_ENC_NTH, NW = NTH / 64, PPT = M32_PIX / NTH;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float* M = lds;
+    float* stg = lds + M32_MAP;
+    int* sidx = (int*)(lds + M32_MAP + M32_STG);
+    float* zzs = lds + M32_MAP + M32_STG + M32_PIX;
+    const int tid = threadIdx.x;
+    const long b = blockIdx.x;
+    float fr[PPT][MS_C];
+#pragma unroll
+    for (int q = 0; q < PPT; ++q)
+#pragma unroll
+        for (int c = 0; c < MS_C; ++c) fr[q][c] = p.f[b * M32_MAP + c * M32_PIX + tid + q * NTH];
+    for (int si = 0; si < p.nscale; ++si) {
+        const int pn = p.pn[si], n = pn * pn;
+        // ---- z[t][c] = area(f_rest) -> M (token-major)
+        if (pn == M32_S) {
+#pragma unroll
+            for (int q = 0; q < PPT; ++q)
+#pragma unroll
+                for (int c4 = 0; c4 < MS_C; c4 += 4)
+                    *(f32x4_t*)(M + (tid + q * NTH) * MS_C + c4) = f32x4_t{fr[q][c4], fr[q][c4 + 1], fr[q][c4 + 2], fr[q][c4 + 3]};
+            __syncthreads();
+        } else {
+            const float* down = p.down + p.down_off[si];
+#pragma unroll
+            for (int c0 = 0; c0 < MS_C; c0 += M32_G) {
+#pragma unroll
+                for (int q = 0; q < PPT; ++q)
+#pragma unroll
+                    for (int c = 0; c < M32_G; ++c) stg[c * M32_PIX + tid + q * NTH] = fr[q][c0 + c];
+                __syncthreads();
+                m32_area_group<NTH>(stg, down, stg + M32_G * M32_PIX, M, c0, pn);
+            }
+        }
+        const long orow = b * p.Ltot + p.idx_off[si];
+        if (!p.margin_out && (p.V % (32 * NW)) == 0) {
+            // ---- nearest code on the matrix pipe: the S = 16 kernel's search (same operands, same chains, first minimum), re-split.  A work item is
+            // (block of 32 tokens, part of the codebook); with >= NW token blocks a wave searches the whole codebook for its blocks and writes the ids itself,
+            // with fewer the codebook is cut into P parts (increasing code order) merged with a strict '<': the first minimum either way.
+            const int lane = tid & 63, w = tid >> 6, col = lane & 31, hi = lane >> 5;
+            for (int t = tid; t < n; t += NTH) {
+                float zz = 0.f;
+#pragma unroll
+                for (int c = 0; c < MS_C; ++c) zz = fmaf(M[t * MS_C + c], M[t * MS_C + c], zz);
+                zzs[t] = zz;
+            }
+            __syncthreads();
+            const int nblk = (n + 31) / 32;
+            const int P = nblk >= 5 ? 1 : (nblk >= 3 ? 2 : (nblk == 2 ? 4 : 8));      // P * nblk <= NW when P > 1
+            const int per_part = p.V / P, cblocks = per_part / 32;
+            float* part_bd = stg;                       // [P][128] (P > 1: n <= 128)
+            int* part_bi = (int*)(stg + NW * 128);
+            for (int item = w; item < nblk * P; item += NW) {
+                const int t0 = (item / P) * 32, part = item % P;
+                float za[MS_C / 2], zr[16];
+                {
+                    const float* zt = M + min(t0 + col, n - 1) * MS_C + hi;
+#pragma unroll
+                    for (int s_ = 0; s_ < MS_C / 2; ++s_) za[s_] = zt[2 * s_];
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) zr[r] = zzs[min(t0 + (r & 3) + 8 * (r >> 2) + 4 * hi, n - 1)];
+                }
+                float bd[16]; int bi[16];
+#pragma unroll
+                for (int r = 0; r < 16; ++r) { bd[r] = INFINITY; bi[r] = 0; }
+                for (int cb = 0; cb < cblocks; ++cb) {
+                    const int v = part * per_part + cb * 32 + col;
+                    f32x4_t e4[MS_C / 4];
+                    const float* er = p.E + (long)v * MS_C;
+#pragma unroll
+                    for (int q = 0; q < MS_C / 4; ++q) e4[q] = *(const f32x4_t*)(er + 4 * q);
+                    f32x16_t acc;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+                    for (int s_ = 0; s_ < MS_C / 2; ++s_) {
+                        const float eb = hi ? e4[s_ >> 1][2 * (s_ & 1) + 1] : e4[s_ >> 1][2 * (s_ & 1)];       // E[v][2 s + hi]
+                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(za[s_], eb, acc, 0, 0, 0);
+                    }
+                    float ee = 0.f;
+#pragma unroll
+                    for (int q = 0; q < MS_C / 4; ++q) {
+                        ee = fmaf(e4[q][0], e4[q][0], ee); ee = fmaf(e4[q][1], e4[q][1], ee);
+                        ee = fmaf(e4[q][2], e4[q][2], ee); ee = fmaf(e4[q][3], e4[q][3], ee);
+                    }
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const float d = __fadd_rn(__fadd_rn(zr[r], ee), __fmul_rn(-2.0f, acc[r]));
+                        if (d < bd[r]) { bd[r] = d; bi[r] = v; }                  // a column's codes come in increasing order: first minimum
+                    }
+                }
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    float d = bd[r]; int i = bi[r];
+#pragma unroll
+                    for (int o = 16; o > 0; o >>= 1) {                            // over the 32 columns of this half-wave
+                        const float d2 = __shfl_xor(d, o, 64);
+                        const int i2 = __shfl_xor(i, o, 64);
+                        if (d2 < d || (d2 == d && i2 < i)) { d = d2; i = i2; }
+                    }
+                    const int t = t0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+                    if (col == 0 && t < n) {
+                        if (P == 1) { sidx[t] = i; p.idx_out[orow + t] = i; }
+                        else { part_bd[part * 128 + t] = d; part_bi[part * 128 + t] = i; }
+                    }
+                }
+            }
+            __syncthreads();
+            if (P > 1) {
+                if (tid < n) {
+                    float bdm = part_bd[tid]; int bim = part_bi[tid];
+                    for (int q = 1; q < P; ++q)
+                        if (part_bd[q * 128 + tid] < bdm) { bdm = part_bd[q * 128 + tid]; bim = part_bi[q * 128 + tid]; }
+                    sidx[tid] = bim;
+                    p.idx_out[orow + tid] = bim;
+                }
+                __syncthreads();
+            }
+        } else {
+            // ---- sequential search (the margins): thread = (token, part of the codebook), rounds of NTH / P tokens
+            const int P = n >= NTH ? 1 : NTH / n;
+            const int tpr = NTH / P;
+            float* red_d = stg; float* red_d2 = stg + NTH; int* red_i = (int*)(stg + 2 * NTH);
+            for (int tb = 0; tb < n; tb += tpr) {
+                const int t = tb + tid / P, part = tid % P;
+                float bd = INFINITY, bd2 = INFINITY;
+                int bi = 0;
+                if (t < n) {
+                    float z[MS_C], zz = 0.f;
+#pragma unroll
+                    for (int c = 0; c < MS_C; ++c) { z[c] = M[t * MS_C + c]; }
+#pragma unroll
+                    for (int c = 0; c < MS_C; ++c) zz = fmaf(z[c], z[c], zz);
+                    const int lo = (int)((long)part * p.V / P), hi = (int)((long)(part + 1) * p.V / P);
+                    for (int v = lo; v < hi; ++v) {
+                        const float* e = p.E + (long)v * MS_C;
+                        float dot = 0.f, ee = 0.f;
+#pragma unroll
+                        for (int c = 0; c < MS_C; c += 4) {
+                            const f32x4_t ev = *(const f32x4_t*)(e + c);
+                            dot = fmaf(z[c], ev[0], dot); dot = fmaf(z[c + 1], ev[1], dot);
+                            dot = fmaf(z[c + 2], ev[2], dot); dot = fmaf(z[c + 3], ev[3], dot);
+                            ee = fmaf(ev[0], ev[0], ee); ee = fmaf(ev[1], ev[1], ee);
+                            ee = fmaf(ev[2], ev[2], ee); ee = fmaf(ev[3], ev[3], ee);
+                        }
+                        const float d = __fadd_rn(__fadd_rn(zz, ee), __fmul_rn(-2.0f, dot));
+                        if (d < bd) { bd2 = bd; bd = d; bi = v; }
+                        else if (d < bd2) bd2 = d;
+                    }
+                }
+                red_d[tid] = bd; red_d2[tid] = bd2; red_i[tid] = bi;
+                __syncthreads();
+                if (t < n && part == 0) {
+                    for (int q = 1; q < P; ++q) {        // parts are in increasing code order -> strict '<' keeps the first minimum
+                        const float d = red_d[tid + q], d2 = red_d2[tid + q];
+                        if (d < bd) { bd2 = fminf(bd, d2); bd = d; bi = red_i[tid + q]; }
+                        else bd2 = fminf(bd2, d);
+                    }
+                    sidx[t] = bi;
+                    p.idx_out[orow + t] = bi;
+                    if (p.margin_out) p.margin_out[orow + t] = bd2 - bd;
+                }
+                __syncthreads();
+            }
+        }
+        // ---- u = up(E[ids]) -> M;  h = 0.5 u + 0.5 (conv(u) + b);  f_rest -= h;  f_hat += h (in f_hat_out, by the pixel's owner)
+        m32_gather_up<NTH>(sidx, p.E, p.up + p.up_off[si], M, stg, pn);
+        const int k = p.phi_map[si];
+        float acc[PPT][MS_C];
+        m32_phi<NTH>(M, p.phi_w + (long)k * MS_C * 9 * MS_C, p.phi_b + k * MS_C, stg, acc);
+        int px = tid;
+        asm volatile("" : "+v"(px));                         // opaque per scale: the 64 f_hat addresses are not hoisted out of the scale loop (they spilled)
+        float* fo = p.f_hat_out ? p.f_hat_out + b * M32_MAP + px : nullptr;
+#pragma unroll
+        for (int q = 0; q < PPT; ++q)
+#pragma unroll
+            for (int co = 0; co < MS_C; ++co) {
+                const int o = co * M32_PIX + q * NTH;
+                const float h = M[o + px] * 0.5f + acc[q][co] * 0.5f;
+                fr[q][co] -= h;
+                if (fo) fo[o] = (si == 0 ? 0.f : fo[o]) + h;
+            }
+        __syncthreads();                                     // M is rewritten by the next scale's z
+    }
+}
+
+static int ms32_next_input(const int* idx, const float* E, const float* phi_w, const float* phi_b, const float* up, const float* down, float* f_hat,
+                           float* tok_out, int nb, int nmaps, int pn, int pn_next, hipStream_t st) {
+    (void)hipFuncSetAttribute((const void*)ms32_next_input_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, M32_LDS_NI);
+    hipLaunchKernelGGL(ms32_next_input_kernel, dim3((unsigned)((long)nb * nmaps)), dim3(1024), M32_LDS_NI, st, idx, E, phi_w, phi_b, up, down, f_hat,
+                       tok_out, nmaps, pn, pn_next);
+    CVAR_CHECK_LAUNCH();
+    return CVAR_OK;
+}
+
+static int ms32_encode(const MsEncodeParams& p, int B, hipStream_t st) {
+    (void)hipFuncSetAttribute((const void*)ms32_encode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, M32_LDS_ENC);
+    hipLaunchKernelGGL(ms32_encode_kernel, dim3(B), dim3(M32_ENC_NTH), M32_LDS_ENC, st, p);
     CVAR_CHECK_LAUNCH();
     return CVAR_OK;
 }

@@ -21,7 +21,7 @@ from . import ops
 from ._lib import CvarError
 from ._lib import ACT_GELU_TANH
 from .pyramid import packed_tables
-from .spec import DEFAULT_PATCH_NUMS, VaeConfig, VarConfig, attention_levels, vae_state_shapes, var_state_shapes
+from .spec import DEFAULT_PATCH_NUMS, VaeConfig, check_latent_size, VarConfig, attention_levels, vae_state_shapes, var_state_shapes
 from .synth import synth_vae_state, synth_var_state
 
 
@@ -81,12 +81,15 @@ class VQVAE(nn.Module):
 
     def __init__(self, vocab_size=4096, z_channels=32, ch=128, dropout=0.0, beta=0.25, using_znorm=False, quant_conv_ks=3,
                  quant_resi=0.5, share_quant_resi=4, default_qresi_counts=0, v_patch_nums=DEFAULT_PATCH_NUMS, test_mode=True,
-                 compute_dtype=torch.bfloat16, init_seed: int = 0, decode_chunk: int = 128, encoder_precision: Optional[str] = None):
-        """encoder_precision (bf16 compute only; None = 'bf16'): arithmetic of the ENCODER conv stack in front of the exact quantizer -
+                 compute_dtype=torch.bfloat16, init_seed: int = 0, decode_chunk: Optional[int] = None, encoder_precision: Optional[str] = None):
+        """v_patch_nums fixes the latent size S = v_patch_nums[-1] and with it the image size 16 S: DEFAULT_PATCH_NUMS (S = 16, 256 x 256 images) or
+        PATCH_NUMS_512 (S = 32, 512 x 512); any other S raises NotImplementedError (the quantizer kernels are built for these two).
+        encoder_precision (bf16 compute only; None = 'bf16'): arithmetic of the ENCODER conv stack in front of the exact quantizer -
         'bf16' (throughput), 'bf16x3' (split-bf16: every operand as hi + lo bf16, three MFMA products per multiply, fp32 accumulate and fp32 activations:
         ~2^-16 relative error per product, ids agree with the reference's fp32 encoder far beyond plain bf16 at about a third of its encoder rate) or 'fp32'
         (the parity mode's exact-f32 MFMA for the encoder only).  The decoder keeps compute_dtype either way."""
         super().__init__()
+        check_latent_size(tuple(v_patch_nums)[-1])
         if using_znorm or quant_conv_ks != 3 or abs(quant_resi - 0.5) > 1e-9 or share_quant_resi != 4 or dropout != 0.0:
             raise NotImplementedError('only the shipped VQVAE configuration (vqvae.py:18-27 defaults, share_quant_resi=4) is built')
         self.cfg = VaeConfig(vocab=vocab_size, z_channels=z_channels, ch=ch, share_quant_resi=share_quant_resi,
@@ -101,8 +104,10 @@ class VQVAE(nn.Module):
             raise ValueError(f'encoder_precision={encoder_precision!r}: one of bf16 / bf16x3 / fp32 (an fp32 model encodes in fp32)')
         self.encoder_precision = ep
         # images per decoder pass (an image's bits do not depend on it).  128 since round 5: VQVAE round trip 1 355 -> 1 373-1 379 images/s, headline +0.4 % at the
-        # same 226 GB peak (64 / 128 / 256: 201.5 / 202.3 / 202.0 images/s on one box)
-        self.decode_chunk = decode_chunk
+        # same 226 GB peak (64 / 128 / 256: 201.5 / 202.3 / 202.0 images/s on one box).  A 512 x 512 image has 4 x the pixels at every decoder level, so 4 x the
+        # activation bytes per image (the widest tensors, (B, 512 * 512, 160) bf16, are 84 MB each against 21 MB) and its 1 024 x 1 024 attention scores add
+        # 4 MB fp32 + 2 MB bf16 per image and block: 32 images per pass keep the 256 x 256 pass's footprint.
+        self.decode_chunk = decode_chunk if decode_chunk is not None else (128 if self.cfg.patch_nums[-1] <= 16 else 32)
         _register_tree(self, vae_state_shapes(self.cfg), synth_vae_state(self.cfg, init_seed), requires_grad=not test_mode)
         self._packed = None
         if test_mode:
@@ -266,7 +271,7 @@ class VQVAE(nn.Module):
                  strideA=HW * 3 * C, strideW=HW * 3 * C, strideC=HW * HW)
         p = torch.empty(B, HW, HW, device=x.device, dtype=T)
         ops.softmax_rows(s, p, B * HW, HW)
-        if HWp != HW:                           # latent sizes other than 16x16 (low-resolution reconstructions, vqvae.py:97-104 same_shape=False)
+        if HWp != HW:                           # latent sizes other than 16x16 / 32x32 (low-resolution reconstructions, vqvae.py:97-104 same_shape=False)
             pp = torch.zeros(B, HW, HWp, device=x.device, dtype=T)
             pp[:, :, :HW] = p
             p = pp
@@ -277,7 +282,7 @@ class VQVAE(nn.Module):
 
     # ---- encoder / decoder
     def _encode_f(self, img: torch.Tensor) -> torch.Tensor:
-        """quant_conv(encoder(img)) -> f (B, Cvae, 16, 16) fp32 (vqvae.py:74; vae_modules.py:144-160)."""
+        """quant_conv(encoder(img)) -> f (B, Cvae, S, S) fp32, S = H / 16 (16 for 256 x 256 images, 32 for 512 x 512) (vqvae.py:74; vae_modules.py:144-160)."""
         P = self._pack()
         if self.encoder_precision != ('bf16' if self.compute_dtype == torch.bfloat16 else 'fp32'):
             return self._encode_f_hiprec(img)
@@ -456,6 +461,7 @@ class VQVAE(nn.Module):
             return pns, P['up'], P['down'], P['phi_map']
         if pns[-1] != self.cfg.patch_nums[-1]:
             raise AssertionError(f'patch_hws[-1]={pns[-1]} != latent size {self.cfg.patch_nums[-1]}')          # quant.py:193
+        check_latent_size(pns[-1])                       # a guard only: the constructor has checked the size the line above compares with
         if len(pns) > 16:
             raise NotImplementedError('at most 16 scales')
         cache = P.setdefault('alt_tables', {})
@@ -1427,7 +1433,8 @@ class ControlVAR(nn.Module):
     @torch.no_grad()
     def autoregressive_infer_cfg(self, B: int, label_B, g_seed: Optional[int] = None, cfg=1.5, top_k=0, top_p=0.0,
                                  more_smooth=False, cond_type=None, _force_idx=None, _trace=False, _gumbel=None) -> torch.Tensor:
-        """control_var.py:356-565: returns (B, 3, 512, 256) in [0,1] (control image on top, RGB below).
+        """control_var.py:356-565: returns (B, 3, 2 H, H) in [0,1] with H = 16 patch_nums[-1] - (B, 3, 512, 256) for the default list, (B, 3, 1024, 512) for
+        PATCH_NUMS_512 (control image on top, RGB below).
         more_smooth: Gumbel-softmax soft code embeddings (:511-515); `_gumbel` (tests) injects the per-pass noise instead of drawing it."""
         f_hat = self._generate(B, label_B, g_seed, cfg, top_k, top_p, more_smooth, cond_type, False, None, None, _force_idx, _trace, _gumbel)
         return self._decode_pair(f_hat)
@@ -1506,7 +1513,7 @@ class VAR(ControlVAR):
     @torch.no_grad()
     def autoregressive_infer_cfg(self, B: int, label_B, g_seed: Optional[int] = None, cfg=1.5, top_k=0, top_p=0.0,
                                  more_smooth=False, _force_idx=None, _trace=False) -> torch.Tensor:
-        """var.py:143-207: returns (B, 3, 256, 256) in [0,1]."""
+        """var.py:143-207: returns (B, 3, H, H) in [0,1], H = 16 patch_nums[-1] (256, or 512 with PATCH_NUMS_512)."""
         f_hat = self._generate(B, label_B, g_seed, cfg, top_k, top_p, more_smooth, None, False, None, None, _force_idx, _trace)
         return self._decode_pair(f_hat)
 

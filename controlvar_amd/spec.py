@@ -18,7 +18,16 @@ from typing import Dict, List, Sequence, Tuple
 
 import numpy as np
 
-DEFAULT_PATCH_NUMS: Tuple[int, ...] = (1, 2, 3, 4, 5, 6, 8, 10, 13, 16)
+DEFAULT_PATCH_NUMS: Tuple[int, ...] = (1, 2, 3, 4, 5, 6, 8, 10, 13, 16)          # 256 x 256 images: 16 x 16 latents, 680 tokens
+PATCH_NUMS_512: Tuple[int, ...] = (1, 2, 3, 4, 6, 9, 13, 18, 24, 32)             # 512 x 512 images: 32 x 32 latents, 2 240 tokens (the VAR family's 512 list)
+SUPPORTED_LATENT_SIZES: Tuple[int, ...] = (16, 32)                                # what the multi-scale quantizer kernels are built for (csrc/msq.hip)
+
+
+def check_latent_size(S: int) -> None:
+    """the quantizer kernels exist for 16 x 16 and 32 x 32 latents only"""
+    if int(S) not in SUPPORTED_LATENT_SIZES:
+        raise NotImplementedError(f'latent size {S} x {S} (the last entry of the scale list): the quantizer kernels are built for '
+                                  f'16 x 16 (256 x 256 images) and 32 x 32 (512 x 512 images) only')
 HEAD_DIM = 64
 NUM_CLASSES = 1000
 NUM_COND_TYPES = 4          # mask, canny, depth, normal; id 4 = unconditional (control_var.py:583)

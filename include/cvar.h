@@ -226,7 +226,8 @@ int cvar_cfg_sample(const float* logits, int B, int nrep, int l, int V, const fl
  *
  * cvar_ms_next_input: get_next_autoregressive_input (quant.py:243-260) for `nmaps` maps per batch row:
  *   f_hat[b][map] += phi_si( bicubic( E[idx[b][map*pn^2 ...]] ) );  tok_out[b][map*pn'^2 + t][:] = area(f_hat, pn')
- *   (tok_out may be NULL at the last scale).  idx int32 [nb][nmaps*pn*pn]; f_hat fp32 [nb][nmaps][Cvae][S][S]. */
+ *   (tok_out may be NULL at the last scale).  idx int32 [nb][nmaps*pn*pn]; f_hat fp32 [nb][nmaps][Cvae][S][S].
+ * Both functions are built for Cvae == 32 and S == 16 (256 x 256 images) or S == 32 (512 x 512); any other S returns CVAR_EUNSUPPORTED. */
 int cvar_ms_next_input(const int32_t* idx, const float* codebook, const float* phi_w, const float* phi_b,
                        const float* up_mat, const float* down_mat, float* f_hat, float* tok_out,
                        int nb, int nmaps, int pn, int pn_next, int S, int Cvae, void* stream);
