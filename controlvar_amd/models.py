@@ -1367,6 +1367,33 @@ class ControlVAR(nn.Module):
         return expo, g
 
     @torch.no_grad()
+    def _capture(self, body):
+        """Capture ``body()`` (launches on device-resident static buffers only) in a HIP graph: (graph, body's result, owned buffers).
+        The warm-up runs on a side stream whose K/V arena and split-K workspace are dropped before the capture; the ones the capture
+        creates are taken out of the per-stream tables and returned as `owned`, to live and die with the graph."""
+        dev = self.device
+        self._pack(); self.vae_proxy[0]._pack()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):                       # warm-up off the capture (module loads, attribute setup, arena)
+            body()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        if self._arena:                                     # the warm-up's K/V arena (arenas are per stream): the capture allocates its own
+            self._arena.pop(side.cuda_stream, None)         # in the graph's pool, and two of them do not fit at large batches
+        ops.release_splitk_workspace(dev, side.cuda_stream)  # ... and the warm-up stream's split-K workspace
+        torch.cuda.empty_cache()
+        ws_before, arena_before = ops.splitk_workspace_keys(), set(self._arena or ())
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            out = body()
+        # buffers created during the capture live in the GRAPH's memory pool and are baked into its launches: they belong to the graph, not
+        # to the per-stream tables - a later stream that is handed the capture stream's (pooled, reused) handle must not inherit them
+        owned = [ops.take_splitk_workspace(k) for k in ops.splitk_workspace_keys() - ws_before]
+        owned += [self._arena.pop(k) for k in set(self._arena or ()) - arena_before]
+        return graph, out, owned
+
+    @torch.no_grad()
     def graphed_generator(self, B: int, cfg=1.5, top_k: int = 0, top_p: float = 0.0):
         """Capture one full `autoregressive_infer_cfg` (10 scales x depth blocks + both VQVAE decodes, ~2.5k launches) in a
         HIP graph and return ``run(label_B, cond_type=None, g_seed=None) -> images``.  Labels, condition types and the
@@ -1383,25 +1410,7 @@ class ControlVAR(nn.Module):
         ty0 = torch.zeros(B, dtype=torch.int64) if self.cfg.mask_factor == 2 else None
         labels_all, types_all = self._prepare_rows(B, lab0, ty0, four_way, 0)
         seed_dev = torch.zeros(1, device=dev, dtype=torch.int64)
-        self._pack(); self.vae_proxy[0]._pack()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):                       # warm-up off the capture (module loads, attribute setup, arena)
-            self._decode_pair(self._generate_core(B, labels_all, types_all, 0, seed_dev, cfg, top_k, top_p, four_way))
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        if self._arena:                                     # the warm-up's K/V arena (arenas are per stream): the capture allocates its own
-            self._arena.pop(side.cuda_stream, None)         # in the graph's pool, and two of them do not fit at large batches
-        ops.release_splitk_workspace(dev, side.cuda_stream)  # ... and the warm-up stream's split-K workspace
-        torch.cuda.empty_cache()
-        ws_before, arena_before = ops.splitk_workspace_keys(), set(self._arena or ())
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            out = self._decode_pair(self._generate_core(B, labels_all, types_all, 0, seed_dev, cfg, top_k, top_p, four_way))
-        # buffers created during the capture live in the GRAPH's memory pool and are baked into its launches: they belong to the graph, not
-        # to the per-stream tables - a later stream that is handed the capture stream's (pooled, reused) handle must not inherit them
-        owned = [ops.take_splitk_workspace(k) for k in ops.splitk_workspace_keys() - ws_before]
-        owned += [self._arena.pop(k) for k in set(self._arena or ()) - arena_before]
+        graph, out, owned = self._capture(lambda: self._decode_pair(self._generate_core(B, labels_all, types_all, 0, seed_dev, cfg, top_k, top_p, four_way)))
 
         def run(label_B, cond_type=None, g_seed=None):
             seed = int(g_seed) if g_seed is not None else int(torch.empty((), dtype=torch.int64).random_().item())
@@ -1415,6 +1424,97 @@ class ControlVAR(nn.Module):
 
         run.graph = graph
         run.owned = owned                                   # dropped together with the graph when `run` goes away
+        return run
+
+    @torch.no_grad()
+    def graphed_conditional_generator(self, B: int, given: str = 'control', cfg=(1.5, 1.5, 1.5), top_k: int = 0, top_p: float = 0.0,
+                                      source: str = 'ids', decode: str = 'both'):
+        """Capture one full `conditional_infer_cfg` in a HIP graph - control in, image out (given='control': the control ids are teacher-forced
+        as `c_mask=`, the image is generated) or image in, control out (given='image', `c_img=`) - and return
+        ``run(label_B, cond_type, given_half, g_seed=None) -> images``.
+        source='ids': run is handed the given half's ids, the reference's list of (B, pn^2) integer tensors or one (B, sum pn^2) tensor, on the
+        CPU or the device.  source='pixels': run is handed (B, 3, 16 S, 16 S) pixels in [-1, 1] and the graph also holds the tokeniser (the
+        calls of `vae.img_to_idxBl`, in the VQVAE's compute_dtype / encoder_precision); ``run.ids()`` returns the ids it produced.
+        decode='both': (B, 3, 2 H, H) exactly as conditional_infer_cfg (control on top, RGB below); decode='generated': only the generated map,
+        (B, 3, H, H), one decoder pass of B images instead of 2 B.
+        Labels, condition types (their 4 B-row forms), the seed, the given ids (int32 (B, sum pn^2)) and the pixels live in static device
+        buffers refreshed before each replay.  more_smooth is not offered under capture; bidirectional models are captured as they are (the
+        four-branch path never draws the order)."""
+        if self.mask_factor != 2:
+            raise NotImplementedError('graphed_conditional_generator needs mask_factor == 2 (control_var.py:333)')
+        if self.sampler == 'torch':
+            raise NotImplementedError("graphed_conditional_generator captures the counter sampler only: sampler='torch' draws its noise with torch on "
+                                      "model.rng between the launches; set model.sampler = 'counter' to capture, or call conditional_infer_cfg")
+        if self.cfg.separator:
+            raise NotImplementedError('separator: conditional_infer_cfg ignores the special tokens (control_var.py:270-330); only forward(), training '
+                                      'and the joint autoregressive_infer_cfg branch are built')
+        for name, val, ok in (('given', given, ('control', 'image')), ('source', source, ('ids', 'pixels')), ('decode', decode, ('both', 'generated'))):
+            if val not in ok:
+                raise ValueError(f'{name}={val!r}: one of {" / ".join(ok)}')
+        try:
+            cfg = tuple(float(c) for c in cfg)
+        except TypeError:
+            cfg = ()
+        if len(cfg) != 3:
+            raise ValueError('cfg: three guidance scales (t1, t2, t3) as in conditional_infer_cfg')
+        if int(B) != B or B < 1:
+            raise ValueError(f'B={B!r}: a positive batch size')
+        if top_k > self.cfg.vocab:                          # as _generate (helpers.py:8-10)
+            raise RuntimeError(f'selected index k out of range (top_k={top_k} > vocabulary {self.cfg.vocab})')
+        dev = self.device
+        vae: VQVAE = self.vae_proxy[0]
+        pns = self.cfg.pyramid.patch_nums
+        Ltot, side_px = sum(pn * pn for pn in pns), 16 * pns[-1]
+        labels_all, types_all = self._prepare_rows(B, torch.zeros(B, dtype=torch.int64), torch.zeros(B, dtype=torch.int64), True, 0)
+        seed_dev = torch.zeros(1, device=dev, dtype=torch.int64)
+        ids_buf = torch.zeros(B, Ltot, device=dev, dtype=torch.int32)
+        pix_buf = torch.zeros(B, 3, side_px, side_px, device=dev, dtype=torch.float32) if source == 'pixels' else None
+        ids_Bl = vae._split(ids_buf)                        # per-scale views of the static buffer: what _generate_core teacher-forces from
+        teach = {'c_mask' if given == 'control' else 'c_img': ids_Bl}
+
+        def body():
+            if pix_buf is not None:
+                ids_buf.copy_(vae._ms_encode(vae._encode_f(pix_buf))[0])
+            f_hat = self._generate_core(B, labels_all, types_all, 0, seed_dev, cfg, top_k, top_p, True, **teach)
+            if decode == 'both':
+                return self._decode_pair(f_hat)
+            return vae._decode(f_hat[:, 1 if given == 'control' else 0].contiguous(), lo=-1.0, hi=1.0, mul=0.5, add=0.5)
+
+        graph, out, owned = self._capture(body)
+
+        def as_rows(name, v):
+            if torch.is_tensor(v) and tuple(v.shape) != (B,):
+                raise ValueError(f'{name}: expected shape ({B},), got {tuple(v.shape)}')
+            return v
+
+        def run(label_B, cond_type, given_half, g_seed=None):
+            label_B, cond_type = as_rows('label_B', label_B), as_rows('cond_type', cond_type)
+            if pix_buf is not None:
+                if not torch.is_tensor(given_half) or tuple(given_half.shape) != tuple(pix_buf.shape) or not given_half.is_floating_point():
+                    raise ValueError(f'given_half: expected pixels of shape {tuple(pix_buf.shape)} (floating point, in [-1, 1]), got '
+                                     f'{tuple(given_half.shape) if torch.is_tensor(given_half) else type(given_half).__name__}')
+            else:
+                if isinstance(given_half, (list, tuple)):
+                    want = [(B, pn * pn) for pn in pns]
+                    if not all(torch.is_tensor(t) for t in given_half) or [tuple(t.shape) for t in given_half] != want:
+                        raise ValueError(f'given_half: expected {len(pns)} id tensors of shapes {want}')
+                    given_half = torch.cat([t.to(given_half[0].device) for t in given_half], dim=1)
+                if not torch.is_tensor(given_half) or tuple(given_half.shape) != (B, Ltot) or given_half.is_floating_point() or given_half.dtype == torch.bool:
+                    raise ValueError(f'given_half: expected integer ids of shape ({B}, {Ltot}) or a list of (B, pn * pn) tensors, got '
+                                     f'{tuple(given_half.shape) if torch.is_tensor(given_half) else type(given_half).__name__}')
+                _check_index_range(given_half, 0, self.cfg.vocab - 1, 'c_mask' if given == 'control' else 'c_img')
+            seed = int(g_seed) if g_seed is not None else int(torch.empty((), dtype=torch.int64).random_().item())
+            la, ta = self._prepare_rows(B, label_B, cond_type, True, seed)
+            labels_all.copy_(la)
+            types_all.copy_(ta)
+            (pix_buf if pix_buf is not None else ids_buf).copy_(given_half)
+            seed_dev.fill_(seed & (2 ** 62 - 1))
+            graph.replay()
+            return out.clone()
+
+        run.graph = graph
+        run.owned = owned                                   # dropped together with the graph when `run` goes away
+        run.ids = lambda: ids_buf.clone()                   # the given half's ids of the last replay ('pixels': what the graph's tokeniser produced)
         return run
 
     def _decode_pair(self, f_hat: torch.Tensor) -> torch.Tensor:
@@ -1518,6 +1618,9 @@ class VAR(ControlVAR):
         return self._decode_pair(f_hat)
 
     def conditional_infer_cfg(self, *a, **k):
+        raise NotImplementedError('plain VAR has no conditional_infer_cfg (var.py)')
+
+    def graphed_conditional_generator(self, *a, **k):
         raise NotImplementedError('plain VAR has no conditional_infer_cfg (var.py)')
 
     def forward(self, label_B, x_BLCv_wo_first_l, cond_type=None, mask_first=True):
