@@ -200,6 +200,11 @@ static int cvar_attention_impl(const void* qkv, const void* q, int dtype, int R,
     const bool qpre = (impl & 4) != 0;                     // the query rows carry scale * log2(e) (cvar_attention_prescaled)
     impl &= 3;
     if (qpre && (dtype != CVAR_BF16 || impl == 1 || !q)) return CVAR_EUNSUPPORTED;
+    // the prescaled kernels take their shift from the first tile's maximum: a hole that hides all of [0, 64) from a level leaves none
+    // (no inference mask has one - an `indep` hole starts at key 0 only for the first scale, where it is one token wide)
+    if (qpre)
+        for (int i = 0; i < p.n_lvl; ++i)
+            if (p.hole_lo[i] <= 0 && p.hole_hi[i] >= 64) return CVAR_EUNSUPPORTED;
     if (dtype == CVAR_BF16 && impl != 1) {
         bool holes = false;
         for (int i = 0; i < p.n_lvl; ++i) holes = holes || p.hole_lo[i] < p.hole_hi[i];
@@ -251,6 +256,11 @@ static int cvar_attention_impl(const void* qkv, const void* q, int dtype, int R,
 // K tile: row-major 128-B rows with the 16-B chunk index XOR-swizzled by (key>>1)&7 (conflict-free ds_read_b128).
 // Global -> register prefetch of tile i+1 is issued before the MFMA work on tile i and written to LDS after it.
 // ================================================================================================
+// A hole that starts at key 0 and covers a whole 64-key tile ([0, 64) or more: the second half of a first level of >= 128 tokens under the
+// `indep` form) leaves a row WITHOUT a visible key in its first tile(s): its running maximum would stay -inf and 2^(-inf - -inf) is a NaN.
+// With holes the maximum is therefore kept at or above this finite floor; every masked score still gives 2^(-inf) = 0, and the first real
+// maximum rescales the (zero) row sum and O by 2^(floor - m) = 0.  Real scores are never this low (|s * c2| < 1e10 for bf16 operands).
+constexpr float FA_M_FLOOR = -1.0e30f;
 constexpr int FA_VT_STRIDE = 68;      // elements per V^T row (64 keys + pad): 136 B, 8-B aligned, 2-way-free writes
 
 // 3 waves per SIMD (<= 168 VGPRs): the softmax phase of one wave overlaps the MFMA phases of the other two (+10 % over 2)
@@ -348,7 +358,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
                 tmax = fmaxf(tmax, s[kb][i]);
             }
         tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-        const float m_new = fmaxf(m, tmax * c2);            // c2 > 0; finite from the first tile on (key 0 is always visible)
+        float m_new = fmaxf(m, tmax * c2);                  // c2 > 0; without holes finite from the first tile on (key 0 is visible)
+        if constexpr (HOLES) m_new = fmaxf(m_new, FA_M_FLOOR);      // see FA_M_FLOOR
         if (!__all(m_new == m)) {                           // rescale only when some row's running max moved (exact skip)
             const float alpha = __builtin_amdgcn_exp2f(m - m_new);
             lsum *= alpha;
@@ -619,7 +630,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         } else {
             // softmax bookkeeping in the exp2 domain: p = 2^(s*c - m), c = scale*log2(e)  (one fma + one v_exp_f32 per score)
             const float tmax = row_max();
-            const float m_new = fmaxf(m, tmax * c2);            // c2 > 0; finite from the first tile on (key 0 is always visible)
+            float m_new = fmaxf(m, tmax * c2);                  // c2 > 0; without holes finite from the first tile on (key 0 is visible)
+            if constexpr (HOLES) m_new = fmaxf(m_new, FA_M_FLOOR);      // see FA_M_FLOOR
             if (!__all(m_new == m)) {                           // rescale only when some row's running max moved (exact skip)
                 const float alpha = __builtin_amdgcn_exp2f(m - m_new);
                 lsum *= alpha;
@@ -969,11 +981,13 @@ __global__ void attn_bwd_prep_kernel(const AttnBwdParams p) {      // dsum[r][h]
     const long rq = i / p.H;
     const T* op = (const T*)p.o + rq * (long)(p.H * 64) + h * 64;
     const T* dp = (const T*)p.dout + rq * (long)(p.H * 64) + h * 64;
-    float a = 0.f;
+    // four partial sums: one 64-term chain loses ~1e-6 absolute in fp32, which a row with few visible keys and a small gradient shows in dQ
+    // (dS = P (dP - D) cancels there); dP in the row-wise kernels below is summed the same way
+    float a[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int d = 0; d < 64; ++d) a = fmaf(Elem<T>::ld(op + d), Elem<T>::ld(dp + d), a);
+    for (int d = 0; d < 64; ++d) a[d & 3] = fmaf(Elem<T>::ld(op + d), Elem<T>::ld(dp + d), a[d & 3]);
     const long r = rq / p.l, q = rq % p.l;
-    p.dsum[(r * p.H + h) * (long)p.l + q] = a;
+    p.dsum[(r * p.H + h) * (long)p.l + q] = (a[0] + a[2]) + (a[1] + a[3]);
 }
 
 template <typename T>
@@ -1020,14 +1034,15 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const AttnBwdParams p)
         for (int kk = 0; kk < KT; ++kk) {
             if (kt0 + kk >= kvlen) break;                 // keys are visible as a prefix ...
             if (kt0 + kk >= vis.hlo && kt0 + kk < vis.hhi) continue;      // ... minus the level's hole
-            float s = 0.f, dp = 0.f;
+            float s = 0.f, dp4[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int d = 0; d < D; d += 4) {
                 const f32x4_t kv = *(const f32x4_t*)&Ks[kk][d];
                 const f32x4_t vv = *(const f32x4_t*)&Vs[kk][d];
                 s = fmaf(q[d], kv[0], s); s = fmaf(q[d + 1], kv[1], s); s = fmaf(q[d + 2], kv[2], s); s = fmaf(q[d + 3], kv[3], s);
-                dp = fmaf(dO[d], vv[0], dp); dp = fmaf(dO[d + 1], vv[1], dp); dp = fmaf(dO[d + 2], vv[2], dp); dp = fmaf(dO[d + 3], vv[3], dp);
+                dp4[0] = fmaf(dO[d], vv[0], dp4[0]); dp4[1] = fmaf(dO[d + 1], vv[1], dp4[1]); dp4[2] = fmaf(dO[d + 2], vv[2], dp4[2]); dp4[3] = fmaf(dO[d + 3], vv[3], dp4[3]);
             }
+            const float dp = (dp4[0] + dp4[2]) + (dp4[1] + dp4[3]);          // partial sums as in attn_bwd_prep_kernel
             const float pr = __expf(s * p.scale - lse);
             const float ds = pr * (dp - Dq);
 #pragma unroll
@@ -1095,14 +1110,15 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const AttnBwdParams p
         __syncthreads();
         for (int qq = 0; qq < QT; ++qq) {
             if (krow >= Kv[qq] || (krow >= Hlo[qq] && krow < Hhi[qq])) continue;      // query does not see this key (or is padding)
-            float s = 0.f, dp = 0.f;
+            float s = 0.f, dp4[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int d = 0; d < D; d += 4) {
                 const f32x4_t qv = *(const f32x4_t*)&Qs[qq][d];
                 const f32x4_t ov = *(const f32x4_t*)&Os[qq][d];
                 s = fmaf(qv[0], k[d], s); s = fmaf(qv[1], k[d + 1], s); s = fmaf(qv[2], k[d + 2], s); s = fmaf(qv[3], k[d + 3], s);
-                dp = fmaf(ov[0], v[d], dp); dp = fmaf(ov[1], v[d + 1], dp); dp = fmaf(ov[2], v[d + 2], dp); dp = fmaf(ov[3], v[d + 3], dp);
+                dp4[0] = fmaf(ov[0], v[d], dp4[0]); dp4[1] = fmaf(ov[1], v[d + 1], dp4[1]); dp4[2] = fmaf(ov[2], v[d + 2], dp4[2]); dp4[3] = fmaf(ov[3], v[d + 3], dp4[3]);
             }
+            const float dp = (dp4[0] + dp4[2]) + (dp4[1] + dp4[3]);          // partial sums as in attn_bwd_prep_kernel
             const float pr = __expf(s * p.scale - Ls[qq]);
             const float ds = pr * (dp - Ds[qq]);
 #pragma unroll

@@ -180,8 +180,9 @@ __global__ __launch_bounds__(256) void cos_qk_norm_bwd_kernel(const T* __restric
     Elem<T>::st(dqkv + off, (gp - xt * dot) / nrm);
     if (which == 0) {
         const float ds = wave_sum(g * xt);
-        // chain rule through sm = exp(min(s, ln 100)): d sm / d s = sm below the clamp, 0 above it
-        if (lane == 0) dsm_tok[rt * H + h] = scale_mul[h] < 4.605170185988092f ? ds * sm : 0.f;
+        // chain rule through sm = exp(min(s, ln 100)): d sm / d s = sm up to and AT the clamp, 0 above it - torch's clamp_max passes the gradient at
+        // equality (basic_var.py:100), and a parameter that was clamped in place sits exactly there
+        if (lane == 0) dsm_tok[rt * H + h] = scale_mul[h] <= 4.605170185988092f ? ds * sm : 0.f;
     }
 }
 

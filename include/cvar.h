@@ -168,7 +168,9 @@ int cvar_attention_rowwise(const void* qkv, const void* q, int dtype, int R, int
 /* ABI 14, inference form only (K/V arena in `kv` + the call's queries in `q`, bf16): the query rows already hold
  * q * scale * log2(e) (cvar_gemm_desc.split_alpha on the QKV GEMM, or cvar_cos_qk_norm's q_mul for cos-attention), so
  * softmax(q k^T scale) v = sum_k 2^(q' k) v / sum_k 2^(q' k)  (basic_var.py:99-117, same function).  The kernel subtracts the running maximum on
- * the matrix pipe (see attn.hip) - one vector operation less per score than cvar_attention. */
+ * the matrix pipe (see attn.hip) - one vector operation less per score than cvar_attention.  A level whose hole covers all of keys [0, 64)
+ * is CVAR_EUNSUPPORTED here (the shift comes from the first key tile, where such a level sees nothing; no inference mask has one) -
+ * cvar_attention serves it. */
 int cvar_attention_prescaled(const void* kv, const void* q, int dtype, int R, int H, int Lmax, int q_off, int l,
                              const int* lvl_end_host, int n_lvl, const int* hole_host, void* out, float* lse, void* stream);
 /* the round-2 MFMA kernel behind cvar_attention's contract: kept as the in-library A/B reference of the round-3 kernel (tools/attn_bench.py) */
@@ -190,7 +192,8 @@ int cvar_cos_qk_norm(void* qkv, void* q, int dtype, int R, int H, int Lmax, int 
                      float* norms /* optional [R][l][H][2] = |q|, |k|, saved for training */,
                      float q_mul /* ABI 14: extra factor on the query side (log2(e) in front of cvar_attention_prescaled; 1 otherwise) */, void* stream);
 /* backward of the pre-pass, in place on dqkv (arena layout, q_off 0): gradients w.r.t. the normalised q, k become gradients
- * w.r.t. the raw projections; dsm_tok[R*l][H] receives d loss / d scale_mul per token (summed over tokens by cvar_colsum). */
+ * w.r.t. the raw projections; dsm_tok[R*l][H] receives d loss / d scale_mul per token (summed over tokens by cvar_colsum): through
+ * exp(clamp_max(scale_mul, log 100)) the gradient passes for scale_mul <= log 100 - also AT the clamp, as torch's clamp_max does - and is 0 above. */
 int cvar_cos_qk_norm_bwd(const void* qkv, void* dqkv, int dtype, int R, int H, int Lmax, int l, const float* scale_mul,
                          const float* norms, float* dsm_tok, void* stream);
 
