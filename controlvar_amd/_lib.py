@@ -1,4 +1,4 @@
-"""ctypes binding of libcvar_hip.so (include/cvar.h).  No torch types cross this boundary:
+"""ctypes binding of libcvar_hip.so (include/cvar.h, include/cvar_serve.h).  No torch types cross this boundary:
 callers hand over raw device pointers (``tensor.data_ptr()``), sizes and the HIP stream handle.
 
 The library is mandatory on the product path: if it is missing or does not load, every op
@@ -111,6 +111,14 @@ SIGNATURES = {
     'cvar_probe_mfma_flops': (C.c_double, [c_i]),
 }
 
+# include/cvar_serve.h: entry points with no counterpart in the reference, versioned by cvar_serve_version() - a table of its own, so
+# that SIGNATURES stays the mirror of cvar.h
+SERVE_VERSION = 1
+SERVE_SIGNATURES = {
+    'cvar_serve_version': (c_i, []),
+    'cvar_cfg_sample_rows': (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -133,13 +141,16 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         except Exception:  # pragma: no cover
             pass
         lib = C.CDLL(path, mode=C.RTLD_GLOBAL)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in (*SIGNATURES.items(), *SERVE_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
         v = lib.cvar_abi_version()
         if v != ABI_VERSION:
             raise CvarError(f'libcvar_hip.so ABI {v} != expected {ABI_VERSION}; rebuild')
+        v = lib.cvar_serve_version()
+        if v != SERVE_VERSION:
+            raise CvarError(f'libcvar_hip.so cvar_serve.h version {v} != expected {SERVE_VERSION}; rebuild')
         _lib = lib
         return lib
 

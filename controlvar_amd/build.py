@@ -48,7 +48,8 @@ def _compile(src: str) -> str:
 def build_lib(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(OBJ, exist_ok=True)
     deps = [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(CSRC, 'cvar_common.h'), os.path.join(CSRC, 'gemm_params.h'),
-                                                         os.path.join(os.path.dirname(HERE), 'include', 'cvar.h')]
+                                                         os.path.join(os.path.dirname(HERE), 'include', 'cvar.h'),
+                                                         os.path.join(os.path.dirname(HERE), 'include', 'cvar_serve.h')]
     stamp = os.path.join(OBJ, 'digest.txt')
     dig = _digest(deps)
     if not force and os.path.exists(LIB) and os.path.exists(stamp) and open(stamp).read() == dig:

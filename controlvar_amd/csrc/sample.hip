@@ -6,6 +6,7 @@
 //            cumulative mass (helpers.py:12-15), inverse-CDF draw from a counter-based generator (no sort); or, with caller-drawn
 //            Exp(1) noise q, torch.multinomial's draw for one sample per row: argmax(p / q) over the softmax p of the masked logits.
 #include "cvar_common.h"
+#include "../../include/cvar_serve.h"
 
 struct SampleParams {
     const float* logits;
@@ -424,6 +425,231 @@ extern "C" int cvar_cfg_sample(const float* logits, int B, int nrep, int l, int 
     } else if (top_k == 1) hipLaunchKernelGGL(cfg_greedy_kernel, grid, block, 0, as_stream(stream), p);
     else if (soft_out) hipLaunchKernelGGL((cfg_sample_kernel<true, false>), grid, block, 0, as_stream(stream), p);
     else hipLaunchKernelGGL((cfg_sample_kernel<false, false>), grid, block, 0, as_stream(stream), p);
+    CVAR_CHECK_LAUNCH();
+    return CVAR_OK;
+}
+
+// ---- per-request form (include/cvar_serve.h) ---------------------------------------------------------------------
+// One batch row = one request: combine weights, top_k, top_p and seed are read per row b from device tables (block-uniform loads), and
+// the draw is keyed by (seed_b, stage, d, t) - the key cfg_sample_kernel forms at B = 1, where d * 1 + 0 = d.  Row b of a launch is
+// therefore bit for bit the B = 1 launch of the scalar kernels on that row's logits, whatever rides beside it; a row with
+// top_k_b == 1 leaves through cfg_greedy_kernel's reduction (lowest index among tied maxima, kept = 1), never through a draw among
+// the ties.  A kernel of its own: cfg_greedy_kernel and cfg_sample_kernel<SOFT, RACE> above compile to exactly what they compiled to
+// before it existed.  The steps below are those of cfg_sample_kernel<false, false>, statement by statement.
+struct RowSampleParams {
+    const float* logits;
+    int B, nrep, l, V, ldv;
+    const float* coef;                      // [B][4] fp32, this stage's weights (host-rounded: never recomputed from cfg_b here)
+    const int* top_k;                       // [B]   <= 0 or >= V: no top-k filter; 1: greedy
+    const float* top_p;                     // [B]
+    const unsigned long long* seed;         // [B]
+    int stage, n_draw;
+    int* idx_out;
+    float* combined;
+    float* margin;
+    int* kept;
+};
+
+// combine_logits with the row's weights: ((c0 l0 + c1 l1) + c2 l2) + c3 l3, separately rounded products
+__device__ __forceinline__ float combine_row(const RowSampleParams& p, const float* cf, const float* base, long repstride, int e) {
+    float v = __fmul_rn(cf[0], base[e]);
+    for (int r = 1; r < p.nrep; ++r) v = __fadd_rn(v, __fmul_rn(cf[r], base[(long)r * repstride + e]));
+    return v;
+}
+
+__global__ __launch_bounds__(256) void cfg_sample_rows_kernel(const RowSampleParams p) {
+    constexpr int EPT = 16;
+    typedef unsigned long long u64;
+    __shared__ int hist_cnt[256];
+    __shared__ u64 hist_mass[256];
+    __shared__ u64 wsum64[4];
+    __shared__ int wsum32[4];
+    __shared__ float wmaxs[4], wmax2[4];
+    __shared__ int wimax[4];
+    __shared__ unsigned sel_digit;
+    __shared__ u64 sel_below;
+    __shared__ int sel_k;
+    const int tid = threadIdx.x;
+    const long bt = blockIdx.x;
+    const long b = bt / p.l, t = bt % p.l;
+    const float* cf = p.coef + b * 4;
+    const int top_k = p.top_k[b];
+    const float top_p = p.top_p[b];
+    const u64 seed = p.seed[b];
+    const long rowstride = (long)p.l * p.ldv, repstride = (long)p.B * rowstride;
+    const float* base = p.logits + (b * p.l + t) * p.ldv;
+    if (top_k == 1) {                                  // block-uniform: cfg_greedy_kernel's loop and reduction, before the sampler's registers exist
+        Top2 g = {-INFINITY, 0x7fffffff, -INFINITY};
+        for (int e = tid; e < p.V; e += 256) {
+            const float x = combine_row(p, cf, base, repstride, e);
+            if (p.combined) p.combined[bt * p.V + e] = x;
+            Top2 cur = {x, e, -INFINITY};
+            g = merge_top2(g, cur);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            Top2 other;
+            other.b1 = __shfl_xor(g.b1, o, 64); other.i1 = __shfl_xor(g.i1, o, 64); other.b2 = __shfl_xor(g.b2, o, 64);
+            g = merge_top2(g, other);
+        }
+        if ((tid & 63) == 0) { wmaxs[tid >> 6] = g.b1; wimax[tid >> 6] = g.i1; wmax2[tid >> 6] = g.b2; }
+        __syncthreads();
+        if (tid == 0) {
+            Top2 r = {wmaxs[0], wimax[0], wmax2[0]};
+            for (int w = 1; w < 4; ++w) { Top2 o = {wmaxs[w], wimax[w], wmax2[w]}; r = merge_top2(r, o); }
+            for (int d = 0; d < p.n_draw; ++d) p.idx_out[((long)d * p.B + b) * p.l + t] = r.i1;
+            if (p.margin) p.margin[bt] = r.b1 - r.b2;
+            if (p.kept) p.kept[bt] = 1;
+        }
+        return;
+    }
+    float v[EPT];
+    unsigned key[EPT];
+    float best = -INFINITY, second = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < EPT; ++i) {
+        const int e = i * 256 + tid;                   // thread-strided ownership: coalesced loads
+        float x = -INFINITY;
+        if (e < p.V) {
+            x = combine_row(p, cf, base, repstride, e);
+            if (p.combined) p.combined[bt * p.V + e] = x;
+        }
+        v[i] = x; key[i] = f2key(x);
+        if (x > best) { second = best; best = x; } else if (x > second) second = x;
+    }
+    // block max (+ second max for the margin output)
+    {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ob = __shfl_xor(best, o, 64), os = __shfl_xor(second, o, 64);
+            second = fmaxf(fminf(best, ob), fmaxf(second, os));
+            best = fmaxf(best, ob);
+        }
+        if ((tid & 63) == 0) { wmaxs[tid >> 6] = best; wmax2[tid >> 6] = second; }
+        __syncthreads();
+        best = wmaxs[0]; second = wmax2[0];
+        for (int w = 1; w < 4; ++w) { second = fmaxf(fminf(best, wmaxs[w]), fmaxf(second, wmax2[w])); best = fmaxf(best, wmaxs[w]); }
+        if (p.margin && tid == 0) p.margin[bt] = best - second;
+    }
+    const float vmax = best;
+
+    // ---- top-k threshold key
+    unsigned tk = 0;
+    if (top_k > 0 && top_k < p.V) {
+        unsigned prefix = 0;
+        int kk = top_k;
+        for (int ps = 3; ps >= 0; --ps) {
+            hist_cnt[tid] = 0;
+            if (tid == 0) { sel_digit = 0u; sel_k = kk; }
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < EPT; ++i) {
+                const bool match = (ps == 3) || ((key[i] >> (8 * (ps + 1))) == prefix);
+                if (match && i * 256 + tid < p.V) atomicAdd(&hist_cnt[(key[i] >> (8 * ps)) & 255], 1);
+            }
+            __syncthreads();
+            const int dd = 255 - tid;                              // thread t owns digit 255-t: suffix counts become a prefix scan
+            const int c = hist_cnt[dd];
+            int tot;
+            const int above = block_excl_scan<int>(c, wsum32, tot);   // elements with a larger digit
+            if (above < kk && above + c >= kk) { sel_digit = (unsigned)dd; sel_k = kk - above; }
+            __syncthreads();
+            prefix = (prefix << 8) | sel_digit;
+            kk = sel_k;
+            __syncthreads();
+        }
+        tk = prefix;
+    }
+    // ---- quantised masses of the top-k set
+    u64 wq[EPT];
+    u64 local = 0;
+#pragma unroll
+    for (int i = 0; i < EPT; ++i) {
+        const bool in = (i * 256 + tid < p.V) && key[i] >= tk;
+        wq[i] = in ? (u64)(__expf(v[i] - vmax) * 1099511627776.0f) : 0ull;      // 2^40
+        local += wq[i];
+    }
+    u64 Z;
+    (void)block_excl_scan<u64>(local, wsum64, Z);
+    // ---- nucleus threshold key: smallest key whose ascending cumulative mass exceeds (1 - top_p) * Z (clamping as in cfg_sample_kernel)
+    unsigned tp = 0;
+    if (top_p > 0.f) {
+        const double keep_from = fmin(fmax(1.0 - (double)top_p, 0.0), 1.0);
+        u64 lim = (u64)(keep_from * (double)Z);
+        if (lim >= Z) lim = Z - 1;
+        unsigned prefix = 0;
+        u64 below = 0;
+        for (int ps = 3; ps >= 0; --ps) {
+            hist_mass[tid] = 0ull;
+            if (tid == 0) { sel_digit = 255u; sel_below = below; }      // defined even if no bucket were selected
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < EPT; ++i) {
+                const bool match = (ps == 3) || ((key[i] >> (8 * (ps + 1))) == prefix);
+                if (match && wq[i]) atomicAdd(&hist_mass[(key[i] >> (8 * ps)) & 255], wq[i]);
+            }
+            __syncthreads();
+            const u64 c = hist_mass[tid];
+            u64 tot;
+            const u64 before = below + block_excl_scan<u64>(c, wsum64, tot);   // mass of smaller digits (ascending)
+            if (before <= lim && before + c > lim) { sel_digit = (unsigned)tid; sel_below = before; }
+            __syncthreads();
+            prefix = (prefix << 8) | sel_digit;
+            below = sel_below;
+            __syncthreads();
+        }
+        tp = prefix;
+    }
+    const unsigned thr = tk > tp ? tk : tp;
+    u64 keepsum = 0;
+    int nkeep = 0;
+#pragma unroll
+    for (int i = 0; i < EPT; ++i) {
+        if (!(key[i] >= thr && wq[i])) wq[i] = 0ull;
+        keepsum += wq[i];
+        nkeep += wq[i] ? 1 : 0;
+    }
+    u64 Zk;
+    const u64 excl = block_excl_scan<u64>(keepsum, wsum64, Zk);
+    if (p.kept) {
+        int tot;
+        (void)block_excl_scan<int>(nkeep, wsum32, tot);
+        if (tid == 0) p.kept[bt] = tot;
+    }
+    for (int d = 0; d < p.n_draw; ++d) {
+        u64 h = splitmix64(seed ^ 0xC0FFEE1234ull);
+        h = splitmix64(h ^ ((u64)p.stage << 48) ^ ((u64)d << 16) ^ (u64)t);       // row = d: the scalar kernel's d * B + b at B = 1
+        const double u = (double)(h >> 11) * (1.0 / 9007199254740992.0);       // 53 bits -> [0,1)
+        u64 target = (u64)(u * (double)Zk);
+        if (target >= Zk) target = Zk > 0 ? Zk - 1 : 0;
+        if (excl <= target && target < excl + keepsum) {                        // exactly one thread
+            u64 run = excl;
+            int pick = tid;
+#pragma unroll
+            for (int i = 0; i < EPT; ++i) {
+                run += wq[i];
+                if (run > target) { pick = i * 256 + tid; break; }
+            }
+            p.idx_out[((long)d * p.B + b) * p.l + t] = pick;
+        }
+    }
+}
+
+extern "C" int cvar_serve_version(void) { return 1; }
+
+extern "C" int cvar_cfg_sample_rows(const float* logits, int B, int nrep, int l, int V, const float* coef, const int32_t* top_k,
+                                    const float* top_p, const int64_t* seed, int stage, int n_draw, int32_t* idx_out, float* combined,
+                                    float* margin, int32_t* kept, int ldv, const float* expo, float* soft_out, void* stream) {
+    if (!logits || !coef || !top_k || !top_p || !seed || !idx_out || B <= 0 || l <= 0 || V <= 1) return CVAR_EINVAL;
+    if (nrep < 1 || nrep > 4 || n_draw < 1 || n_draw > 4 || V > 4096) return CVAR_EUNSUPPORTED;
+    if (ldv != 0 && ldv < V) return CVAR_EINVAL;
+    if (expo || soft_out) return CVAR_EUNSUPPORTED;                // caller-drawn noise and more_smooth have no per-row form
+    RowSampleParams p;
+    p.logits = logits; p.B = B; p.nrep = nrep; p.l = l; p.V = V; p.ldv = ldv ? ldv : V;
+    p.coef = coef; p.top_k = (const int*)top_k; p.top_p = top_p; p.seed = (const unsigned long long*)seed;
+    p.stage = stage; p.n_draw = n_draw;
+    p.idx_out = idx_out; p.combined = combined; p.margin = margin; p.kept = kept;
+    hipLaunchKernelGGL(cfg_sample_rows_kernel, dim3((unsigned)((long)B * l)), dim3(256), 0, as_stream(stream), p);
     CVAR_CHECK_LAUNCH();
     return CVAR_OK;
 }

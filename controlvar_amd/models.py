@@ -739,6 +739,109 @@ class _TorchDraws:
             raise RuntimeError(f'torch sampler: {len(self.schedule) - self.pos} scheduled draws were not taken')
 
 
+# ---- per-request sampling parameters (an addition of this library; include/cvar_serve.h) ---------------------------------------
+def _host_array(v) -> np.ndarray:
+    """a sampling parameter as a host array; a device tensor is read back (this synchronises with the device)"""
+    if torch.is_tensor(v):
+        return v.detach().cpu().numpy()
+    if isinstance(v, (list, tuple)) and any(torch.is_tensor(x) for x in v):
+        v = [_host_array(x) for x in v]
+    return np.asarray(v)
+
+
+def _per_request(cfg, top_k, top_p, g_seed, four_way: bool) -> bool:
+    """does any of the sampling parameters come per batch row?  A scalar (python / numpy number, 0-d array or tensor; g_seed also None) is
+    the reference's one-value-per-call form, and so is ONE triple of guidance scales for the four-branch cfg; everything else is per row"""
+    if _host_array(cfg).ndim == (2 if four_way else 1):
+        return True
+    return any(v is not None and _host_array(v).ndim != 0 for v in (top_k, top_p, g_seed))
+
+
+class _RequestTable:
+    """The per-row sampling parameters of one batch in ONE contiguous host buffer - seeds int64 [B] | top_k int32 [B] | top_p fp32 [B] |
+    combine weights fp32 [nstage][B][4] - so that one host-to-device copy refreshes all of them (before a graph replay)."""
+
+    def __init__(self, B: int, nstage: int):
+        self.B, self.nstage = B, nstage
+        self.host = torch.zeros(self.nbytes(B, nstage), dtype=torch.uint8)
+        self.seed, self.top_k, self.top_p, self.coef = self.views(self.host)
+
+    @staticmethod
+    def nbytes(B: int, nstage: int) -> int:
+        return 8 * B + 4 * B + 4 * B + 16 * nstage * B
+
+    def views(self, buf: torch.Tensor):
+        """(seed (B,) int64, top_k (B,) int32, top_p (B,) fp32, coef (nstage, B, 4) fp32) views of `buf`, the host buffer or a device copy of it"""
+        B = self.B
+        return (buf[:8 * B].view(torch.int64), buf[8 * B:12 * B].view(torch.int32), buf[12 * B:16 * B].view(torch.float32),
+                buf[16 * B:].view(torch.float32).view(self.nstage, B, 4))
+
+
+def _request_table(B: int, cfg, top_k, top_p, g_seed, four_way: bool, vocab: int, nstage: int) -> _RequestTable:
+    """Normalise per-request sampling parameters.  cfg / top_k / top_p / g_seed: each a scalar (broadcast to the B rows) or a length-B
+    sequence, numpy array or tensor (a device tensor is read back, which synchronises); the four-branch cfg is one triple or (B, 3).
+    g_seed=None draws one host seed per row, as the scalar path draws its one; seeds are taken modulo 2^64.  The combine weights of every
+    stage come from the very expressions of _generate_core, in python doubles, rounded to fp32 once: bit-identical to what the scalar
+    call hands to cvar_cfg_sample.  Raises before anything is written anywhere: ValueError on a wrong length or shape, RuntimeError on
+    top_k > vocabulary (as the scalar call)."""
+    def rows(name, v, width=None):
+        a = _host_array(v)
+        if a.dtype == object or a.dtype.kind not in 'iuf':
+            raise ValueError(f'{name}: numbers expected, got {a.dtype}')
+        scalar_ndim = 0 if width is None else 1
+        want = (B,) if width is None else (B, width)
+        if a.ndim == scalar_ndim and (width is None or a.shape == (width,)):
+            a = np.broadcast_to(a, want)
+        if a.shape != want:
+            raise ValueError(f'{name}: a scalar or shape {want} (one per batch row) expected, got {a.shape}' if width is None else
+                             f'{name}: one triple of guidance scales or shape {want} expected, got {a.shape}')
+        return a
+
+    cfg_r = rows('cfg', cfg, 3 if four_way else None).astype(np.float64)
+    k_r = rows('top_k', top_k)
+    if k_r.dtype.kind == 'f':
+        if not np.all(k_r == np.round(k_r)):
+            raise ValueError('top_k: integers expected')
+    k_r = k_r.astype(np.int64)
+    if (k_r > vocab).any():                              # as _generate (helpers.py:8-10: torch.topk raises on k > V)
+        raise RuntimeError(f'selected index k out of range (top_k={int(k_r.max())} > vocabulary {vocab})')
+    p_r = rows('top_p', top_p).astype(np.float32)
+    if g_seed is None:
+        seeds = [int(s) for s in torch.empty(B, dtype=torch.int64).random_().tolist()]
+    else:
+        # python integers, not a numpy array: seeds are arbitrary-size integers taken modulo 2^64 (int(g_seed) & (2^64 - 1) in the scalar call)
+        seeds = _host_array(g_seed).tolist() if torch.is_tensor(g_seed) or isinstance(g_seed, np.ndarray) else g_seed
+        seeds = list(seeds) if isinstance(seeds, (list, tuple)) else [seeds] * B
+        if len(seeds) != B or not all(isinstance(s, (int, np.integer)) and not isinstance(s, bool) for s in seeds):
+            raise ValueError(f'g_seed: one integer or {B} integers (one per batch row) expected')
+        seeds = [int(s) for s in seeds]
+    tab = _RequestTable(B, nstage)
+    tab.seed.copy_(torch.from_numpy(np.array([s & (2 ** 64 - 1) for s in seeds], dtype=np.uint64).view(np.int64)))
+    tab.top_k.copy_(torch.from_numpy(np.maximum(k_r, -1).astype(np.int32)))          # <= 0: no filter (every negative value means the same)
+    tab.top_p.copy_(torch.from_numpy(np.ascontiguousarray(p_r)))
+    coef = np.zeros((nstage, B, 4), dtype=np.float32)
+    for si in range(nstage):
+        ratio = si / (nstage - 1)
+        for b in range(B):
+            if four_way:
+                t1, t2, t3 = [c * ratio for c in cfg_r[b].tolist()]
+                coef[si, b] = [1 + t1, t2 - t1, t3 - t2, -t3]
+            else:
+                t = float(cfg_r[b]) * ratio
+                coef[si, b, :2] = [1 + t, -t]
+    tab.coef.copy_(torch.from_numpy(coef))
+    return tab
+
+
+def _refuse_request_keywords(g_seed, request: dict):
+    """run() of a graph captured with per_request=False: cfg / top_k / top_p are baked into its launches, and its one seed is a scalar"""
+    if request:
+        raise TypeError(f'run() got {", ".join(sorted(request))}: this graph was captured with per_request=False, which bakes cfg, top_k and top_p into its '
+                        'launches - capture it with per_request=True to pass them per call and per row')
+    if g_seed is not None and _host_array(g_seed).ndim != 0:
+        raise ValueError('g_seed: one integer - this graph was captured with per_request=False; capture it with per_request=True for one seed per row')
+
+
 class ControlVAR(nn.Module):
     """Joint (control, image) next-scale transformer (reference: models/control_var.py:23-689).
 
@@ -1163,6 +1266,10 @@ class ControlVAR(nn.Module):
     @torch.no_grad()
     def _generate(self, B, label_B, g_seed, cfg_scale, top_k, top_p, more_smooth, cond_type, four_way, c_mask, c_img,
                   force_idx=None, trace: bool = False, gumbel=None):
+        if _per_request(cfg_scale, top_k, top_p, g_seed, four_way):
+            return self._generate_rows(B, label_B, g_seed, cfg_scale, top_k, top_p, more_smooth, cond_type, four_way, c_mask, c_img, force_idx, trace)
+        if four_way:
+            cfg_scale = tuple(cfg_scale)
         if top_k > self.cfg.vocab:                     # helpers.py:8-10: torch.topk raises on k > V; top_k <= 0 means no top-k filter
             raise RuntimeError(f'selected index k out of range (top_k={top_k} > vocabulary {self.cfg.vocab})')
         draws = None
@@ -1208,11 +1315,52 @@ class ControlVAR(nn.Module):
             draws.finish()
         return f_hat
 
+    def _check_per_request(self, label_B, cond_type, four_way, more_smooth=False):
+        """what per-request mode does not offer, said on the host before any device work"""
+        if more_smooth:
+            raise NotImplementedError('per-request sampling parameters: more_smooth is not offered (the soft-embedding kernel has no per-row form); pass '
+                                      'scalar cfg / top_k / top_p / g_seed, or more_smooth=False')
+        if self.sampler == 'torch':
+            raise NotImplementedError("per-request sampling parameters: sampler='torch' is not offered (its noise comes from ONE generator stream in "
+                                      "batch order, so a row's draw depends on its slot); set model.sampler = 'counter'")
+        if self.cfg.separate_decoding and not self.cfg.indep and not four_way:
+            raise NotImplementedError('per-request sampling parameters: the two-pass separate_decoding branch (control_var.py:428-485) is not offered; '
+                                      'pass scalar cfg / top_k / top_p / g_seed')
+        if label_B is None or (self.cfg.mask_factor == 2 and cond_type is None):
+            raise ValueError('per-request sampling parameters: label_B' + (' and cond_type' if self.cfg.mask_factor == 2 else '') + ' must be given per row - '
+                             'None draws them from the one batch seed of the scalar path, which a batch of requests does not have')
+
+    @torch.no_grad()
+    def _generate_rows(self, B, label_B, g_seed, cfg_scale, top_k, top_p, more_smooth, cond_type, four_way, c_mask, c_img, force_idx=None, trace: bool = False):
+        """per-request mode (an addition of this library): any of cfg / top_k / top_p / g_seed given per batch row.  Row b produces exactly
+        what the scalar call produces at B = 1 with (label_b, cond_type_b, cfg_b, top_k_b, top_p_b, g_seed = seed_b): combined logits, kept-set
+        size, margin, ids and image - bit for bit under deterministic_plan=True (the sampler always is; the plan makes the logits independent
+        of the batch).  A bidirectional model still draws ONE (control, image) order per call from python's `random`, as the scalar path."""
+        self._check_per_request(label_B, cond_type, four_way, more_smooth)
+        table = _request_table(B, cfg_scale, top_k, top_p, g_seed, four_way, self.cfg.vocab, len(self.cfg.pyramid.patch_nums))
+        self._pack(check=True); self.vae_proxy[0]._pack(check=True)
+        for name, ids in (('c_mask', c_mask), ('c_img', c_img), ('_force_idx', force_idx)):
+            if ids is not None:
+                _check_index_range(torch.cat([t.reshape(-1) for t in ids]), 0, self.cfg.vocab - 1, name)
+        labels_all, types_all = self._prepare_rows(B, label_B, cond_type, four_way, 0)
+        mask_first = True
+        if self.cfg.mask_factor == 2 and not four_way:
+            import random                                 # control_var.py:403, as _generate
+            mask_first = True if (random.random() < 0.5 or not self.bidirectional) else False
+        if self.cfg.separator and four_way:
+            raise NotImplementedError('separator: conditional_infer_cfg ignores the special tokens (control_var.py:270-330); only forward(), training '
+                                      'and the joint autoregressive_infer_cfg branch are built')
+        rows = table.views(table.host.to(self.device))
+        return self._generate_core(B, labels_all, types_all, 0, None, None, None, None, four_way, c_mask, c_img, force_idx, trace, mask_first=mask_first,
+                                   rows=rows)
+
     @torch.no_grad()
     def _generate_core(self, B, labels_all, types_all, seed, seed_dev, cfg_scale, top_k, top_p, four_way, c_mask=None, c_img=None,
-                       force_idx=None, trace: bool = False, mask_first: bool = True, more_smooth: bool = False, gumbel=None, draws=None):
+                       force_idx=None, trace: bool = False, mask_first: bool = True, more_smooth: bool = False, gumbel=None, draws=None, rows=None):
         """the 10-scale loop on device-resident inputs only (capturable in a HIP graph: no host sync, static shapes).
-        draws (sampler='torch'): the noise of each sampling call comes from the caller's torch generator (_TorchDraws)"""
+        draws (sampler='torch'): the noise of each sampling call comes from the caller's torch generator (_TorchDraws).
+        rows (per-request mode): device views (seed, top_k, top_p, coef [nstage][B][4]) of a _RequestTable; the sampling call of every scale
+        is then the per-row one and cfg_scale / top_k / top_p / seed are not used"""
         cfg, P = self.cfg, self._pack()
         vae: VQVAE = self.vae_proxy[0]
         py, mf, C = cfg.pyramid, cfg.mask_factor, cfg.C
@@ -1238,7 +1386,9 @@ class ControlVAR(nn.Module):
             l = py.l[si]
             ratio = si / (nstage - 1)
             logits = self._blocks_and_head(x[:R * l], ada, R, l, py.begin[si], py.L, arena, lvl_end=inf_lvl, holes=inf_holes)
-            if four_way:
+            if rows is not None:
+                coef = None                                              # _request_table built them with the expressions below
+            elif four_way:
                 t1, t2, t3 = [c * ratio for c in cfg_scale]
                 coef = [1 + t1, t2 - t1, t3 - t2, -t3]
             else:
@@ -1250,7 +1400,9 @@ class ControlVAR(nn.Module):
             mg = torch.empty(B, l, device=dev, dtype=torch.float32) if trace else None
             expo, g_si = self._torch_noise(draws, n_draw * B, l, more_smooth)
             soft = None
-            if more_smooth and top_k != 1:
+            if rows is not None:
+                ops.cfg_sample_rows(logits, B, nrep, l, cfg.vocab, rows[3][si], rows[1], rows[2], rows[0], si, n_draw, idx, comb, mg, ldv=cfg.head_ld)
+            elif more_smooth and top_k != 1:
                 if gumbel is not None:
                     g_si = gumbel[si].to(device=dev, dtype=torch.float32).contiguous()          # greedy: the in-place masked softmax is one-hot, i.e. exactly E[idx] (control_var.py:511-515)
                 soft = torch.empty(n_draw * B, l, cfg.cvae, device=dev, dtype=torch.float32)
@@ -1394,11 +1546,59 @@ class ControlVAR(nn.Module):
         return graph, out, owned
 
     @torch.no_grad()
-    def graphed_generator(self, B: int, cfg=1.5, top_k: int = 0, top_p: float = 0.0):
+    def _capture_per_request(self, B, four_way, labels_all, types_all, cfg, top_k, top_p, finish, teach=None, refresh=None, prologue=None):
+        """per_request=True of the two graphed generators: capture the scale loop with the per-row sampler on a static _RequestTable and return
+        run(label_B, cond_type[, given_half], g_seed=None, cfg=..., top_k=..., top_p=...).  refresh(given_half) validates the given half and
+        returns the copy into its static buffer (conditional form); prologue() runs inside the graph before the scale loop"""
+        dev, vocab, nstage = self.device, self.cfg.vocab, len(self.cfg.pyramid.patch_nums)
+        tab_dev = _request_table(B, cfg, top_k, top_p, 0, four_way, vocab, nstage).host.to(dev)          # also validates the defaults
+        rows = _RequestTable(B, nstage).views(tab_dev)
+
+        def body():
+            if prologue is not None:
+                prologue()
+            return finish(self._generate_core(B, labels_all, types_all, 0, None, None, None, None, four_way, rows=rows, **(teach or {})))
+
+        graph, out, owned = self._capture(body)
+
+        def replay(label_B, cond_type, g_seed, r_cfg, r_top_k, r_top_p, given_half=None):
+            # everything that can refuse runs before the first static buffer is written
+            self._check_per_request(label_B, cond_type, four_way)
+            for name, v in (('label_B', label_B), ('cond_type', cond_type)):
+                if torch.is_tensor(v) and tuple(v.shape) != (B,):
+                    raise ValueError(f'{name}: expected shape ({B},), got {tuple(v.shape)}')
+            table = _request_table(B, r_cfg, r_top_k, r_top_p, g_seed, four_way, vocab, nstage)
+            la, ta = self._prepare_rows(B, label_B, cond_type, four_way, 0)
+            copy_given = refresh(given_half) if refresh is not None else None
+            labels_all.copy_(la)
+            if types_all is not None:
+                types_all.copy_(ta)
+            if copy_given is not None:
+                copy_given()
+            tab_dev.copy_(table.host)                       # seeds, top_k, top_p and every stage's weights: one host-to-device copy
+            graph.replay()
+            return out.clone()
+
+        if refresh is None:
+            def run(label_B, cond_type=None, g_seed=None, cfg=cfg, top_k=top_k, top_p=top_p):
+                return replay(label_B, cond_type, g_seed, cfg, top_k, top_p)
+        else:
+            def run(label_B, cond_type, given_half, g_seed=None, cfg=cfg, top_k=top_k, top_p=top_p):
+                return replay(label_B, cond_type, g_seed, cfg, top_k, top_p, given_half)
+        run.graph = graph
+        run.owned = owned                                   # dropped together with the graph when `run` goes away
+        return run
+
+    @torch.no_grad()
+    def graphed_generator(self, B: int, cfg=1.5, top_k: int = 0, top_p: float = 0.0, per_request: bool = False):
         """Capture one full `autoregressive_infer_cfg` (10 scales x depth blocks + both VQVAE decodes, ~2.5k launches) in a
         HIP graph and return ``run(label_B, cond_type=None, g_seed=None) -> images``.  Labels, condition types and the
         sampling seed live in static device buffers that are refreshed before each replay, so every call draws new samples.
-        Removes the host launch cost that dominates small batches (the reference's loop is host-launched op by op)."""
+        Removes the host launch cost that dominates small batches (the reference's loop is host-launched op by op).
+        per_request=True captures the per-row sampler instead: cfg, top_k, top_p and the seed of every row live in one static table that
+        one copy refreshes, and ``run(label_B, cond_type, g_seed=None, cfg=..., top_k=..., top_p=...)`` takes each as a scalar or per row
+        (those given here are its defaults) - one graph serves every mix of guidance scales, greedy beside sampled.  Row b of a replay is
+        what autoregressive_infer_cfg(B, ...) gives in per-request mode; everything is validated on the host before a buffer is touched."""
         dev = self.device
         four_way = False
         if self.sampler == 'torch':
@@ -1409,10 +1609,13 @@ class ControlVAR(nn.Module):
         lab0 = torch.zeros(B, dtype=torch.int64)
         ty0 = torch.zeros(B, dtype=torch.int64) if self.cfg.mask_factor == 2 else None
         labels_all, types_all = self._prepare_rows(B, lab0, ty0, four_way, 0)
+        if per_request:
+            return self._capture_per_request(B, four_way, labels_all, types_all, cfg, top_k, top_p, self._decode_pair)
         seed_dev = torch.zeros(1, device=dev, dtype=torch.int64)
         graph, out, owned = self._capture(lambda: self._decode_pair(self._generate_core(B, labels_all, types_all, 0, seed_dev, cfg, top_k, top_p, four_way)))
 
-        def run(label_B, cond_type=None, g_seed=None):
+        def run(label_B, cond_type=None, g_seed=None, **request):
+            _refuse_request_keywords(g_seed, request)
             seed = int(g_seed) if g_seed is not None else int(torch.empty((), dtype=torch.int64).random_().item())
             la, ta = self._prepare_rows(B, label_B, cond_type, four_way, seed)
             labels_all.copy_(la)
@@ -1428,7 +1631,7 @@ class ControlVAR(nn.Module):
 
     @torch.no_grad()
     def graphed_conditional_generator(self, B: int, given: str = 'control', cfg=(1.5, 1.5, 1.5), top_k: int = 0, top_p: float = 0.0,
-                                      source: str = 'ids', decode: str = 'both'):
+                                      source: str = 'ids', decode: str = 'both', per_request: bool = False):
         """Capture one full `conditional_infer_cfg` in a HIP graph - control in, image out (given='control': the control ids are teacher-forced
         as `c_mask=`, the image is generated) or image in, control out (given='image', `c_img=`) - and return
         ``run(label_B, cond_type, given_half, g_seed=None) -> images``.
@@ -1439,7 +1642,9 @@ class ControlVAR(nn.Module):
         (B, 3, H, H), one decoder pass of B images instead of 2 B.
         Labels, condition types (their 4 B-row forms), the seed, the given ids (int32 (B, sum pn^2)) and the pixels live in static device
         buffers refreshed before each replay.  more_smooth is not offered under capture; bidirectional models are captured as they are (the
-        four-branch path never draws the order)."""
+        four-branch path never draws the order).
+        per_request=True: as graphed_generator's - ``run(label_B, cond_type, given_half, g_seed=None, cfg=..., top_k=..., top_p=...)`` with each of
+        g_seed / cfg / top_k / top_p a scalar (cfg: one triple) or per row (cfg: (B, 3)); those given here are the defaults of run."""
         if self.mask_factor != 2:
             raise NotImplementedError('graphed_conditional_generator needs mask_factor == 2 (control_var.py:333)')
         if self.sampler == 'torch':
@@ -1451,16 +1656,17 @@ class ControlVAR(nn.Module):
         for name, val, ok in (('given', given, ('control', 'image')), ('source', source, ('ids', 'pixels')), ('decode', decode, ('both', 'generated'))):
             if val not in ok:
                 raise ValueError(f'{name}={val!r}: one of {" / ".join(ok)}')
-        try:
-            cfg = tuple(float(c) for c in cfg)
-        except TypeError:
-            cfg = ()
-        if len(cfg) != 3:
-            raise ValueError('cfg: three guidance scales (t1, t2, t3) as in conditional_infer_cfg')
         if int(B) != B or B < 1:
             raise ValueError(f'B={B!r}: a positive batch size')
-        if top_k > self.cfg.vocab:                          # as _generate (helpers.py:8-10)
-            raise RuntimeError(f'selected index k out of range (top_k={top_k} > vocabulary {self.cfg.vocab})')
+        if not per_request:                                 # per_request: _request_table checks the defaults, which may come per row
+            try:
+                cfg = tuple(float(c) for c in cfg)
+            except TypeError:
+                cfg = ()
+            if len(cfg) != 3:
+                raise ValueError('cfg: three guidance scales (t1, t2, t3) as in conditional_infer_cfg')
+            if top_k > self.cfg.vocab:                      # as _generate (helpers.py:8-10)
+                raise RuntimeError(f'selected index k out of range (top_k={top_k} > vocabulary {self.cfg.vocab})')
         dev = self.device
         vae: VQVAE = self.vae_proxy[0]
         pns = self.cfg.pyramid.patch_nums
@@ -1472,23 +1678,26 @@ class ControlVAR(nn.Module):
         ids_Bl = vae._split(ids_buf)                        # per-scale views of the static buffer: what _generate_core teacher-forces from
         teach = {'c_mask' if given == 'control' else 'c_img': ids_Bl}
 
-        def body():
+        def tokenise():
             if pix_buf is not None:
                 ids_buf.copy_(vae._ms_encode(vae._encode_f(pix_buf))[0])
-            f_hat = self._generate_core(B, labels_all, types_all, 0, seed_dev, cfg, top_k, top_p, True, **teach)
+
+        def finish(f_hat):
             if decode == 'both':
                 return self._decode_pair(f_hat)
             return vae._decode(f_hat[:, 1 if given == 'control' else 0].contiguous(), lo=-1.0, hi=1.0, mul=0.5, add=0.5)
 
-        graph, out, owned = self._capture(body)
+        def body():
+            tokenise()
+            return finish(self._generate_core(B, labels_all, types_all, 0, seed_dev, cfg, top_k, top_p, True, **teach))
 
         def as_rows(name, v):
             if torch.is_tensor(v) and tuple(v.shape) != (B,):
                 raise ValueError(f'{name}: expected shape ({B},), got {tuple(v.shape)}')
             return v
 
-        def run(label_B, cond_type, given_half, g_seed=None):
-            label_B, cond_type = as_rows('label_B', label_B), as_rows('cond_type', cond_type)
+        def as_given(given_half):
+            """the given half as run() takes it, checked on the host -> what is copied into the static pixel / id buffer"""
             if pix_buf is not None:
                 if not torch.is_tensor(given_half) or tuple(given_half.shape) != tuple(pix_buf.shape) or not given_half.is_floating_point():
                     raise ValueError(f'given_half: expected pixels of shape {tuple(pix_buf.shape)} (floating point, in [-1, 1]), got '
@@ -1503,6 +1712,22 @@ class ControlVAR(nn.Module):
                     raise ValueError(f'given_half: expected integer ids of shape ({B}, {Ltot}) or a list of (B, pn * pn) tensors, got '
                                      f'{tuple(given_half.shape) if torch.is_tensor(given_half) else type(given_half).__name__}')
                 _check_index_range(given_half, 0, self.cfg.vocab - 1, 'c_mask' if given == 'control' else 'c_img')
+            return given_half
+
+        if per_request:
+            def refresh(given_half):
+                checked = as_given(given_half)
+                return lambda: (pix_buf if pix_buf is not None else ids_buf).copy_(checked)
+
+            run = self._capture_per_request(B, True, labels_all, types_all, cfg, top_k, top_p, finish, teach=teach, prologue=tokenise, refresh=refresh)
+            run.ids = lambda: ids_buf.clone()
+            return run
+        graph, out, owned = self._capture(body)
+
+        def run(label_B, cond_type, given_half, g_seed=None, **request):
+            _refuse_request_keywords(g_seed, request)
+            label_B, cond_type = as_rows('label_B', label_B), as_rows('cond_type', cond_type)
+            given_half = as_given(given_half)
             seed = int(g_seed) if g_seed is not None else int(torch.empty((), dtype=torch.int64).random_().item())
             la, ta = self._prepare_rows(B, label_B, cond_type, True, seed)
             labels_all.copy_(la)
@@ -1545,7 +1770,7 @@ class ControlVAR(nn.Module):
         """control_var.py:223-354: 4-branch CFG with teacher forcing of the control (c_mask) or image (c_img) ids."""
         if self.mask_factor != 2:
             raise NotImplementedError('conditional_infer_cfg needs mask_factor == 2 (control_var.py:333)')
-        f_hat = self._generate(B, label_B, g_seed, tuple(cfg), top_k, top_p, more_smooth, cond_type, True, c_mask, c_img, _force_idx, _trace, _gumbel)
+        f_hat = self._generate(B, label_B, g_seed, cfg, top_k, top_p, more_smooth, cond_type, True, c_mask, c_img, _force_idx, _trace, _gumbel)
         return self._decode_pair(f_hat)
 
     def forward(self, label_B: torch.LongTensor, x_BLCv_wo_first_l: torch.Tensor, cond_type=None, mask_first=True) -> torch.Tensor:

@@ -253,6 +253,24 @@ def cfg_sample(logits: torch.Tensor, B: int, nrep: int, l: int, V: int, coef: Se
     return idx_out
 
 
+def cfg_sample_rows(logits: torch.Tensor, B: int, nrep: int, l: int, V: int, coef: torch.Tensor, top_k: torch.Tensor, top_p: torch.Tensor,
+                    seed: torch.Tensor, stage: int, n_draw: int, idx_out: torch.Tensor, combined: Optional[torch.Tensor] = None,
+                    margin: Optional[torch.Tensor] = None, kept: Optional[torch.Tensor] = None, ldv: int = 0,
+                    expo: Optional[torch.Tensor] = None, soft_out: Optional[torch.Tensor] = None):
+    """cfg_sample with one parameter set per batch row (cvar_cfg_sample_rows, include/cvar_serve.h): coef (B, 4) float32 - this stage's
+    combine weights, rounded on the host -, top_k (B,) int32, top_p (B,) float32, seed (B,) int64 (the uint64 seed's bit pattern), all
+    contiguous on the device of `logits`.  Row b equals cfg_sample at B = 1 on that row's logits with coef[b], top_k[b], top_p[b] and
+    seed[b], bit for bit.  expo / soft_out are refused by the library (CvarError): the per-row form draws from the counter generator only."""
+    for name, t, dtype, shape in (('coef', coef, torch.float32, (B, 4)), ('top_k', top_k, torch.int32, (B,)), ('top_p', top_p, torch.float32, (B,)),
+                                  ('seed', seed, torch.int64, (B,))):
+        if t is not None and (not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != logits.device):
+            raise ValueError(f'cfg_sample_rows: {name} must be a contiguous {str(dtype)[6:]} {shape} tensor on {logits.device}')
+    check(_lib.load().cvar_cfg_sample_rows(_ptr(logits), B, nrep, l, V, _ptr(coef), _ptr(top_k), _ptr(top_p), _ptr(seed), stage, n_draw,
+                                           _ptr(idx_out), _ptr(combined), _ptr(margin), _ptr(kept), int(ldv), _ptr(expo), _ptr(soft_out), _stream()),
+          'cvar_cfg_sample_rows')
+    return idx_out
+
+
 def ms_next_input(idx: torch.Tensor, codebook, phi_w, phi_b, up, down, f_hat, tok_out, nb, nmaps, pn, pn_next, S, Cvae,
                   phi_k: int, up_off: int, down_off: int):
     lib = _lib.load()

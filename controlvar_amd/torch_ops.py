@@ -377,6 +377,23 @@ _define('cfg_sample', '(Tensor logits, int B, int nrep, float[] coef, int top_k,
         lambda logits, B, nrep, coef, top_k, top_p, seed, stage, n_draw=1, expo=None: logits.new_empty(n_draw * B, logits.shape[1], dtype=torch.int32))
 
 
+def _cfg_sample_rows(logits, B, nrep, coef, top_k, top_p, seed, stage, n_draw=1):
+    """cfg_sample with one (coef, top_k, top_p, seed) per batch row (include/cvar_serve.h): logits (nrep*B, l, V) fp32, coef (B, 4) fp32 (this
+    stage's weights), top_k (B,) int32, top_p (B,) fp32, seed (B,) int64 -> ids (n_draw*B, l) int32.  Row b is cfg_sample at B = 1 with
+    row b's values, bit for bit, in whatever slot it rides"""
+    if logits.dtype != torch.float32 or logits.dim() != 3 or logits.shape[0] != nrep * B:
+        raise ValueError('cfg_sample_rows: logits must be float32 (nrep*B, l, V)')
+    _, l, V = logits.shape
+    idx = torch.empty(n_draw * B, l, device=logits.device, dtype=torch.int32)
+    K.cfg_sample_rows(logits.contiguous(), B, nrep, l, V, coef, top_k, top_p, seed, stage, n_draw, idx)
+    return idx
+
+
+_define('cfg_sample_rows', '(Tensor logits, int B, int nrep, Tensor coef, Tensor top_k, Tensor top_p, Tensor seed, int stage, int n_draw=1) -> Tensor',
+        _cfg_sample_rows,
+        lambda logits, B, nrep, coef, top_k, top_p, seed, stage, n_draw=1: logits.new_empty(n_draw * B, logits.shape[1], dtype=torch.int32))
+
+
 # ------------------------------------------------------------------------------------------------------------------- quantizer pyramid
 def _ms_encode(f, codebook, phi_w, phi_b, phi_map, patch_nums, up, down):
     """f (B, Cvae, S, S) fp32 -> (ids (B, sum pn^2) int32, f_hat (B, Cvae, S, S))   (quant.py:184-215)"""

@@ -1,0 +1,45 @@
+/* cvar_serve.h - entry points with no counterpart in the reference; same rules as cvar.h: plain pointers + sizes + stream,
+ * no allocation, asynchronous, negative `cvar_status` on error.
+ *
+ * The functions live in the same libcvar_hip.so as those of cvar.h.  They are versioned on their own: cvar_serve_version() bumps on
+ * any signature change in THIS header, cvar_abi_version() stays the version of cvar.h.
+ */
+#ifndef CVAR_SERVE_H
+#define CVAR_SERVE_H
+
+#include "cvar.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+int cvar_serve_version(void);               /* 1 */
+
+/* ---------------------------------------------------------------------------------------------
+ * CFG combine + sampling with one parameter set per batch row (a row = one request of a serving batch).
+ * As cvar_cfg_sample, with its scalar coef_host / top_k / top_p / seed / seed_dev replaced by DEVICE tables indexed by the batch row b:
+ *   coef  [B][4] fp32   combine weights of THIS stage (entries >= nrep are not used), added up as ((c0 l0 + c1 l1) + c2 l2) + c3 l3 with
+ *                       separately rounded products.  The caller rounds them to fp32 on the host; the kernel never derives them from a
+ *                       guidance scale (a contracted 1 + cfg * ratio would change bits);
+ *   top_k [B]    int32  <= 0 or >= V: no top-k filter; 1: greedy - argmax, lowest index on ties, kept = 1, the same id in all n_draw
+ *                       rows - inside the same launch, for that row only;
+ *   top_p [B]    fp32   <= 0: no nucleus filter;
+ *   seed  [B]    uint64 stored as its int64 bit pattern.
+ * The draw of row b, draw row d, token t is keyed by (seed[b], stage, d, t): the key cvar_cfg_sample forms at B = 1.  Row b of one call
+ * therefore equals - idx_out (all n_draw rows), combined, margin and kept, bit for bit - the call
+ *   cvar_cfg_sample(logits of row b, B = 1, ..., coef[b], top_k[b], top_p[b], seed[b], seed_dev = NULL, ...)
+ * and does not depend on the slot b or on the other rows.
+ * logits [nrep*B][l][ldv], idx_out [n_draw*B][l], the optional combined [B][l][V] / margin [B][l] / kept [B][l] and ldv: as there.
+ * nrep 1..4, n_draw 1..4, V <= 4096 (CVAR_EUNSUPPORTED otherwise); a NULL table is CVAR_EINVAL.  The values IN the tables are not
+ * checked (they are on the device): the caller keeps top_k <= V as it does for the scalar call.
+ * expo, soft_out: the caller-drawn noise and the more_smooth output of cvar_cfg_sample have no per-row form; both must be NULL,
+ * anything else returns CVAR_EUNSUPPORTED (never a silent fallback to the counter draw or to hard ids). */
+int cvar_cfg_sample_rows(const float* logits, int B, int nrep, int l, int V,
+                         const float* coef /* [B][4] */, const int32_t* top_k /* [B] */, const float* top_p /* [B] */, const int64_t* seed /* [B] */,
+                         int stage, int n_draw, int32_t* idx_out, float* combined, float* margin, int32_t* kept, int ldv,
+                         const float* expo /* must be NULL */, float* soft_out /* must be NULL */, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif
