@@ -5,6 +5,9 @@
 //   sample : radix-select thresholds for top-k (ties kept, helpers.py:9-10) and the nucleus cut on the ascending
 //            cumulative mass (helpers.py:12-15), inverse-CDF draw from a counter-based generator (no sort); or, with caller-drawn
 //            Exp(1) noise q, torch.multinomial's draw for one sample per row: argmax(p / q) over the softmax p of the masked logits.
+//   One text serves the scalar launch (cvar_cfg_sample: parameters in the kernel arguments) and the per-request launch (cvar_cfg_sample_rows: one
+//   parameter set per batch row in device tables): greedy_token and sample_token are templates on the parameter struct and reach whatever differs
+//   per row through the accessors below, nothing else.
 #include "cvar_common.h"
 #include "../../include/cvar_serve.h"
 
@@ -34,23 +37,51 @@ struct SampleParams {
     const float* expo;
 };
 
+// Per-request form (include/cvar_serve.h): one batch row = one request.  Combine weights, top_k, top_p and seed are read per row b from device
+// tables (block-uniform loads: one workgroup per token).  No expo / soft_out: cvar_cfg_sample_rows refuses both.
+struct RowSampleParams {
+    const float* logits;
+    int B, nrep, l, V, ldv;
+    const float* coef;                      // [B][4] fp32, this stage's weights (host-rounded: never recomputed from cfg_b here)
+    const int* top_k;                       // [B]   <= 0 or >= V: no top-k filter; 1: greedy
+    const float* top_p;                     // [B]
+    const unsigned long long* seed;         // [B]
+    int stage, n_draw;
+    int* idx_out;
+    float* combined;
+    float* margin;
+    int* kept;
+};
+
+// ---- what differs between the two forms: where a row's parameters come from, and which row keys the generator --------------------------------
+// The per-request draw is keyed by (seed_b, stage, d, t) - the key the scalar form builds at B = 1, where d * 1 + 0 = d.  With everything else in
+// one text, row b of a per-request launch is bit for bit the scalar launch at B = 1 on that row's logits, whatever rides beside it.
+// seed_of is evaluated where a draw uses it, never handed down as a value: a by-value seed costs the SOFT instances 28 VGPRs and a wave per SIMD.
+__device__ __forceinline__ const float* coef_of(const SampleParams& p, long) { return p.coef; }
+__device__ __forceinline__ const float* coef_of(const RowSampleParams& p, long b) { return p.coef + b * 4; }
+__device__ __forceinline__ int top_k_of(const SampleParams& p, long) { return p.top_k; }
+__device__ __forceinline__ int top_k_of(const RowSampleParams& p, long b) { return p.top_k[b]; }
+__device__ __forceinline__ float top_p_of(const SampleParams& p, long) { return p.top_p; }
+__device__ __forceinline__ float top_p_of(const RowSampleParams& p, long b) { return p.top_p[b]; }
+__device__ __forceinline__ unsigned long long seed_of(const SampleParams& p, long) { return p.seed + (p.seed_dev ? p.seed_dev[0] : 0ull); }
+__device__ __forceinline__ unsigned long long seed_of(const RowSampleParams& p, long b) { return p.seed[b]; }
+__device__ __forceinline__ long key_row(const SampleParams& p, int d, long b) { return (long)d * p.B + b; }
+__device__ __forceinline__ long key_row(const RowSampleParams&, int d, long) { return d; }
+
 __device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
     x += 0x9E3779B97F4A7C15ull;
     x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
     x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
     return x ^ (x >> 31);
 }
-__device__ __forceinline__ float uniform01(unsigned long long seed, int stage, long row, int t) {
-    unsigned long long h = splitmix64(seed ^ 0xC0FFEE1234ull);
-    h = splitmix64(h ^ ((unsigned long long)stage << 48) ^ ((unsigned long long)row << 16) ^ (unsigned long long)t);
-    return (float)(h >> 40) * (1.0f / 16777216.0f);           // 24 random bits -> [0,1)
-}
 
-__device__ __forceinline__ float combine_logits(const SampleParams& p, long b, long t, int e) {
+template <class P>
+__device__ __forceinline__ float combine_logits(const P& p, long b, long t, int e) {
     const long rowstride = (long)p.l * p.ldv;
     const float* base = p.logits + (b * p.l + t) * p.ldv + e;
-    float v = __fmul_rn(p.coef[0], base[0]);
-    for (int r = 1; r < p.nrep; ++r) v = __fadd_rn(v, __fmul_rn(p.coef[r], base[(long)r * p.B * rowstride]));
+    const float* cf = coef_of(p, b);
+    float v = __fmul_rn(cf[0], base[0]);
+    for (int r = 1; r < p.nrep; ++r) v = __fadd_rn(v, __fmul_rn(cf[r], base[(long)r * p.B * rowstride]));
     return v;
 }
 
@@ -63,7 +94,9 @@ __device__ __forceinline__ Top2 merge_top2(Top2 a, Top2 b) {
     return o;
 }
 
-__global__ __launch_bounds__(256) void cfg_greedy_kernel(const SampleParams p) {
+// argmax with the lowest index among tied maxima, the id in all n_draw rows, kept = 1
+template <class P>
+__device__ __forceinline__ void greedy_token(const P& p) {
     __shared__ float sb1[4], sb2[4];
     __shared__ int si1[4];
     const int tid = threadIdx.x;
@@ -92,6 +125,8 @@ __global__ __launch_bounds__(256) void cfg_greedy_kernel(const SampleParams p) {
         if (p.kept) p.kept[bt] = 1;
     }
 }
+
+__global__ __launch_bounds__(256) void cfg_greedy_kernel(const SampleParams p) { greedy_token(p); }
 
 // ---- top-k / top-p sampling without a sort ---------------------------------------------------------------------
 // Both filters of helpers.py:8-15 are VALUE thresholds: top-k keeps v >= (k-th largest value) (ties kept), the nucleus
@@ -135,8 +170,8 @@ __device__ __forceinline__ bool race_before(float a, int ia, float b, int ib) {
 // SOFT = false (every launch without more_smooth): the soft-embedding block and its registers compile away (146 -> ~90 VGPRs: the kernel is
 // bound by memory and LDS latency, and went 44 % slower when the block cost it two of its five waves per SIMD).
 // RACE = true (expo != NULL): the draw is torch.multinomial's one-sample path on the caller's noise; RACE = false compiles the counter draw only.
-template <bool SOFT, bool RACE>
-__global__ __launch_bounds__(256) void cfg_sample_kernel(const SampleParams p) {
+template <bool SOFT, bool RACE, class P>
+__device__ __forceinline__ void sample_token(const P& p) {
     constexpr int EPT = 16;
     typedef unsigned long long u64;
     __shared__ int hist_cnt[256];
@@ -182,9 +217,10 @@ __global__ __launch_bounds__(256) void cfg_sample_kernel(const SampleParams p) {
 
     // ---- top-k threshold key
     unsigned tk = 0;
-    if (p.top_k > 0 && p.top_k < p.V) {
+    const int top_k = top_k_of(p, b);
+    if (top_k > 0 && top_k < p.V) {
         unsigned prefix = 0;
-        int kk = p.top_k;
+        int kk = top_k;
         for (int ps = 3; ps >= 0; --ps) {
             hist_cnt[tid] = 0;
             if (tid == 0) { sel_digit = 0u; sel_k = kk; }
@@ -220,13 +256,14 @@ __global__ __launch_bounds__(256) void cfg_sample_kernel(const SampleParams p) {
     (void)block_excl_scan<u64>(local, wsum64, Z);
     // ---- nucleus threshold key: smallest key whose ascending cumulative mass exceeds (1 - top_p) * Z
     unsigned tp = 0;
-    if (p.top_p > 0.f) {
+    const float top_p = top_p_of(p, b);
+    if (top_p > 0.f) {
         // (1 - top_p) in double and clamped: top_p < 2^-24 would round 1 - top_p to 1 in float (lim == Z: no bucket qualifies), and
         // top_p > 1 would cast a negative double to u64.  lim <= Z - 1 guarantees that exactly one bucket per pass satisfies the
         // selection below; Z > 0 always (the maximum carries mass 2^40).  The last (largest) element is therefore always kept, as
         // helpers.py:14 does.  Elements TIED with the cut value are all kept here (value threshold), where the reference cuts
         // inside the tie by sort order - a difference only for exactly equal logits.
-        const double keep_from = fmin(fmax(1.0 - (double)p.top_p, 0.0), 1.0);
+        const double keep_from = fmin(fmax(1.0 - (double)top_p, 0.0), 1.0);
         u64 lim = (u64)(keep_from * (double)Z);
         if (lim >= Z) lim = Z - 1;
         unsigned prefix = 0;
@@ -315,8 +352,8 @@ __global__ __launch_bounds__(256) void cfg_sample_kernel(const SampleParams p) {
         }
     } else {
         for (int d = 0; d < p.n_draw; ++d) {
-            unsigned long long h = splitmix64((p.seed + (p.seed_dev ? p.seed_dev[0] : 0ull)) ^ 0xC0FFEE1234ull);
-            h = splitmix64(h ^ ((unsigned long long)p.stage << 48) ^ ((unsigned long long)((long)d * p.B + b) << 16) ^ (unsigned long long)t);
+            unsigned long long h = splitmix64(seed_of(p, b) ^ 0xC0FFEE1234ull);
+            h = splitmix64(h ^ ((unsigned long long)p.stage << 48) ^ ((unsigned long long)key_row(p, d, b) << 16) ^ (unsigned long long)t);
             const double u = (double)(h >> 11) * (1.0 / 9007199254740992.0);       // 53 bits -> [0,1)
             u64 target = (u64)(u * (double)Zk);
             if (target >= Zk) target = Zk > 0 ? Zk - 1 : 0;
@@ -350,8 +387,8 @@ __global__ __launch_bounds__(256) void cfg_sample_kernel(const SampleParams p) {
                     float g;
                     if (p.gumbel) g = p.gumbel[(row * p.l + t) * (long)p.V + e];
                     else {
-                        unsigned long long h = splitmix64((p.seed + (p.seed_dev ? p.seed_dev[0] : 0ull)) ^ 0x5EEDF00D77ull);
-                        h = splitmix64(h ^ ((unsigned long long)p.stage << 52) ^ ((unsigned long long)row << 28) ^ ((unsigned long long)t << 12) ^ (unsigned long long)e);
+                        unsigned long long h = splitmix64(seed_of(p, b) ^ 0x5EEDF00D77ull);
+                        h = splitmix64(h ^ ((unsigned long long)p.stage << 52) ^ ((unsigned long long)key_row(p, d, b) << 28) ^ ((unsigned long long)t << 12) ^ (unsigned long long)e);
                         const float u = ((float)(h >> 40) + 0.5f) * (1.0f / 16777216.0f);          // (0, 1)
                         g = -__logf(-__logf(u));                                                 // -log(Exp(1) sample)
                     }
@@ -400,6 +437,16 @@ __global__ __launch_bounds__(256) void cfg_sample_kernel(const SampleParams p) {
     }
 }
 
+template <bool SOFT, bool RACE>
+__global__ __launch_bounds__(256) void cfg_sample_kernel(const SampleParams p) { sample_token<SOFT, RACE>(p); }
+
+// A row with top_k_b == 1 leaves through greedy_token (lowest index among tied maxima, kept = 1), never through a draw among the ties.  The branch
+// is block-uniform and sits ahead of the sampler's sixteen loads per thread: a greedy reduction over those loaded values cost 121 VGPRs and a wave.
+__global__ __launch_bounds__(256) void cfg_sample_rows_kernel(const RowSampleParams p) {
+    if (p.top_k[blockIdx.x / p.l] == 1) { greedy_token(p); return; }
+    sample_token<false, false>(p);
+}
+
 extern "C" int cvar_cfg_sample(const float* logits, int B, int nrep, int l, int V, const float* coef_host,
                                int top_k, float top_p, uint64_t seed, const uint64_t* seed_dev, int stage, int n_draw,
                                int32_t* idx_out, float* combined, float* margin, int32_t* kept, int ldv,
@@ -427,212 +474,6 @@ extern "C" int cvar_cfg_sample(const float* logits, int B, int nrep, int l, int 
     else hipLaunchKernelGGL((cfg_sample_kernel<false, false>), grid, block, 0, as_stream(stream), p);
     CVAR_CHECK_LAUNCH();
     return CVAR_OK;
-}
-
-// ---- per-request form (include/cvar_serve.h) ---------------------------------------------------------------------
-// One batch row = one request: combine weights, top_k, top_p and seed are read per row b from device tables (block-uniform loads), and
-// the draw is keyed by (seed_b, stage, d, t) - the key cfg_sample_kernel forms at B = 1, where d * 1 + 0 = d.  Row b of a launch is
-// therefore bit for bit the B = 1 launch of the scalar kernels on that row's logits, whatever rides beside it; a row with
-// top_k_b == 1 leaves through cfg_greedy_kernel's reduction (lowest index among tied maxima, kept = 1), never through a draw among
-// the ties.  A kernel of its own: cfg_greedy_kernel and cfg_sample_kernel<SOFT, RACE> above compile to exactly what they compiled to
-// before it existed.  The steps below are those of cfg_sample_kernel<false, false>, statement by statement.
-struct RowSampleParams {
-    const float* logits;
-    int B, nrep, l, V, ldv;
-    const float* coef;                      // [B][4] fp32, this stage's weights (host-rounded: never recomputed from cfg_b here)
-    const int* top_k;                       // [B]   <= 0 or >= V: no top-k filter; 1: greedy
-    const float* top_p;                     // [B]
-    const unsigned long long* seed;         // [B]
-    int stage, n_draw;
-    int* idx_out;
-    float* combined;
-    float* margin;
-    int* kept;
-};
-
-// combine_logits with the row's weights: ((c0 l0 + c1 l1) + c2 l2) + c3 l3, separately rounded products
-__device__ __forceinline__ float combine_row(const RowSampleParams& p, const float* cf, const float* base, long repstride, int e) {
-    float v = __fmul_rn(cf[0], base[e]);
-    for (int r = 1; r < p.nrep; ++r) v = __fadd_rn(v, __fmul_rn(cf[r], base[(long)r * repstride + e]));
-    return v;
-}
-
-__global__ __launch_bounds__(256) void cfg_sample_rows_kernel(const RowSampleParams p) {
-    constexpr int EPT = 16;
-    typedef unsigned long long u64;
-    __shared__ int hist_cnt[256];
-    __shared__ u64 hist_mass[256];
-    __shared__ u64 wsum64[4];
-    __shared__ int wsum32[4];
-    __shared__ float wmaxs[4], wmax2[4];
-    __shared__ int wimax[4];
-    __shared__ unsigned sel_digit;
-    __shared__ u64 sel_below;
-    __shared__ int sel_k;
-    const int tid = threadIdx.x;
-    const long bt = blockIdx.x;
-    const long b = bt / p.l, t = bt % p.l;
-    const float* cf = p.coef + b * 4;
-    const int top_k = p.top_k[b];
-    const float top_p = p.top_p[b];
-    const u64 seed = p.seed[b];
-    const long rowstride = (long)p.l * p.ldv, repstride = (long)p.B * rowstride;
-    const float* base = p.logits + (b * p.l + t) * p.ldv;
-    if (top_k == 1) {                                  // block-uniform: cfg_greedy_kernel's loop and reduction, before the sampler's registers exist
-        Top2 g = {-INFINITY, 0x7fffffff, -INFINITY};
-        for (int e = tid; e < p.V; e += 256) {
-            const float x = combine_row(p, cf, base, repstride, e);
-            if (p.combined) p.combined[bt * p.V + e] = x;
-            Top2 cur = {x, e, -INFINITY};
-            g = merge_top2(g, cur);
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            Top2 other;
-            other.b1 = __shfl_xor(g.b1, o, 64); other.i1 = __shfl_xor(g.i1, o, 64); other.b2 = __shfl_xor(g.b2, o, 64);
-            g = merge_top2(g, other);
-        }
-        if ((tid & 63) == 0) { wmaxs[tid >> 6] = g.b1; wimax[tid >> 6] = g.i1; wmax2[tid >> 6] = g.b2; }
-        __syncthreads();
-        if (tid == 0) {
-            Top2 r = {wmaxs[0], wimax[0], wmax2[0]};
-            for (int w = 1; w < 4; ++w) { Top2 o = {wmaxs[w], wimax[w], wmax2[w]}; r = merge_top2(r, o); }
-            for (int d = 0; d < p.n_draw; ++d) p.idx_out[((long)d * p.B + b) * p.l + t] = r.i1;
-            if (p.margin) p.margin[bt] = r.b1 - r.b2;
-            if (p.kept) p.kept[bt] = 1;
-        }
-        return;
-    }
-    float v[EPT];
-    unsigned key[EPT];
-    float best = -INFINITY, second = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < EPT; ++i) {
-        const int e = i * 256 + tid;                   // thread-strided ownership: coalesced loads
-        float x = -INFINITY;
-        if (e < p.V) {
-            x = combine_row(p, cf, base, repstride, e);
-            if (p.combined) p.combined[bt * p.V + e] = x;
-        }
-        v[i] = x; key[i] = f2key(x);
-        if (x > best) { second = best; best = x; } else if (x > second) second = x;
-    }
-    // block max (+ second max for the margin output)
-    {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ob = __shfl_xor(best, o, 64), os = __shfl_xor(second, o, 64);
-            second = fmaxf(fminf(best, ob), fmaxf(second, os));
-            best = fmaxf(best, ob);
-        }
-        if ((tid & 63) == 0) { wmaxs[tid >> 6] = best; wmax2[tid >> 6] = second; }
-        __syncthreads();
-        best = wmaxs[0]; second = wmax2[0];
-        for (int w = 1; w < 4; ++w) { second = fmaxf(fminf(best, wmaxs[w]), fmaxf(second, wmax2[w])); best = fmaxf(best, wmaxs[w]); }
-        if (p.margin && tid == 0) p.margin[bt] = best - second;
-    }
-    const float vmax = best;
-
-    // ---- top-k threshold key
-    unsigned tk = 0;
-    if (top_k > 0 && top_k < p.V) {
-        unsigned prefix = 0;
-        int kk = top_k;
-        for (int ps = 3; ps >= 0; --ps) {
-            hist_cnt[tid] = 0;
-            if (tid == 0) { sel_digit = 0u; sel_k = kk; }
-            __syncthreads();
-#pragma unroll
-            for (int i = 0; i < EPT; ++i) {
-                const bool match = (ps == 3) || ((key[i] >> (8 * (ps + 1))) == prefix);
-                if (match && i * 256 + tid < p.V) atomicAdd(&hist_cnt[(key[i] >> (8 * ps)) & 255], 1);
-            }
-            __syncthreads();
-            const int dd = 255 - tid;                              // thread t owns digit 255-t: suffix counts become a prefix scan
-            const int c = hist_cnt[dd];
-            int tot;
-            const int above = block_excl_scan<int>(c, wsum32, tot);   // elements with a larger digit
-            if (above < kk && above + c >= kk) { sel_digit = (unsigned)dd; sel_k = kk - above; }
-            __syncthreads();
-            prefix = (prefix << 8) | sel_digit;
-            kk = sel_k;
-            __syncthreads();
-        }
-        tk = prefix;
-    }
-    // ---- quantised masses of the top-k set
-    u64 wq[EPT];
-    u64 local = 0;
-#pragma unroll
-    for (int i = 0; i < EPT; ++i) {
-        const bool in = (i * 256 + tid < p.V) && key[i] >= tk;
-        wq[i] = in ? (u64)(__expf(v[i] - vmax) * 1099511627776.0f) : 0ull;      // 2^40
-        local += wq[i];
-    }
-    u64 Z;
-    (void)block_excl_scan<u64>(local, wsum64, Z);
-    // ---- nucleus threshold key: smallest key whose ascending cumulative mass exceeds (1 - top_p) * Z (clamping as in cfg_sample_kernel)
-    unsigned tp = 0;
-    if (top_p > 0.f) {
-        const double keep_from = fmin(fmax(1.0 - (double)top_p, 0.0), 1.0);
-        u64 lim = (u64)(keep_from * (double)Z);
-        if (lim >= Z) lim = Z - 1;
-        unsigned prefix = 0;
-        u64 below = 0;
-        for (int ps = 3; ps >= 0; --ps) {
-            hist_mass[tid] = 0ull;
-            if (tid == 0) { sel_digit = 255u; sel_below = below; }      // defined even if no bucket were selected
-            __syncthreads();
-#pragma unroll
-            for (int i = 0; i < EPT; ++i) {
-                const bool match = (ps == 3) || ((key[i] >> (8 * (ps + 1))) == prefix);
-                if (match && wq[i]) atomicAdd(&hist_mass[(key[i] >> (8 * ps)) & 255], wq[i]);
-            }
-            __syncthreads();
-            const u64 c = hist_mass[tid];
-            u64 tot;
-            const u64 before = below + block_excl_scan<u64>(c, wsum64, tot);   // mass of smaller digits (ascending)
-            if (before <= lim && before + c > lim) { sel_digit = (unsigned)tid; sel_below = before; }
-            __syncthreads();
-            prefix = (prefix << 8) | sel_digit;
-            below = sel_below;
-            __syncthreads();
-        }
-        tp = prefix;
-    }
-    const unsigned thr = tk > tp ? tk : tp;
-    u64 keepsum = 0;
-    int nkeep = 0;
-#pragma unroll
-    for (int i = 0; i < EPT; ++i) {
-        if (!(key[i] >= thr && wq[i])) wq[i] = 0ull;
-        keepsum += wq[i];
-        nkeep += wq[i] ? 1 : 0;
-    }
-    u64 Zk;
-    const u64 excl = block_excl_scan<u64>(keepsum, wsum64, Zk);
-    if (p.kept) {
-        int tot;
-        (void)block_excl_scan<int>(nkeep, wsum32, tot);
-        if (tid == 0) p.kept[bt] = tot;
-    }
-    for (int d = 0; d < p.n_draw; ++d) {
-        u64 h = splitmix64(seed ^ 0xC0FFEE1234ull);
-        h = splitmix64(h ^ ((u64)p.stage << 48) ^ ((u64)d << 16) ^ (u64)t);       // row = d: the scalar kernel's d * B + b at B = 1
-        const double u = (double)(h >> 11) * (1.0 / 9007199254740992.0);       // 53 bits -> [0,1)
-        u64 target = (u64)(u * (double)Zk);
-        if (target >= Zk) target = Zk > 0 ? Zk - 1 : 0;
-        if (excl <= target && target < excl + keepsum) {                        // exactly one thread
-            u64 run = excl;
-            int pick = tid;
-#pragma unroll
-            for (int i = 0; i < EPT; ++i) {
-                run += wq[i];
-                if (run > target) { pick = i * 256 + tid; break; }
-            }
-            p.idx_out[((long)d * p.B + b) * p.l + t] = pick;
-        }
-    }
 }
 
 extern "C" int cvar_serve_version(void) { return 1; }
