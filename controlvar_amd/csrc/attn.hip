@@ -125,17 +125,28 @@ __global__ __launch_bounds__(256) void attn_rowwise_kernel(const AttnParams p) {
             lsum *= alpha;
 #pragma unroll
             for (int d = 0; d < D; ++d) o[d] *= alpha;
+            // The tile's row sum and its P V are summed from zero and join the running values with ONE addition each.  Added key by key, every
+            // P behind a late dominant key (running sum ~ 1, P ~ 4e-8 < half an ulp of it) was rounded away: at 4480 keys the tail of the keys went
+            // missing from lsum and O, 3e-5 of a row's norm and of lse - fourteen times what fp32 costs the same formula.
+            float tsum = 0.f;
 #pragma unroll
             for (int kk = 0; kk < KT; ++kk) {
                 float pr = __expf(s[kk] - m_new);
-                lsum += pr;
+                tsum += pr;
                 if constexpr (sizeof(T) == 2) pr = bf16_to_f32(f32_to_bf16(pr));   // P is a bf16 MFMA operand in bf16 mode
+                s[kk] = pr;
+            }
+            lsum += tsum;
 #pragma unroll
-                for (int d = 0; d < D; d += 4) {
+            for (int d = 0; d < D; d += 4) {
+                float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+#pragma unroll
+                for (int kk = 0; kk < KT; ++kk) {
                     const f32x4_t vv = *(const f32x4_t*)&Vs[kk][d];
-                    o[d] = fmaf(pr, vv[0], o[d]); o[d + 1] = fmaf(pr, vv[1], o[d + 1]);
-                    o[d + 2] = fmaf(pr, vv[2], o[d + 2]); o[d + 3] = fmaf(pr, vv[3], o[d + 3]);
+                    a0 = fmaf(s[kk], vv[0], a0); a1 = fmaf(s[kk], vv[1], a1);
+                    a2 = fmaf(s[kk], vv[2], a2); a3 = fmaf(s[kk], vv[3], a3);
                 }
+                o[d] += a0; o[d + 1] += a1; o[d + 2] += a2; o[d + 3] += a3;
             }
             m = m_new;
         }
