@@ -117,6 +117,9 @@ SERVE_VERSION = 1
 SERVE_SIGNATURES = {
     'cvar_serve_version': (c_i, []),
     'cvar_cfg_sample_rows': (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p]),
+    # region-constrained generation: joined at version 1 (an added entry point changes no signature)
+    'cvar_edit_force_table': (c_i, [c_p, c_p, c_p, c_p, C.POINTER(c_i), c_i, c_i, c_i, c_i, c_i, c_p, c_p]),
+    'cvar_cfg_sample_edit': (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_p]),
 }
 
 _lib = None

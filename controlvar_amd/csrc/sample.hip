@@ -447,6 +447,25 @@ __global__ __launch_bounds__(256) void cfg_sample_rows_kernel(const RowSamplePar
     sample_token<false, false>(p);
 }
 
+// Region-constrained generation (include/cvar_serve.h): token (b, t) is forced to forced[b * ldf + t] when that is >= 0.  The load is block-uniform
+// and sits ahead of everything else: a forced token leaves before it reads a logit.  forced / ldf ride beside RowSampleParams, not inside it, so
+// that cfg_sample_rows_kernel keeps its argument block and its instruction stream.
+__global__ __launch_bounds__(256) void cfg_sample_edit_kernel(const RowSampleParams p, const int* __restrict__ forced, const int ldf) {
+    const long bt = blockIdx.x;
+    const long b = bt / p.l, t = bt % p.l;
+    const int id = forced[b * ldf + t];
+    if (id >= 0) {
+        if (threadIdx.x == 0) {
+            for (int d = 0; d < p.n_draw; ++d) p.idx_out[((long)d * p.B + b) * p.l + t] = id;
+            if (p.margin) p.margin[bt] = INFINITY;
+            if (p.kept) p.kept[bt] = 0;
+        }
+        return;
+    }
+    if (p.top_k[b] == 1) { greedy_token(p); return; }
+    sample_token<false, false>(p);
+}
+
 extern "C" int cvar_cfg_sample(const float* logits, int B, int nrep, int l, int V, const float* coef_host,
                                int top_k, float top_p, uint64_t seed, const uint64_t* seed_dev, int stage, int n_draw,
                                int32_t* idx_out, float* combined, float* margin, int32_t* kept, int ldv,
@@ -491,6 +510,25 @@ extern "C" int cvar_cfg_sample_rows(const float* logits, int B, int nrep, int l,
     p.stage = stage; p.n_draw = n_draw;
     p.idx_out = idx_out; p.combined = combined; p.margin = margin; p.kept = kept;
     hipLaunchKernelGGL(cfg_sample_rows_kernel, dim3((unsigned)((long)B * l)), dim3(256), 0, as_stream(stream), p);
+    CVAR_CHECK_LAUNCH();
+    return CVAR_OK;
+}
+
+extern "C" int cvar_cfg_sample_edit(const float* logits, int B, int nrep, int l, int V, const float* coef, const int32_t* top_k,
+                                    const float* top_p, const int64_t* seed, int stage, int n_draw, int32_t* idx_out, float* combined,
+                                    float* margin, int32_t* kept, int ldv, const float* expo, float* soft_out, const int32_t* forced, int ldf,
+                                    void* stream) {
+    if (!logits || !coef || !top_k || !top_p || !seed || !idx_out || B <= 0 || l <= 0 || V <= 1) return CVAR_EINVAL;
+    if (!forced || ldf < l) return CVAR_EINVAL;
+    if (nrep < 1 || nrep > 4 || n_draw < 1 || n_draw > 4 || V > 4096) return CVAR_EUNSUPPORTED;
+    if (ldv != 0 && ldv < V) return CVAR_EINVAL;
+    if (expo || soft_out) return CVAR_EUNSUPPORTED;
+    RowSampleParams p;
+    p.logits = logits; p.B = B; p.nrep = nrep; p.l = l; p.V = V; p.ldv = ldv ? ldv : V;
+    p.coef = coef; p.top_k = (const int*)top_k; p.top_p = top_p; p.seed = (const unsigned long long*)seed;
+    p.stage = stage; p.n_draw = n_draw;
+    p.idx_out = idx_out; p.combined = combined; p.margin = margin; p.kept = kept;
+    hipLaunchKernelGGL(cfg_sample_edit_kernel, dim3((unsigned)((long)B * l)), dim3(256), 0, as_stream(stream), p, (const int*)forced, ldf);
     CVAR_CHECK_LAUNCH();
     return CVAR_OK;
 }

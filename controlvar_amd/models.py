@@ -842,6 +842,62 @@ def _refuse_request_keywords(g_seed, request: dict):
         raise ValueError('g_seed: one integer - this graph was captured with per_request=False; capture it with per_request=True for one seed per row')
 
 
+# ---- region-constrained generation (an addition of this library; include/cvar_serve.h) --------------------------------------------
+def edit_keep_cells(keep: torch.Tensor, pn: int) -> torch.Tensor:
+    """The cell rule of region-constrained generation on the host: keep (B, S, S) bool at latent resolution -> (B, pn * pn) bool, which tokens
+    of scale pn are forced to the source.  Cell (i, j) covers the latent rows floor(i S / pn) .. ceil((i + 1) S / pn) - 1 and the same columns -
+    the bins of F.interpolate(mode='area'), with which the quantizer forms that token (quant.py:199,238) - and is kept iff
+    2 * (kept latent cells in the bin) > bin size: a strict majority in integers, an exact half stays free.  cvar_edit_force_table is the
+    device form of this function."""
+    k = keep.detach().cpu().to(torch.int64)
+    B, S = k.shape[0], k.shape[-1]
+    out = torch.empty(B, pn, pn, dtype=torch.bool)
+    for i in range(pn):
+        r0, r1 = i * S // pn, -((-(i + 1) * S) // pn)
+        for j in range(pn):
+            c0, c1 = j * S // pn, -((-(j + 1) * S) // pn)
+            out[:, i, j] = 2 * k[:, r0:r1, c0:c1].sum(dim=(1, 2)) > (r1 - r0) * (c1 - c0)
+    return out.view(B, pn * pn)
+
+
+def _edit_half(half: str, src, keep, B: int, pns, vocab: int, pixels: bool = False):
+    """one half (img / ctrl) of an edit request, checked on the host -> (source or None, keep mask (B, S, S) uint8 or None).  The source is
+    returned as flat integer ids (B, sum pn^2) - or, with pixels=True, as the (B, 3, 16 S, 16 S) pixels it was given as -, on the device it
+    came on.  keep: True keeps the whole half, None nothing.  A mask without a source is a ValueError; a source without a mask is unused."""
+    S, Lsrc = pns[-1], sum(pn * pn for pn in pns)
+    if keep is None:
+        mask = None
+    elif keep is True:
+        mask = torch.ones(B, S, S, dtype=torch.uint8)
+    elif torch.is_tensor(keep) and keep.dtype == torch.bool and tuple(keep.shape) == (B, S, S):
+        mask = keep.to(torch.uint8)
+    else:
+        raise ValueError(f'keep_{half}: True, None or a bool tensor of shape ({B}, {S}, {S}) (latent resolution, True = keep the source) expected, got '
+                         f'{(str(keep.dtype)[6:] + " " + str(tuple(keep.shape))) if torch.is_tensor(keep) else repr(keep)[:40]}')
+    if src is None:
+        if mask is not None:
+            raise ValueError(f'keep_{half} is given without src_{half}: there is nothing to keep')
+        return None, None
+    if pixels:
+        want = (B, 3, 16 * S, 16 * S)
+        if not torch.is_tensor(src) or tuple(src.shape) != want or not src.is_floating_point():
+            raise ValueError(f'src_{half}: expected pixels of shape {want} (floating point, in [-1, 1]), got '
+                             f'{tuple(src.shape) if torch.is_tensor(src) else type(src).__name__}')
+        return src, mask
+    if isinstance(src, (list, tuple)):
+        want = [(B, pn * pn) for pn in pns]
+        if not all(torch.is_tensor(t) for t in src) or [tuple(t.shape) for t in src] != want:
+            raise ValueError(f'src_{half}: expected {len(pns)} id tensors of shapes {want} (what img_to_idxBl returns)')
+        if any(t.is_floating_point() or t.dtype == torch.bool for t in src):
+            raise ValueError(f'src_{half}: expected integer ids')
+        src = torch.cat([t.to(src[0].device) for t in src], dim=1)
+    if not torch.is_tensor(src) or tuple(src.shape) != (B, Lsrc) or src.is_floating_point() or src.dtype == torch.bool:
+        raise ValueError(f'src_{half}: expected integer ids of shape ({B}, {Lsrc}) or a list of (B, pn * pn) tensors, got '
+                         f'{tuple(src.shape) if torch.is_tensor(src) else type(src).__name__}')
+    _check_index_range(src, 0, vocab - 1, f'src_{half}')
+    return src, mask
+
+
 class ControlVAR(nn.Module):
     """Joint (control, image) next-scale transformer (reference: models/control_var.py:23-689).
 
@@ -1356,11 +1412,16 @@ class ControlVAR(nn.Module):
 
     @torch.no_grad()
     def _generate_core(self, B, labels_all, types_all, seed, seed_dev, cfg_scale, top_k, top_p, four_way, c_mask=None, c_img=None,
-                       force_idx=None, trace: bool = False, mask_first: bool = True, more_smooth: bool = False, gumbel=None, draws=None, rows=None):
+                       force_idx=None, trace: bool = False, mask_first: bool = True, more_smooth: bool = False, gumbel=None, draws=None, rows=None,
+                       forced=None):
         """the 10-scale loop on device-resident inputs only (capturable in a HIP graph: no host sync, static shapes).
         draws (sampler='torch'): the noise of each sampling call comes from the caller's torch generator (_TorchDraws).
         rows (per-request mode): device views (seed, top_k, top_p, coef [nstage][B][4]) of a _RequestTable; the sampling call of every scale
-        is then the per-row one and cfg_scale / top_k / top_p / seed are not used"""
+        is then the per-row one and cfg_scale / top_k / top_p / seed are not used.
+        forced (region-constrained generation, with rows only): device (B, L) int32, the source id of every kept token and -1 elsewhere
+        (ops.edit_force_table); the sampling launch of every scale then writes the kept ids itself (ops.cfg_sample_edit)"""
+        if forced is not None and (rows is None or four_way):
+            raise ValueError('forced: the per-request joint path only (rows given, two branches)')
         cfg, P = self.cfg, self._pack()
         vae: VQVAE = self.vae_proxy[0]
         py, mf, C = cfg.pyramid, cfg.mask_factor, cfg.C
@@ -1400,7 +1461,10 @@ class ControlVAR(nn.Module):
             mg = torch.empty(B, l, device=dev, dtype=torch.float32) if trace else None
             expo, g_si = self._torch_noise(draws, n_draw * B, l, more_smooth)
             soft = None
-            if rows is not None:
+            if forced is not None:
+                ops.cfg_sample_edit(logits, B, nrep, l, cfg.vocab, rows[3][si], rows[1], rows[2], rows[0], si, n_draw, idx, forced[:, py.begin[si]:py.end[si]],
+                                    comb, mg, ldv=cfg.head_ld)
+            elif rows is not None:
                 ops.cfg_sample_rows(logits, B, nrep, l, cfg.vocab, rows[3][si], rows[1], rows[2], rows[0], si, n_draw, idx, comb, mg, ldv=cfg.head_ld)
             elif more_smooth and top_k != 1:
                 if gumbel is not None:
@@ -1742,6 +1806,135 @@ class ControlVAR(nn.Module):
         run.ids = lambda: ids_buf.clone()                   # the given half's ids of the last replay ('pixels': what the graph's tokeniser produced)
         return run
 
+    # ---- region-constrained generation
+    def _check_edit(self, label_B, cond_type, more_smooth=False):
+        """what edit_infer_cfg / graphed_edit_generator do not offer, said on the host before any device work"""
+        self._check_per_request(label_B, cond_type, False, more_smooth)
+        if self.cfg.separator:
+            raise NotImplementedError('region-constrained generation: separator models are not offered (their scales carry special tokens between '
+                                      'the halves, which the forced-token table does not lay out)')
+
+    def _edit_table(self, B, src_ctrl, keep_ctrl, src_img, keep_img, mask_first, forced=None):
+        """device halves (flat int32 ids, uint8 masks; None where a half keeps nothing) -> forced (B, L) int32, one launch"""
+        cfg = self.cfg
+        if forced is None:
+            forced = torch.empty(B, cfg.pyramid.L, device=self.device, dtype=torch.int32)
+        return ops.edit_force_table(keep_ctrl, keep_img, src_ctrl if keep_ctrl is not None else None, src_img if keep_img is not None else None,
+                                    cfg.pyramid.patch_nums, B, mask_first, cfg.mask_factor, forced)
+
+    @torch.no_grad()
+    def edit_infer_cfg(self, B: int, label_B, cond_type, *, src_img=None, keep_img=None, src_ctrl=None, keep_ctrl=None, g_seed=None, cfg=1.5,
+                       top_k=0, top_p=0.0, trace: bool = False, more_smooth: bool = False) -> torch.Tensor:
+        """Region-constrained generation (an addition of this library): keep the source's tokens where a mask says "keep", sample the others in
+        their context - in-painting, out-painting, editing under a control map (keep_ctrl=True, the image partly kept), or a consistent joint
+        edit (the same region of both halves free).  Returns what autoregressive_infer_cfg returns.
+        src_img / src_ctrl: the half's multi-scale ids, the list of (B, pn^2) tensors vae.img_to_idxBl returns (or one (B, sum pn^2) tensor).
+        keep_img / keep_ctrl: (B, S, S) bool at latent resolution (S = patch_nums[-1]), True = keep the source; the python value True keeps the
+        whole half, None nothing.  A token of scale pn is kept iff a strict majority of the latent cells in its area-pooling bin is
+        (edit_keep_cells); at the last scale that is the mask itself.  Kept tokens carry the source id of their scale and cell and feed the
+        next scale like sampled ones; every other token is sampled exactly as the per-request joint path samples it, so with nothing kept
+        the result is autoregressive_infer_cfg's in per-request mode, bit for bit.
+        g_seed / cfg / top_k / top_p: a scalar or one value per row, as in per-request mode (a scalar seed gives identical requests
+        identical results).  label_B and cond_type are given per row.  trace=True leaves last_trace as _trace does, 'idx' holding the ids
+        AFTER forcing, plus last_trace['forced'], the table.  more_smooth, sampler='torch', the two-pass separate_decoding branch and
+        separator models are refused."""
+        self._check_edit(label_B, cond_type, more_smooth)
+        pns = self.cfg.pyramid.patch_nums
+        s_ctrl, k_ctrl = _edit_half('ctrl', src_ctrl, keep_ctrl, B, pns, self.cfg.vocab) if self.cfg.mask_factor == 2 else (None, None)
+        s_img, k_img = _edit_half('img', src_img, keep_img, B, pns, self.cfg.vocab)
+        table = _request_table(B, cfg, top_k, top_p, g_seed, False, self.cfg.vocab, len(pns))
+        self._pack(check=True); self.vae_proxy[0]._pack(check=True)
+        labels_all, types_all = self._prepare_rows(B, label_B, cond_type, False, 0)
+        mask_first = True
+        if self.cfg.mask_factor == 2:
+            import random                                 # control_var.py:403, as _generate_rows: the table below is built for the drawn order
+            mask_first = True if (random.random() < 0.5 or not self.bidirectional) else False
+        dev = self.device
+        on_dev = [None if t is None else t.to(device=dev, dtype=dt).contiguous() for t, dt in ((s_ctrl, torch.int32), (k_ctrl, torch.uint8),
+                                                                                                (s_img, torch.int32), (k_img, torch.uint8))]
+        forced = self._edit_table(B, *on_dev, mask_first)
+        rows = table.views(table.host.to(dev))
+        f_hat = self._generate_core(B, labels_all, types_all, 0, None, None, None, None, False, trace=trace, mask_first=mask_first, rows=rows, forced=forced)
+        if trace:
+            self.last_trace['forced'] = forced
+        return self._decode_pair(f_hat)
+
+    @torch.no_grad()
+    def graphed_edit_generator(self, B: int, source: str = 'ids', cfg=1.5, top_k=0, top_p=0.0, decode: str = 'both'):
+        """Capture one full `edit_infer_cfg` in a HIP graph and return
+        ``run(label_B, cond_type, *, src_img=None, keep_img=None, src_ctrl=None, keep_ctrl=None, g_seed=None, cfg=..., top_k=..., top_p=...) -> images``.
+        The keep masks (uint8, all zero = nothing kept), the sources and the request table live in static device buffers refreshed before each
+        replay; the graph holds the forced-token table's launch and the per-request scale loop with the forcing sampler.
+        source='ids': the sources are ids as edit_infer_cfg takes them.  source='pixels': they are (B, 3, 16 S, 16 S) pixels in [-1, 1] and the
+        graph also holds the tokeniser of both halves (the calls of `vae.img_to_idxBl`); ``run.ids()`` returns the (control, image) ids it produced.
+        A half whose source is not given keeps the buffer of the previous replay and a mask of zeros.
+        decode='both': what edit_infer_cfg returns; decode='generated': the image map only, (B, 3, H, H), one decoder pass of B images.
+        cfg / top_k / top_p given here are the defaults of run; each and g_seed is a scalar or per row.  Everything is validated on the host
+        before the first static buffer is written: a refused run leaves the graph as it was.  Bidirectional models are refused as
+        graphed_generator refuses them."""
+        if self.sampler == 'torch':
+            raise NotImplementedError("graphed_edit_generator captures the counter sampler only: sampler='torch' draws its noise with torch on model.rng "
+                                      "between the launches; set model.sampler = 'counter' to capture")
+        if self.bidirectional:
+            raise NotImplementedError('the captured generator fixes the (control, image) order; bidirectional models draw it per call')
+        for name, val, ok in (('source', source, ('ids', 'pixels')), ('decode', decode, ('both', 'generated'))):
+            if val not in ok:
+                raise ValueError(f'{name}={val!r}: one of {" / ".join(ok)}')
+        if int(B) != B or B < 1:
+            raise ValueError(f'B={B!r}: a positive batch size')
+        mf = self.cfg.mask_factor
+        lab0 = torch.zeros(B, dtype=torch.int64)
+        self._check_edit(lab0, lab0)
+        dev = self.device
+        vae: VQVAE = self.vae_proxy[0]
+        pns = self.cfg.pyramid.patch_nums
+        S, Lsrc, pixels = pns[-1], sum(pn * pn for pn in pns), source == 'pixels'
+        labels_all, types_all = self._prepare_rows(B, lab0, lab0 if mf == 2 else None, False, 0)
+        halves = ('ctrl', 'img') if mf == 2 else ('img',)
+        keep_buf = {h: torch.zeros(B, S, S, device=dev, dtype=torch.uint8) for h in halves}
+        ids_buf = {h: torch.zeros(B, Lsrc, device=dev, dtype=torch.int32) for h in halves}
+        pix_buf = {h: torch.zeros(B, 3, 16 * S, 16 * S, device=dev, dtype=torch.float32) for h in halves} if pixels else None
+        forced = torch.full((B, self.cfg.pyramid.L), -1, device=dev, dtype=torch.int32)
+
+        def prologue():
+            if pixels:
+                for h in halves:                            # each half as its own batch of B: the calls of img_to_idxBl
+                    ids_buf[h].copy_(vae._ms_encode(vae._encode_f(pix_buf[h]))[0])
+            self._edit_table(B, ids_buf.get('ctrl'), keep_buf.get('ctrl'), ids_buf['img'], keep_buf['img'], True, forced)
+
+        def finish(f_hat):
+            if decode == 'both':
+                return self._decode_pair(f_hat)
+            return vae._decode(f_hat[:, mf - 1].contiguous(), lo=-1.0, hi=1.0, mul=0.5, add=0.5)
+
+        def refresh(request):
+            checked = {h: _edit_half(h, request.get('src_' + h), request.get('keep_' + h), B, pns, self.cfg.vocab, pixels) for h in halves}
+
+            def copy():
+                for h, (src, mask) in checked.items():
+                    if src is not None:
+                        (pix_buf if pixels else ids_buf)[h].copy_(src)
+                    if mask is None:
+                        keep_buf[h].zero_()
+                    else:
+                        keep_buf[h].copy_(mask)
+            return copy
+
+        inner = self._capture_per_request(B, False, labels_all, types_all, cfg, top_k, top_p, finish, teach={'forced': forced}, refresh=refresh,
+                                          prologue=prologue)
+
+        if mf == 2:
+            def run(label_B, cond_type, *, src_img=None, keep_img=None, src_ctrl=None, keep_ctrl=None, g_seed=None, cfg=cfg, top_k=top_k, top_p=top_p):
+                return inner(label_B, cond_type, dict(src_img=src_img, keep_img=keep_img, src_ctrl=src_ctrl, keep_ctrl=keep_ctrl), g_seed=g_seed, cfg=cfg,
+                             top_k=top_k, top_p=top_p)
+        else:
+            def run(label_B, cond_type=None, *, src_img=None, keep_img=None, g_seed=None, cfg=cfg, top_k=top_k, top_p=top_p):
+                return inner(label_B, None, dict(src_img=src_img, keep_img=keep_img), g_seed=g_seed, cfg=cfg, top_k=top_k, top_p=top_p)
+        run.graph, run.owned = inner.graph, inner.owned
+        run.ids = lambda: tuple(ids_buf[h].clone() for h in halves)          # the sources of the last replay ('pixels': what the tokeniser produced)
+        run.forced = lambda: forced.clone()                                  # ... and its forced-token table
+        return run
+
     def _decode_pair(self, f_hat: torch.Tensor) -> torch.Tensor:
         vae: VQVAE = self.vae_proxy[0]
         B, mf = f_hat.shape[:2]
@@ -1841,6 +2034,13 @@ class VAR(ControlVAR):
         """var.py:143-207: returns (B, 3, H, H) in [0,1], H = 16 patch_nums[-1] (256, or 512 with PATCH_NUMS_512)."""
         f_hat = self._generate(B, label_B, g_seed, cfg, top_k, top_p, more_smooth, None, False, None, None, _force_idx, _trace)
         return self._decode_pair(f_hat)
+
+    @torch.no_grad()
+    def edit_infer_cfg(self, B: int, label_B, *, src_img=None, keep_img=None, g_seed=None, cfg=1.5, top_k=0, top_p=0.0, trace: bool = False,
+                       more_smooth: bool = False) -> torch.Tensor:
+        """ControlVAR.edit_infer_cfg for the one half a plain VAR has: returns (B, 3, H, H) as autoregressive_infer_cfg"""
+        return super().edit_infer_cfg(B, label_B, None, src_img=src_img, keep_img=keep_img, g_seed=g_seed, cfg=cfg, top_k=top_k, top_p=top_p, trace=trace,
+                                      more_smooth=more_smooth)
 
     def conditional_infer_cfg(self, *a, **k):
         raise NotImplementedError('plain VAR has no conditional_infer_cfg (var.py)')

@@ -271,6 +271,50 @@ def cfg_sample_rows(logits: torch.Tensor, B: int, nrep: int, l: int, V: int, coe
     return idx_out
 
 
+def cfg_sample_edit(logits: torch.Tensor, B: int, nrep: int, l: int, V: int, coef: torch.Tensor, top_k: torch.Tensor, top_p: torch.Tensor,
+                    seed: torch.Tensor, stage: int, n_draw: int, idx_out: torch.Tensor, forced: torch.Tensor, combined: Optional[torch.Tensor] = None,
+                    margin: Optional[torch.Tensor] = None, kept: Optional[torch.Tensor] = None, ldv: int = 0,
+                    expo: Optional[torch.Tensor] = None, soft_out: Optional[torch.Tensor] = None):
+    """cfg_sample_rows with per-token forcing (cvar_cfg_sample_edit, include/cvar_serve.h).  forced: (B, l) int32 on the device of `logits`,
+    unit stride along the tokens - this stage's columns of the forced-token table, a view of it will do (its row stride is handed on as ldf).
+    A token with forced >= 0 gets that id in all n_draw rows, kept = 0, margin = +inf, no combined row, and none of its logits is read; every
+    other token is what cfg_sample_rows gives, bit for bit."""
+    for name, t, dtype, shape in (('coef', coef, torch.float32, (B, 4)), ('top_k', top_k, torch.int32, (B,)), ('top_p', top_p, torch.float32, (B,)),
+                                  ('seed', seed, torch.int64, (B,))):
+        if t is not None and (not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != logits.device):
+            raise ValueError(f'cfg_sample_edit: {name} must be a contiguous {str(dtype)[6:]} {shape} tensor on {logits.device}')
+    ldf = 0
+    if forced is not None:
+        if (not torch.is_tensor(forced) or forced.dtype != torch.int32 or tuple(forced.shape) != (B, l) or forced.stride(1) != 1
+                or (B > 1 and forced.stride(0) < l) or forced.device != logits.device):
+            raise ValueError(f'cfg_sample_edit: forced must be an int32 ({B}, {l}) tensor on {logits.device} with unit stride along the tokens')
+        ldf = forced.stride(0) if B > 1 else max(forced.stride(0), l)
+    check(_lib.load().cvar_cfg_sample_edit(_ptr(logits), B, nrep, l, V, _ptr(coef), _ptr(top_k), _ptr(top_p), _ptr(seed), stage, n_draw,
+                                           _ptr(idx_out), _ptr(combined), _ptr(margin), _ptr(kept), int(ldv), _ptr(expo), _ptr(soft_out),
+                                           _ptr(forced), int(ldf), _stream()),
+          'cvar_cfg_sample_edit')
+    return idx_out
+
+
+def edit_force_table(keep_ctrl: Optional[torch.Tensor], keep_img: Optional[torch.Tensor], src_ctrl: Optional[torch.Tensor],
+                     src_img: Optional[torch.Tensor], patch_nums: Sequence[int], B: int, mask_first: bool, mask_factor: int, forced: torch.Tensor):
+    """The forced-token table of every scale in one launch (cvar_edit_force_table, include/cvar_serve.h).  keep_*: (B, S, S) uint8 or None,
+    src_*: (B, sum pn^2) int32 or None, forced: (B, mask_factor * sum pn^2) int32, all contiguous on one device; S = patch_nums[-1].
+    forced = the source id where the cell rule keeps the token (a strict majority of its area-pooling bin is kept), -1 where it is free."""
+    pns = [int(p) for p in patch_nums]
+    S, Lsrc = pns[-1], sum(p * p for p in pns)
+    for name, t, dtype, shape in (('keep_ctrl', keep_ctrl, torch.uint8, (B, S, S)), ('keep_img', keep_img, torch.uint8, (B, S, S)),
+                                  ('src_ctrl', src_ctrl, torch.int32, (B, Lsrc)), ('src_img', src_img, torch.int32, (B, Lsrc)),
+                                  ('forced', forced, torch.int32, (B, mask_factor * Lsrc))):
+        if t is not None and (not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous()
+                              or (forced is not None and t.device != forced.device)):
+            raise ValueError(f'edit_force_table: {name} must be a contiguous {str(dtype)[6:]} {shape} tensor' + (f' on {forced.device}' if forced is not None else ''))
+    arr = (C.c_int * len(pns))(*pns)
+    check(_lib.load().cvar_edit_force_table(_ptr(keep_ctrl), _ptr(keep_img), _ptr(src_ctrl), _ptr(src_img), arr, len(pns), B, S, int(bool(mask_first)),
+                                            int(mask_factor), _ptr(forced), _stream()), 'cvar_edit_force_table')
+    return forced
+
+
 def ms_next_input(idx: torch.Tensor, codebook, phi_w, phi_b, up, down, f_hat, tok_out, nb, nmaps, pn, pn_next, S, Cvae,
                   phi_k: int, up_off: int, down_off: int):
     lib = _lib.load()

@@ -394,6 +394,37 @@ _define('cfg_sample_rows', '(Tensor logits, int B, int nrep, Tensor coef, Tensor
         lambda logits, B, nrep, coef, top_k, top_p, seed, stage, n_draw=1: logits.new_empty(n_draw * B, logits.shape[1], dtype=torch.int32))
 
 
+def _cfg_sample_edit(logits, B, nrep, coef, top_k, top_p, seed, stage, forced, n_draw=1):
+    """cfg_sample_rows with per-token forcing (include/cvar_serve.h): forced (B, l) int32, this stage's columns of the forced-token table (a
+    view of it will do).  A token with forced >= 0 gets that id and none of its logits is read; every other token is cfg_sample_rows's"""
+    if logits.dtype != torch.float32 or logits.dim() != 3 or logits.shape[0] != nrep * B:
+        raise ValueError('cfg_sample_edit: logits must be float32 (nrep*B, l, V)')
+    _, l, V = logits.shape
+    idx = torch.empty(n_draw * B, l, device=logits.device, dtype=torch.int32)
+    K.cfg_sample_edit(logits.contiguous(), B, nrep, l, V, coef, top_k, top_p, seed, stage, n_draw, idx, forced)
+    return idx
+
+
+_define('cfg_sample_edit', '(Tensor logits, int B, int nrep, Tensor coef, Tensor top_k, Tensor top_p, Tensor seed, int stage, Tensor forced, int n_draw=1) -> Tensor',
+        _cfg_sample_edit,
+        lambda logits, B, nrep, coef, top_k, top_p, seed, stage, forced, n_draw=1: logits.new_empty(n_draw * B, logits.shape[1], dtype=torch.int32))
+
+
+def _edit_force_table(src_img, keep_img, src_ctrl, keep_ctrl, patch_nums, mask_first=True, mask_factor=2):
+    """keep masks (B, S, S) uint8 at latent resolution + multi-scale source ids (B, sum pn^2) int32 -> the forced-token table
+    (B, mask_factor * sum pn^2) int32 of every scale in one launch: the source id where the cell rule keeps the token, -1 where it is free"""
+    B = src_img.shape[0]
+    forced = torch.empty(B, mask_factor * sum(p * p for p in patch_nums), device=src_img.device, dtype=torch.int32)
+    return K.edit_force_table(keep_ctrl, keep_img, src_ctrl if keep_ctrl is not None else None, src_img if keep_img is not None else None,
+                              list(patch_nums), B, mask_first, mask_factor, forced)
+
+
+_define('edit_force_table', '(Tensor src_img, Tensor? keep_img, Tensor? src_ctrl, Tensor? keep_ctrl, int[] patch_nums, bool mask_first=True, int mask_factor=2) -> Tensor',
+        _edit_force_table,
+        lambda src_img, keep_img, src_ctrl, keep_ctrl, patch_nums, mask_first=True, mask_factor=2:
+        src_img.new_empty(src_img.shape[0], mask_factor * sum(p * p for p in patch_nums), dtype=torch.int32))
+
+
 # ------------------------------------------------------------------------------------------------------------------- quantizer pyramid
 def _ms_encode(f, codebook, phi_w, phi_b, phi_map, patch_nums, up, down):
     """f (B, Cvae, S, S) fp32 -> (ids (B, sum pn^2) int32, f_hat (B, Cvae, S, S))   (quant.py:184-215)"""

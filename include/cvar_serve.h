@@ -2,7 +2,8 @@
  * no allocation, asynchronous, negative `cvar_status` on error.
  *
  * The functions live in the same libcvar_hip.so as those of cvar.h.  They are versioned on their own: cvar_serve_version() bumps on
- * any signature change in THIS header, cvar_abi_version() stays the version of cvar.h.
+ * any signature change in THIS header, cvar_abi_version() stays the version of cvar.h.  Adding an entry point changes no signature and
+ * leaves the version alone: cvar_edit_force_table and cvar_cfg_sample_edit joined at version 1.
  */
 #ifndef CVAR_SERVE_H
 #define CVAR_SERVE_H
@@ -38,6 +39,35 @@ int cvar_cfg_sample_rows(const float* logits, int B, int nrep, int l, int V,
                          const float* coef /* [B][4] */, const int32_t* top_k /* [B] */, const float* top_p /* [B] */, const int64_t* seed /* [B] */,
                          int stage, int n_draw, int32_t* idx_out, float* combined, float* margin, int32_t* kept, int ldv,
                          const float* expo /* must be NULL */, float* soft_out /* must be NULL */, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Region-constrained generation: keep the source's tokens where a latent-resolution mask says "keep", sample the others.
+ *
+ * cvar_edit_force_table: one launch turns the keep masks of a batch into the forced-token table of every scale.
+ *   keep_ctrl / keep_img [B][S][S] uint8 (non-zero = keep the source there), each may be NULL (nothing of that half is kept);
+ *   src_ctrl / src_img   [B][sum pn^2] int32, the half's multi-scale ids, scale after scale (required where the half's mask is given);
+ *   patch_nums           HOST array of the nstage scale sizes (1 <= pn <= S, the last one == S; nstage 1..16);
+ *   forced               [B][L] int32, L = sum mask_factor * pn^2, in the token order of generation: per scale the two halves, control first
+ *                        when mask_first != 0 and image first otherwise (mask_factor == 1: the image half only; keep_ctrl must be NULL).
+ * Cell (i, j) of scale pn covers the latent rows floor(i S / pn) .. ceil((i + 1) S / pn) - 1 and the same columns - the bins of area
+ * interpolation, with which the quantizer forms that token.  The cell is kept iff 2 * (kept latent cells in the bin) > bin size: a strict
+ * majority in integers, an exact half stays free; at the last scale the rule is the mask itself.
+ * forced = the source id of that scale and cell where kept, -1 where free.  The ids are copied, not checked. */
+int cvar_edit_force_table(const uint8_t* keep_ctrl, const uint8_t* keep_img, const int32_t* src_ctrl, const int32_t* src_img,
+                          const int* patch_nums /* host, [nstage] */, int nstage, int B, int S, int mask_first, int mask_factor,
+                          int32_t* forced /* [B][L] */, void* stream);
+
+/* cvar_cfg_sample_edit: cvar_cfg_sample_rows with per-token forcing.  forced points at THIS stage's slice of the table, row stride ldf
+ * (>= l): token (b, t) reads forced[b * ldf + t].
+ *   >= 0: that id goes to all n_draw rows of idx_out, kept = 0, margin = +inf, its combined row is NOT written, and no logit of the token
+ *         is read (they may hold anything, NaN included);
+ *   <  0: the token is what cvar_cfg_sample_rows gives on the same inputs - idx_out, combined, margin and kept, bit for bit.
+ * forced == NULL or ldf < l is CVAR_EINVAL; every other argument is checked as cvar_cfg_sample_rows checks it. */
+int cvar_cfg_sample_edit(const float* logits, int B, int nrep, int l, int V,
+                         const float* coef /* [B][4] */, const int32_t* top_k /* [B] */, const float* top_p /* [B] */, const int64_t* seed /* [B] */,
+                         int stage, int n_draw, int32_t* idx_out, float* combined, float* margin, int32_t* kept, int ldv,
+                         const float* expo /* must be NULL */, float* soft_out /* must be NULL */,
+                         const int32_t* forced, int ldf, void* stream);
 
 #ifdef __cplusplus
 }
