@@ -120,6 +120,8 @@ SERVE_SIGNATURES = {
     # region-constrained generation: joined at version 1 (an added entry point changes no signature)
     'cvar_edit_force_table': (c_i, [c_p, c_p, c_p, c_p, C.POINTER(c_i), c_i, c_i, c_i, c_i, c_i, c_p, c_p]),
     'cvar_cfg_sample_edit': (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_p]),
+    # per-request LoRA adapters: joined at version 1
+    'cvar_lora_down_rows': (c_i, [c_p, c_l, c_p, c_l, c_p, c_p, c_i, c_i, c_i, c_p, c_l, c_i, c_p, c_l, c_i, c_i, c_p]),
 }
 
 _lib = None

@@ -7,8 +7,11 @@
 //   cvar_lora_dx     dx = (dx + s * drop'(du A)) * gelu'(aux)      (in place after the base data-gradient GEMM)
 //   cvar_lora_wgrad  G[n, j] = s * sum_m drop(Y)[m, n] Z[m, j]    (dB = dY^T u, dA = s du^T drop(x)), split-M fp32 partials +
 //                    a fixed-order finish: no float atomics, bit-identical on every run
+//   cvar_lora_down_rows  the per-row form of cvar_lora_down for inference (include/cvar_serve.h): every sequence of a batch picks its own
+//                    adapter of a bank, no dropout; the other slots' columns of the K-augmented operand are written as zeros
 // The dropout keep mask of (seed, tag, row, column) is a counter-based hash: forward and backward regenerate it, nothing is stored.
 #include "cvar_common.h"
+#include "../../include/cvar_serve.h"
 
 #define LORA_R 16           // rank held in registers; r < 16 leaves the upper accumulators unused
 
@@ -90,13 +93,13 @@ template <> struct Raw8<float> {
 // block = 4 waves x ROWS rows; per 512-column slab the block stages A[0:r][slab] in LDS once (instead of every wave reading it from
 // L2 per row group), lane owns 8 columns of the slab and accumulates ROWS x 16 partial dot products, which one transposing butterfly
 // (63 shuffles for 64 values) reduces so that lane l ends with (row l / 16, rank column l % 16)
+// The body is shared by lora_down_kernel and lora_down_rows_kernel (one text, so a row of either is the same sum): the wave's rows are
+// m0 .. m0 + ROWS - 1, those at or past m_end are skipped; returns the lane's reduced value, unscaled
 template <typename T, int ROWS>
-__global__ __launch_bounds__(256) void lora_down_kernel(const T* __restrict__ x, long ldx, const T* __restrict__ A, long lda, T* __restrict__ u,
-                                                        long ldu, T* __restrict__ xc, long ldxc, int M, int K, int r, float scale, LoraMask mk) {
+__device__ __forceinline__ float lora_down_body(const T* __restrict__ x, long ldx, const T* __restrict__ A, long lda, T* __restrict__ xc, long ldxc,
+                                                T (*As)[512], const long m0, const long M, int K, int r, const LoraMask& mk) {
     static_assert(ROWS * LORA_R == 64, "one reduced value per lane");
-    __shared__ __attribute__((aligned(16))) T As[LORA_R][512];
     const int lane = threadIdx.x & 63;
-    const long m0 = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * ROWS;        // no early exit: every wave joins the slab barriers
     float acc[ROWS * LORA_R];
 #pragma unroll
     for (int i = 0; i < ROWS * LORA_R; ++i) acc[i] = 0.f;
@@ -160,9 +163,55 @@ __global__ __launch_bounds__(256) void lora_down_kernel(const T* __restrict__ x,
             acc[i] = keep + __shfl_xor(send, w, 64);
         }
     }
+    return acc[0];
+}
+
+template <typename T, int ROWS>
+__global__ __launch_bounds__(256) void lora_down_kernel(const T* __restrict__ x, long ldx, const T* __restrict__ A, long lda, T* __restrict__ u,
+                                                        long ldu, T* __restrict__ xc, long ldxc, int M, int K, int r, float scale, LoraMask mk) {
+    __shared__ __attribute__((aligned(16))) T As[LORA_R][512];
+    const int lane = threadIdx.x & 63;
+    const long m0 = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * ROWS;        // no early exit: every wave joins the slab barriers
+    const float v = lora_down_body<T, ROWS>(x, ldx, A, lda, xc, ldxc, As, m0, (long)M, K, r, mk);
     const long m = m0 + lane / LORA_R;
     const int j = lane % LORA_R;
-    if (m < M && j < r) Elem<T>::st(u + m * ldu + j, scale * acc[0]);
+    if (m < M && j < r) Elem<T>::st(u + m * ldu + j, scale * v);
+}
+
+// ---- per-row adapters (inference; include/cvar_serve.h) -------------------------------------------------------------------
+// block = (sequence, 16-row chunk of its l rows): the slot is block-uniform and read once, ahead of everything else, so a block never
+// stages an A slab for rows of another adapter.  The reduction is lora_down_body with r = 16 and no dropout; the wave then writes its
+// rows' kpad columns behind K: the slot's 16 values, zeros in every other 8-column group.  A slot < 0 block copies and zero-fills
+// without touching the bank.
+template <typename T>
+__global__ __launch_bounds__(256) void lora_down_rows_kernel(const T* __restrict__ x, long ldx, const T* __restrict__ bank, long lda,
+                                                             const float* __restrict__ scale, const int* __restrict__ slot, int l, int chunks,
+                                                             T* __restrict__ xa, long ldxa, int kpad, T* __restrict__ xc, long ldxc, int K) {
+    __shared__ __attribute__((aligned(16))) T As[LORA_R][512];
+    const int seq = blockIdx.x / chunks;
+    const int s = slot[seq];
+    const int lane = threadIdx.x & 63;
+    const long m_end = ((long)seq + 1) * l;
+    const long m0 = (long)seq * l + ((long)(blockIdx.x % chunks) * 4 + (threadIdx.x >> 6)) * 4;
+    if (s >= 0) {
+        LoraMask mk;
+        mk.key = 0; mk.thresh = 0; mk.inv_keep = 1.f; mk.on = 0;
+        const float v = lora_down_body<T, 4>(x, ldx, bank + (long)s * LORA_R * lda, lda, xc, ldxc, As, m0, m_end, K, LORA_R, mk);
+        const long m = m0 + lane / LORA_R;
+        if (m < m_end) Elem<T>::st(xa + m * ldxa + K + s * LORA_R + lane % LORA_R, scale[s] * v);
+    } else if (xc) {
+        for (int rr = 0; rr < 4; ++rr)
+            if (m0 + rr < m_end)
+                for (int k0 = lane * 8; k0 < K; k0 += 512) copy8(x + (m0 + rr) * ldx + k0, xc + (m0 + rr) * ldxc + k0);
+    }
+    const int g8 = kpad >> 3;                               // 8-column groups per row; groups 2 s and 2 s + 1 hold the slot's values
+    float z[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) z[e] = 0.f;
+    for (int c = lane; c < 4 * g8; c += 64) {
+        const int rr = c / g8, g = c % g8;
+        if (m0 + rr < m_end && (s < 0 || (g >> 1) != s)) st8(xa + (m0 + rr) * ldxa + K + g * 8, z);
+    }
 }
 
 // ---- data gradient of the adapter branch (in place) ----------------------------------------------------------------------
@@ -348,6 +397,27 @@ extern "C" int cvar_lora_down(const void* x, int64_t ldx, const void* A, int64_t
     else if (dtype == CVAR_F32)
         hipLaunchKernelGGL((lora_down_kernel<float, 4>), grid, block, 0, as_stream(stream), (const float*)x, (long)ldx, (const float*)A, (long)lda,
                            (float*)u, (long)ldu, (float*)x_copy, (long)ld_copy, M, K, r, scale, mk);
+    else return CVAR_EUNSUPPORTED;
+    CVAR_CHECK_LAUNCH();
+    return CVAR_OK;
+}
+
+extern "C" int cvar_lora_down_rows(const void* x, int64_t ldx, const void* A_bank, int64_t lda, const float* scale, const int32_t* slot, int n_slots,
+                                   int R, int l, void* xa, int64_t ldxa, int kpad, void* x_copy, int64_t ld_copy, int K, int dtype, void* stream) {
+    if (!x || !A_bank || !scale || !slot || !xa || R <= 0 || l < 1 || K <= 0 || n_slots < 1 || n_slots > 8) return CVAR_EINVAL;
+    if (kpad % 16 || kpad < 16 * n_slots) return CVAR_EINVAL;
+    if (K % 8 || ldx % 8 || lda % 8 || ldxa % 8 || ldx < K || lda < K || ldxa < (int64_t)K + kpad || !al16(x) || !al16(A_bank) || !al16(xa))
+        return CVAR_EUNSUPPORTED;
+    if (x_copy && (ld_copy % 8 || ld_copy < K || !al16(x_copy))) return CVAR_EUNSUPPORTED;
+    const int chunks = cdiv(l, 16);
+    if ((int64_t)R * l > 0x7fffffff || (int64_t)R * chunks > 0x7fffffff) return CVAR_EUNSUPPORTED;
+    const dim3 grid(R * chunks), block(256);
+    if (dtype == CVAR_BF16)
+        hipLaunchKernelGGL((lora_down_rows_kernel<bf16_t>), grid, block, 0, as_stream(stream), (const bf16_t*)x, (long)ldx, (const bf16_t*)A_bank, (long)lda,
+                           scale, (const int*)slot, l, chunks, (bf16_t*)xa, (long)ldxa, kpad, (bf16_t*)x_copy, (long)ld_copy, K);
+    else if (dtype == CVAR_F32)
+        hipLaunchKernelGGL((lora_down_rows_kernel<float>), grid, block, 0, as_stream(stream), (const float*)x, (long)ldx, (const float*)A_bank, (long)lda,
+                           scale, (const int*)slot, l, chunks, (float*)xa, (long)ldxa, kpad, (float*)x_copy, (long)ld_copy, K);
     else return CVAR_EUNSUPPORTED;
     CVAR_CHECK_LAUNCH();
     return CVAR_OK;

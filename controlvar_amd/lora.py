@@ -8,6 +8,9 @@ rank-r branch through the HIP kernels of csrc/lora.hip (DESIGN.md "LoRA").  A ta
 
 Only A and B train; every other parameter is frozen.  In eval() the adapters are merged into the packed GEMM weights, so inference
 runs exactly the adapter-free kernels.
+
+attach_adapters (an addition of this library) is the serving form: a bank of up to 8 adapters beside the unchanged base
+weights, one of which every request of a generation batch picks with ``adapter=``.
 """
 from __future__ import annotations
 
@@ -61,6 +64,8 @@ def add_lora(model, r: int = 16, alpha: float = 32, dropout: float = 0.05, seed:
     _check_supported(model)
     if has_lora(model):
         raise RuntimeError('the model already has LoRA adapters (one adapter per model)')
+    if getattr(model, '_adapter_bank', None) is not None:
+        raise RuntimeError('the model has an adapter bank (attach_adapters): a bank and add_lora on one model are mutually exclusive (detach_adapters first)')
     if not 1 <= r <= MAX_RANK:
         raise NotImplementedError(f'LoRA rank {r}: the GPU kernels take 1 <= r <= {MAX_RANK}')
     if not 0.0 <= dropout < 1.0:
@@ -199,6 +204,151 @@ def load_lora(model, src) -> None:
         _invalidate(model)
     else:
         model.load_state_dict(sd, strict=True)
+
+
+# ---- adapter bank: several adapters on one model, chosen per request (an addition of this library) ---------------------
+MAX_ADAPTERS = 8                        # slots of one bank (cvar_lora_down_rows: n_slots 1..8)
+BANK_KINDS = (('proj', 'attn.proj'), ('fc1', 'ffn.fc1'), ('fc2', 'ffn.fc2'))
+
+
+def has_adapters(model) -> bool:
+    return getattr(model, '_adapter_bank', None) is not None
+
+
+def _adapter_tensors(src, targets) -> "OrderedDict[str, Tuple[torch.Tensor, torch.Tensor]]":
+    """one adapter state (a path or a mapping in any layout load_lora reads) -> target name -> (A (r, in), B (out, r)) in fp32 on the host;
+    the base weights of a whole-model layout are not read"""
+    obj = torch.load(os.fspath(src), map_location='cpu') if isinstance(src, (str, os.PathLike)) else src
+    if 'model_state_dict' in obj:
+        obj = obj['model_state_dict']
+    sd = {k: v for k, v in to_module_layout(obj).items() if '.lora_' in k}
+    want = {f'{t}.lora_{ab}.{ADAPTER}.weight' for t in targets for ab in 'AB'}
+    if set(sd) != want:
+        raise KeyError(f'adapter state: missing {sorted(want - set(sd))[:4]}, unexpected {sorted(set(sd) - want)[:4]}')
+    return OrderedDict((t, (sd[f'{t}.lora_A.{ADAPTER}.weight'].detach().float().cpu(), sd[f'{t}.lora_B.{ADAPTER}.weight'].detach().float().cpu()))
+                       for t in targets)
+
+
+def attach_adapters(model, sources, alpha=32) -> List[str]:
+    """Attach a bank of 1..8 LoRA adapters to an adapter-free model, for generation with ``adapter=`` (one adapter id per request of a
+    batch; -1 = the base model).  sources: adapter states, each a path or mapping in a layout load_lora reads; their ranks may differ
+    (1..16).  alpha: one value or one per adapter; scale = alpha / r.  The bank is no set of parameters: state_dict() is unchanged, and
+    calls without ``adapter=`` run exactly the adapter-free launches.  Returns the target names."""
+    _check_supported(model)
+    if has_lora(model):
+        raise RuntimeError('the model has add_lora adapters: a bank and add_lora on one model are mutually exclusive (merge_lora first)')
+    sources = list(sources)
+    if not 1 <= len(sources) <= MAX_ADAPTERS:
+        raise NotImplementedError(f'{len(sources)} adapters: a bank holds 1 .. {MAX_ADAPTERS}')
+    alphas = [float(alpha)] * len(sources) if isinstance(alpha, (int, float)) else [float(a) for a in alpha]
+    if len(alphas) != len(sources):
+        raise ValueError(f'alpha: one value or {len(sources)} values (one per adapter) expected, got {len(alphas)}')
+    names = target_names(model)
+    mods = dict(model.named_modules())
+    adapters_, ranks = [], []
+    for k, src in enumerate(sources):
+        ad = _adapter_tensors(src, names)
+        r = int(next(iter(ad.values()))[0].shape[0])
+        if not 1 <= r <= MAX_RANK:
+            raise NotImplementedError(f'LoRA rank {r}: the GPU kernels take 1 <= r <= {MAX_RANK}')
+        for t, (A, B) in ad.items():
+            out_f, in_f = mods[t]._parameters['weight'].shape
+            for ab, v, want in (('A', A, (r, in_f)), ('B', B, (out_f, r))):
+                if tuple(v.shape) != want:
+                    raise ValueError(f'{t}.lora_{ab}.{ADAPTER}.weight: shape {tuple(v.shape)} != {want}')
+        adapters_.append(ad)
+        ranks.append(r)
+    model._adapter_bank = dict(n=len(sources), ranks=ranks, alphas=alphas, scales=[a / r for a, r in zip(alphas, ranks)], targets=list(names),
+                               adapters=adapters_, pack=None)
+    return names
+
+
+def detach_adapters(model):
+    if not has_adapters(model):
+        raise RuntimeError('the model has no adapter bank')
+    model._adapter_bank = None
+    return model
+
+
+def bank_kx(n: int, dtype: torch.dtype, groups: int = 1) -> int:
+    """columns behind K of an augmented operand: 16 per (slot, group), rounded up to the 128-byte step of train.py (rp)"""
+    rp = 128 // torch.tensor([], dtype=dtype).element_size()
+    return -(-16 * n * groups // rp) * rp
+
+
+def pack_bank(bank, P: Mapping[str, Any], C: int, depth: int, dtype: torch.dtype) -> Dict[str, Any]:
+    """The device operands of a bank over the packed base weights P (w_proj / w_fc1 / w_fc2 (depth, out, in), w_ada (n_ada, C)), in `dtype`:
+       A[kind]   (depth, n, 16, k_in), kind 'ada': (depth + 1, n, 16, C) - rows >= the adapter's rank are zero;
+       W[kind]   (depth, out, k_in + kx) = [W | B_0 | ... | B_{n-1} | 0], adapter k in columns k_in + 16 k .. + r_k;
+       W['ada']  (n_ada, C + kx_ada) = [W_ada | blockdiag]: target t (block t, then head_nm), slot k in columns C + 16 (t n + k), rows of target t;
+       scale     (n,) fp32 = alpha / r."""
+    n, dev = bank['n'], P['w_proj'].device
+    kx, kxa = bank_kx(n, dtype), bank_kx(n, dtype, depth + 1)
+    A, W = {}, {}
+    for kind, name in BANK_KINDS:
+        w = P['w_' + kind]
+        _, n_out, k_in = w.shape
+        A[kind] = torch.zeros(depth, n, 16, k_in, device=dev, dtype=dtype)
+        W[kind] = torch.zeros(depth, n_out, k_in + kx, device=dev, dtype=dtype)
+        W[kind][:, :, :k_in] = w
+        for k, (ad, r) in enumerate(zip(bank['adapters'], bank['ranks'])):
+            for i in range(depth):
+                a, b = ad[f'blocks.{i}.{name}']
+                A[kind][i, k, :r] = a.to(device=dev, dtype=dtype)
+                W[kind][i, :, k_in + 16 * k:k_in + 16 * k + r] = b.to(device=dev, dtype=dtype)
+    tn = [f'blocks.{t}.ada_lin.1' for t in range(depth)] + ['head_nm.ada_lin.1']
+    n_ada = P['w_ada'].shape[0]
+    A['ada'] = torch.zeros(depth + 1, n, 16, C, device=dev, dtype=dtype)
+    W['ada'] = torch.zeros(n_ada, C + kxa, device=dev, dtype=dtype)
+    W['ada'][:, :C] = P['w_ada']
+    for k, (ad, r) in enumerate(zip(bank['adapters'], bank['ranks'])):
+        for t, name in enumerate(tn):
+            a, b = ad[name]
+            A['ada'][t, k, :r] = a.to(device=dev, dtype=dtype)
+            c0 = C + 16 * (t * n + k)
+            W['ada'][t * 6 * C:t * 6 * C + b.shape[0], c0:c0 + r] = b.to(device=dev, dtype=dtype)
+    return dict(n=n, kx=kx, kxa=kxa, A=A, W=W, scale=torch.tensor(bank['scales'], dtype=torch.float32, device=dev))
+
+
+def bank_pack(model) -> Dict[str, Any]:
+    """pack_bank of the model's bank, built once per base pack"""
+    bank = model._adapter_bank
+    P = model._pack()
+    if bank['pack'] is None or bank['pack'][0] is not P:
+        bank['pack'] = (P, pack_bank(bank, P, model.cfg.C, model.cfg.depth, model.compute_dtype))
+    return bank['pack'][1]
+
+
+def adapter_ids(adapter, B: int, n: int):
+    """``adapter=`` of a generation call -> (B,) int32 numpy array: one int (broadcast) or a length-B sequence / tensor of ints in [-1, n)"""
+    import numpy as np
+    a = adapter.detach().cpu().numpy() if torch.is_tensor(adapter) else np.asarray(adapter)
+    if a.dtype == object or a.dtype.kind not in 'iu':
+        raise ValueError(f'adapter: integers expected, got {a.dtype}')
+    if a.ndim == 0:
+        a = np.broadcast_to(a, (B,))
+    if a.shape != (B,):
+        raise ValueError(f'adapter: one integer or shape ({B},) (one per batch row) expected, got {a.shape}')
+    if (a < -1).any() or (a >= n).any():
+        raise ValueError(f'adapter: id out of range - {n} adapter(s) attached, ids -1 (the base model) .. {n - 1} expected, got {sorted(set(a.tolist()))}')
+    return np.ascontiguousarray(a.astype(np.int32))
+
+
+def sequence_slots(ids, nrep: int):
+    """request ids (B,) -> the slot of every sequence of the batch (nrep * B,): the CFG rows are laid out branch-major ([cond ; uncond],
+    row = branch * B + b), and every branch of a request uses the request's adapter"""
+    import numpy as np
+    return np.tile(np.asarray(ids, dtype=np.int32), nrep)
+
+
+def merged_adapter_state(sd: Mapping[str, torch.Tensor], bank, k: int) -> Dict[str, torch.Tensor]:
+    """state dict of the base model with adapter k of the bank folded in (W + s B A in fp32): what merge_lora gives for that adapter alone"""
+    out = dict(sd)
+    s = bank['scales'][k]
+    for t, (A, B) in bank['adapters'][k].items():
+        W = sd[f'{t}.weight']
+        out[f'{t}.weight'] = (W.float() + s * (B.to(W.device) @ A.to(W.device))).to(W.dtype)
+    return out
 
 
 def trainable_parameters(model) -> Tuple[int, int]:

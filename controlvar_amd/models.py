@@ -759,31 +759,37 @@ def _per_request(cfg, top_k, top_p, g_seed, four_way: bool) -> bool:
 
 class _RequestTable:
     """The per-row sampling parameters of one batch in ONE contiguous host buffer - seeds int64 [B] | top_k int32 [B] | top_p fp32 [B] |
-    combine weights fp32 [nstage][B][4] - so that one host-to-device copy refreshes all of them (before a graph replay)."""
+    combine weights fp32 [nstage][B][4] - so that one host-to-device copy refreshes all of them (before a graph replay).
+    n_seq > 0 (per-request adapters): the adapter slot of every sequence, int32 [n_seq], rides behind them in the same buffer."""
 
-    def __init__(self, B: int, nstage: int):
-        self.B, self.nstage = B, nstage
-        self.host = torch.zeros(self.nbytes(B, nstage), dtype=torch.uint8)
+    def __init__(self, B: int, nstage: int, n_seq: int = 0):
+        self.B, self.nstage, self.n_seq = B, nstage, n_seq
+        self.host = torch.zeros(self.nbytes(B, nstage) + 4 * n_seq, dtype=torch.uint8)
         self.seed, self.top_k, self.top_p, self.coef = self.views(self.host)
+        self.slot = self.slot_view(self.host)
 
     @staticmethod
     def nbytes(B: int, nstage: int) -> int:
         return 8 * B + 4 * B + 4 * B + 16 * nstage * B
 
+    def slot_view(self, buf: torch.Tensor):
+        """(n_seq,) int32 view of the adapter slots in `buf` (None without them)"""
+        return buf[self.nbytes(self.B, self.nstage):].view(torch.int32) if self.n_seq else None
+
     def views(self, buf: torch.Tensor):
         """(seed (B,) int64, top_k (B,) int32, top_p (B,) fp32, coef (nstage, B, 4) fp32) views of `buf`, the host buffer or a device copy of it"""
         B = self.B
         return (buf[:8 * B].view(torch.int64), buf[8 * B:12 * B].view(torch.int32), buf[12 * B:16 * B].view(torch.float32),
-                buf[16 * B:].view(torch.float32).view(self.nstage, B, 4))
+                buf[16 * B:self.nbytes(B, self.nstage)].view(torch.float32).view(self.nstage, B, 4))
 
 
-def _request_table(B: int, cfg, top_k, top_p, g_seed, four_way: bool, vocab: int, nstage: int) -> _RequestTable:
+def _request_table(B: int, cfg, top_k, top_p, g_seed, four_way: bool, vocab: int, nstage: int, slots=None) -> _RequestTable:
     """Normalise per-request sampling parameters.  cfg / top_k / top_p / g_seed: each a scalar (broadcast to the B rows) or a length-B
     sequence, numpy array or tensor (a device tensor is read back, which synchronises); the four-branch cfg is one triple or (B, 3).
     g_seed=None draws one host seed per row, as the scalar path draws its one; seeds are taken modulo 2^64.  The combine weights of every
     stage come from the very expressions of _generate_core, in python doubles, rounded to fp32 once: bit-identical to what the scalar
     call hands to cvar_cfg_sample.  Raises before anything is written anywhere: ValueError on a wrong length or shape, RuntimeError on
-    top_k > vocabulary (as the scalar call)."""
+    top_k > vocabulary (as the scalar call).  slots (per-request adapters): the validated slot of every sequence (lora.sequence_slots)."""
     def rows(name, v, width=None):
         a = _host_array(v)
         if a.dtype == object or a.dtype.kind not in 'iuf':
@@ -815,7 +821,9 @@ def _request_table(B: int, cfg, top_k, top_p, g_seed, four_way: bool, vocab: int
         if len(seeds) != B or not all(isinstance(s, (int, np.integer)) and not isinstance(s, bool) for s in seeds):
             raise ValueError(f'g_seed: one integer or {B} integers (one per batch row) expected')
         seeds = [int(s) for s in seeds]
-    tab = _RequestTable(B, nstage)
+    tab = _RequestTable(B, nstage, 0 if slots is None else len(slots))
+    if slots is not None:
+        tab.slot.copy_(torch.from_numpy(np.ascontiguousarray(slots, dtype=np.int32)))
     tab.seed.copy_(torch.from_numpy(np.array([s & (2 ** 64 - 1) for s in seeds], dtype=np.uint64).view(np.int64)))
     tab.top_k.copy_(torch.from_numpy(np.maximum(k_r, -1).astype(np.int32)))          # <= 0: no filter (every negative value means the same)
     tab.top_p.copy_(torch.from_numpy(np.ascontiguousarray(p_r)))
@@ -1221,8 +1229,11 @@ class ControlVAR(nn.Module):
         return ent[1]
 
     # ---- one pass of all blocks + head over l new tokens per sequence
-    def _blocks_and_head(self, x, ada, R: int, l: int, q_off: int, Lmax: int, arena, lvl_end=None, holes=None):
-        """x: (R*l, C) fp32 residual stream (updated in place).  Returns logits (R*l, V) fp32."""
+    def _blocks_and_head(self, x, ada, R: int, l: int, q_off: int, Lmax: int, arena, lvl_end=None, holes=None, ad=None):
+        """x: (R*l, C) fp32 residual stream (updated in place).  Returns logits (R*l, V) fp32.
+        ad (per-request adapters): (lora.bank_pack, slot (R,) int32 on the device).  proj / fc1 / fc2 then run over the K-augmented weights
+        [W | B_0 .. B_{n-1} | 0] with an operand that ops.lora_down_rows widened by each row's own s x A^T; without it the launches are
+        exactly the adapter-free ones."""
         P, cfg = self._pack(), self.cfg
         C, H, T = cfg.C, cfg.H, self.compute_dtype
         M = R * l
@@ -1231,7 +1242,16 @@ class ControlVAR(nn.Module):
         dev = x.device
         u = torch.empty(M, C, device=dev, dtype=T)
         o = torch.empty(M, C, device=dev, dtype=T)
-        hbuf = torch.empty(M, hid, device=dev, dtype=T)
+        kx = 0 if ad is None else ad[0]['kx']
+        kc, kh = C + kx, hid + kx                                     # K = lda = ldw of proj / fc1 and of fc2: wider by the bank's columns
+        if ad is None:
+            oa, ua, w_proj, w_fc1, w_fc2 = o, u, P['w_proj'], P['w_fc1'], P['w_fc2']
+        else:
+            BK, slot = ad
+            oa = torch.empty(M, kc, device=dev, dtype=T)              # [o | u_proj of the row's slot, zeros elsewhere]
+            ua = torch.empty(M, kc, device=dev, dtype=T)              # [adaLN output | u_fc1]
+            w_proj, w_fc1, w_fc2 = BK['W']['proj'], BK['W']['fc1'], BK['W']['fc2']
+        hbuf = torch.empty(M, kh, device=dev, dtype=T)                # adapters: [gelu | u_fc2], fc1 writes it through ldc
         qs = torch.empty(M, C, device=dev, dtype=T)                 # queries of this pass: (R, l, C)
         arena_stride = R * Lmax * 2 * C
         # bf16 mode: the queries carry softmax scale * log2(e) from the producing epilogue (one rounding of q * c; the attention kernel then
@@ -1255,15 +1275,21 @@ class ControlVAR(nn.Module):
                 ops.cos_qk_norm(arena, R, H, Lmax, q_off, l, P['scale_mul'], qkv_off=i * arena_stride, sm_off=i * H, q=qs, q_mul=LOG2E if pre else 1.0)
             ops.attention(arena, o, R, H, Lmax, q_off, l, float(cfg.attn_scale), lvl_end, qkv_off=i * arena_stride, holes=holes, q=qs, prescaled=pre)
             ln2 = (u, ada, a0 + 3 * C, a0 + 5 * C, n_ada, l, cfg.norm_eps)
-            ops.gemm(o, P['w_proj'], x, M=M, N=C, K=C, w_off=i * C * C, bias=P['b_proj'][i], gate=ada, gate_off=a0, ldg=n_ada, gate_rows=l,
+            if ad is not None:
+                ops.lora_down_rows(o, BK['A']['proj'][i], BK['scale'], slot, oa, R=R, l=l, K=C, kpad=kx, ldxa=kc, x_copy=oa, ld_copy=kc)
+            ops.gemm(oa, w_proj, x, M=M, N=C, K=kc, w_off=i * C * kc, bias=P['b_proj'][i], gate=ada, gate_off=a0, ldg=n_ada, gate_rows=l,
                      residual=x, ln=ln2 if fuse_ln else None, small_m=sm, split_k=sm)
             if not fuse_ln:
                 ops.ln_modulate(x, *ln2[1:6], u, M, C, cfg.norm_eps)
-            ops.gemm(u, P['w_fc1'], hbuf, M=M, N=hid, K=C, w_off=i * hid * C, bias=P['b_fc1'][i], act=ACT_GELU_TANH, small_m=sm, split_k=sm)
+            if ad is not None:
+                ops.lora_down_rows(u, BK['A']['fc1'][i], BK['scale'], slot, ua, R=R, l=l, K=C, kpad=kx, ldxa=kc, x_copy=ua, ld_copy=kc)
+            ops.gemm(ua, w_fc1, hbuf, M=M, N=hid, K=kc, ldc=kh, w_off=i * hid * kc, bias=P['b_fc1'][i], act=ACT_GELU_TANH, small_m=sm, split_k=sm)
+            if ad is not None:                             # fc1 wrote the wide buffer itself: no copy
+                ops.lora_down_rows(hbuf, BK['A']['fc2'][i], BK['scale'], slot, hbuf, R=R, l=l, K=hid, kpad=kx, ldx=kh, ldxa=kh)
             # the row finished by fc2 is the input of the next block's first adaLN (or of the head's)
             a1 = a0 + 6 * C
             ln1 = (u, ada, a1 + 2 * C, a1 + 4 * C, n_ada, l, cfg.norm_eps) if i + 1 < cfg.depth else (u, ada, ah, ah + C, n_ada, l, cfg.norm_eps)
-            ops.gemm(hbuf, P['w_fc2'], x, M=M, N=C, K=hid, w_off=i * C * hid, bias=P['b_fc2'][i], gate=ada, gate_off=a0 + C, ldg=n_ada,
+            ops.gemm(hbuf, w_fc2, x, M=M, N=C, K=kh, w_off=i * C * kh, bias=P['b_fc2'][i], gate=ada, gate_off=a0 + C, ldg=n_ada,
                      gate_rows=l, residual=x, ln=ln1 if fuse_ln else None, small_m=sm, split_k=sm)
             if not fuse_ln:
                 ops.ln_modulate(x, *ln1[1:6], u, M, C, cfg.norm_eps)
@@ -1271,12 +1297,24 @@ class ControlVAR(nn.Module):
         ops.gemm(u, P['w_head'], logits, M=M, N=cfg.head_ld, K=C, bias=P['b_head'], small_m=sm, split_k=sm)
         return logits
 
-    def _ada(self, cond: torch.Tensor, R: int):
+    def _ada(self, cond: torch.Tensor, R: int, ad=None):
         P = self._pack()
         cs = torch.empty(R, self.cfg.C, device=cond.device, dtype=self.compute_dtype)
         ops.silu_cast(cond, cs)
         ada = torch.empty(R, P['n_ada'], device=cond.device, dtype=torch.float32)
         sm = not self.deterministic_plan
+        if ad is not None:
+            # per-request adapters: the operand [cs | one 16-column group per (ada target, slot)] is widened once per generation - one skinny
+            # launch per target, each owning its 16 n columns (the last one also the padding) - against [W_ada | blockdiag]
+            BK, slot = ad
+            C, n, nt = self.cfg.C, BK['n'], self.cfg.depth + 1
+            ld = C + BK['kxa']
+            csa = torch.empty(R, ld, device=cond.device, dtype=self.compute_dtype)
+            for t in range(nt):
+                ops.lora_down_rows(cs, BK['A']['ada'][t], BK['scale'], slot, csa, R=R, l=1, K=C, kpad=16 * n if t + 1 < nt else BK['kxa'] - 16 * n * t,
+                                   ldxa=ld, xa_off=16 * n * t, x_copy=csa if t == 0 else None, ld_copy=ld)
+            ops.gemm(csa, BK['W']['ada'], ada, M=R, N=P['n_ada'], K=ld, lda=ld, ldw=ld, bias=P['b_ada'], small_m=sm, split_k=sm)
+            return ada
         ops.gemm(cs, P['w_ada'], ada, M=R, N=P['n_ada'], K=self.cfg.C, bias=P['b_ada'], small_m=sm, split_k=sm)
         return ada
 
@@ -1321,9 +1359,10 @@ class ControlVAR(nn.Module):
 
     @torch.no_grad()
     def _generate(self, B, label_B, g_seed, cfg_scale, top_k, top_p, more_smooth, cond_type, four_way, c_mask, c_img,
-                  force_idx=None, trace: bool = False, gumbel=None):
-        if _per_request(cfg_scale, top_k, top_p, g_seed, four_way):
-            return self._generate_rows(B, label_B, g_seed, cfg_scale, top_k, top_p, more_smooth, cond_type, four_way, c_mask, c_img, force_idx, trace)
+                  force_idx=None, trace: bool = False, gumbel=None, adapter=None):
+        if adapter is not None or _per_request(cfg_scale, top_k, top_p, g_seed, four_way):          # adapter= selects the per-request path, as a per-row cfg does
+            return self._generate_rows(B, label_B, g_seed, cfg_scale, top_k, top_p, more_smooth, cond_type, four_way, c_mask, c_img, force_idx, trace,
+                                       adapter=adapter)
         if four_way:
             cfg_scale = tuple(cfg_scale)
         if top_k > self.cfg.vocab:                     # helpers.py:8-10: torch.topk raises on k > V; top_k <= 0 means no top-k filter
@@ -1387,13 +1426,32 @@ class ControlVAR(nn.Module):
                              'None draws them from the one batch seed of the scalar path, which a batch of requests does not have')
 
     @torch.no_grad()
-    def _generate_rows(self, B, label_B, g_seed, cfg_scale, top_k, top_p, more_smooth, cond_type, four_way, c_mask, c_img, force_idx=None, trace: bool = False):
+    def _adapter_slots(self, adapter, B: int, nrep: int):
+        """``adapter=`` -> the slot of every sequence (host int32, nrep * B), or None when it is not given; refuses on the host"""
+        if adapter is None:
+            return None
+        from . import lora
+        if not lora.has_adapters(self):
+            raise RuntimeError('adapter=: no bank attached - call controlvar_amd.lora.attach_adapters(model, sources) first')
+        return lora.sequence_slots(lora.adapter_ids(adapter, B, self._adapter_bank['n']), nrep)
+
+    def _adapter_operands(self, table: _RequestTable, dev_buf: torch.Tensor):
+        """(bank pack, device slot table) for _generate_core, or None for a table without slots"""
+        if not table.n_seq:
+            return None
+        from . import lora
+        return lora.bank_pack(self), table.slot_view(dev_buf)
+
+    @torch.no_grad()
+    def _generate_rows(self, B, label_B, g_seed, cfg_scale, top_k, top_p, more_smooth, cond_type, four_way, c_mask, c_img, force_idx=None, trace: bool = False,
+                       adapter=None):
         """per-request mode (an addition of this library): any of cfg / top_k / top_p / g_seed given per batch row.  Row b produces exactly
         what the scalar call produces at B = 1 with (label_b, cond_type_b, cfg_b, top_k_b, top_p_b, g_seed = seed_b): combined logits, kept-set
         size, margin, ids and image - bit for bit under deterministic_plan=True (the sampler always is; the plan makes the logits independent
         of the batch).  A bidirectional model still draws ONE (control, image) order per call from python's `random`, as the scalar path."""
         self._check_per_request(label_B, cond_type, four_way, more_smooth)
-        table = _request_table(B, cfg_scale, top_k, top_p, g_seed, four_way, self.cfg.vocab, len(self.cfg.pyramid.patch_nums))
+        slots = self._adapter_slots(adapter, B, 4 if four_way else 2)
+        table = _request_table(B, cfg_scale, top_k, top_p, g_seed, four_way, self.cfg.vocab, len(self.cfg.pyramid.patch_nums), slots=slots)
         self._pack(check=True); self.vae_proxy[0]._pack(check=True)
         for name, ids in (('c_mask', c_mask), ('c_img', c_img), ('_force_idx', force_idx)):
             if ids is not None:
@@ -1406,20 +1464,23 @@ class ControlVAR(nn.Module):
         if self.cfg.separator and four_way:
             raise NotImplementedError('separator: conditional_infer_cfg ignores the special tokens (control_var.py:270-330); only forward(), training '
                                       'and the joint autoregressive_infer_cfg branch are built')
-        rows = table.views(table.host.to(self.device))
+        tab_dev = table.host.to(self.device)              # the request table and the adapter slots: one upload
         return self._generate_core(B, labels_all, types_all, 0, None, None, None, None, four_way, c_mask, c_img, force_idx, trace, mask_first=mask_first,
-                                   rows=rows)
+                                   rows=table.views(tab_dev), ad=self._adapter_operands(table, tab_dev))
 
     @torch.no_grad()
     def _generate_core(self, B, labels_all, types_all, seed, seed_dev, cfg_scale, top_k, top_p, four_way, c_mask=None, c_img=None,
                        force_idx=None, trace: bool = False, mask_first: bool = True, more_smooth: bool = False, gumbel=None, draws=None, rows=None,
-                       forced=None):
+                       forced=None, ad=None):
         """the 10-scale loop on device-resident inputs only (capturable in a HIP graph: no host sync, static shapes).
         draws (sampler='torch'): the noise of each sampling call comes from the caller's torch generator (_TorchDraws).
         rows (per-request mode): device views (seed, top_k, top_p, coef [nstage][B][4]) of a _RequestTable; the sampling call of every scale
         is then the per-row one and cfg_scale / top_k / top_p / seed are not used.
         forced (region-constrained generation, with rows only): device (B, L) int32, the source id of every kept token and -1 elsewhere
-        (ops.edit_force_table); the sampling launch of every scale then writes the kept ids itself (ops.cfg_sample_edit)"""
+        (ops.edit_force_table); the sampling launch of every scale then writes the kept ids itself (ops.cfg_sample_edit)
+        ad (per-request adapters, with rows only): (lora.bank_pack, device slot (R,) int32) handed to _ada and _blocks_and_head"""
+        if ad is not None and rows is None:
+            raise ValueError('ad: the per-request path only (rows given)')
         if forced is not None and (rows is None or four_way):
             raise ValueError('forced: the per-request joint path only (rows given, two branches)')
         cfg, P = self.cfg, self._pack()
@@ -1433,7 +1494,7 @@ class ControlVAR(nn.Module):
         cond = torch.empty(R, C, device=dev, dtype=torch.float32)
         self._first_tokens(P, labels_all, types_all, x, cond, R, py.first_l, P['lvl_pos'], mask_first)
         gen_table = P['lvl_pos'] if four_way else (P['lvl_pos_gen'] if mask_first else P['lvl_pos_gen_'])
-        ada = self._ada(cond, R)
+        ada = self._ada(cond, R, ad)
         arena = self._get_arena(R, py.L)
         S = py.patch_nums[-1]
         f_hat = torch.zeros(nb, mf, cfg.cvae, S, S, device=dev, dtype=torch.float32)
@@ -1446,7 +1507,7 @@ class ControlVAR(nn.Module):
         for si, pn in enumerate(py.patch_nums):
             l = py.l[si]
             ratio = si / (nstage - 1)
-            logits = self._blocks_and_head(x[:R * l], ada, R, l, py.begin[si], py.L, arena, lvl_end=inf_lvl, holes=inf_holes)
+            logits = self._blocks_and_head(x[:R * l], ada, R, l, py.begin[si], py.L, arena, lvl_end=inf_lvl, holes=inf_holes, ad=ad)
             if rows is not None:
                 coef = None                                              # _request_table built them with the expressions below
             elif four_way:
@@ -1610,28 +1671,39 @@ class ControlVAR(nn.Module):
         return graph, out, owned
 
     @torch.no_grad()
-    def _capture_per_request(self, B, four_way, labels_all, types_all, cfg, top_k, top_p, finish, teach=None, refresh=None, prologue=None):
+    def _capture_per_request(self, B, four_way, labels_all, types_all, cfg, top_k, top_p, finish, teach=None, refresh=None, prologue=None,
+                             adapters: bool = False):
         """per_request=True of the two graphed generators: capture the scale loop with the per-row sampler on a static _RequestTable and return
         run(label_B, cond_type[, given_half], g_seed=None, cfg=..., top_k=..., top_p=...).  refresh(given_half) validates the given half and
-        returns the copy into its static buffer (conditional form); prologue() runs inside the graph before the scale loop"""
+        returns the copy into its static buffer (conditional form); prologue() runs inside the graph before the scale loop.
+        adapters=True: the adapter launches are captured over the attached bank, the slot of every sequence rides in the same static table,
+        and run takes adapter= (default: every row on the base model)"""
         dev, vocab, nstage = self.device, self.cfg.vocab, len(self.cfg.pyramid.patch_nums)
-        tab_dev = _request_table(B, cfg, top_k, top_p, 0, four_way, vocab, nstage).host.to(dev)          # also validates the defaults
-        rows = _RequestTable(B, nstage).views(tab_dev)
+        nrep = 4 if four_way else 2
+        slots0 = self._adapter_slots(-1, B, nrep) if adapters else None
+        table0 = _request_table(B, cfg, top_k, top_p, 0, four_way, vocab, nstage, slots=slots0)         # also validates the defaults
+        tab_dev = table0.host.to(dev)
+        rows = table0.views(tab_dev)
+        ad = self._adapter_operands(table0, tab_dev)
 
         def body():
             if prologue is not None:
                 prologue()
-            return finish(self._generate_core(B, labels_all, types_all, 0, None, None, None, None, four_way, rows=rows, **(teach or {})))
+            return finish(self._generate_core(B, labels_all, types_all, 0, None, None, None, None, four_way, rows=rows, ad=ad, **(teach or {})))
 
         graph, out, owned = self._capture(body)
 
-        def replay(label_B, cond_type, g_seed, r_cfg, r_top_k, r_top_p, given_half=None):
+        def replay(label_B, cond_type, g_seed, r_cfg, r_top_k, r_top_p, given_half=None, adapter=None):
             # everything that can refuse runs before the first static buffer is written
             self._check_per_request(label_B, cond_type, four_way)
+            if adapter is not None and not adapters:
+                raise TypeError('run() got adapter=: this graph was captured without adapters=True, so it holds none of the adapter launches - '
+                                'capture it with adapters=True to choose an adapter per call and per row')
+            slots = self._adapter_slots(-1 if adapter is None else adapter, B, nrep) if adapters else None
             for name, v in (('label_B', label_B), ('cond_type', cond_type)):
                 if torch.is_tensor(v) and tuple(v.shape) != (B,):
                     raise ValueError(f'{name}: expected shape ({B},), got {tuple(v.shape)}')
-            table = _request_table(B, r_cfg, r_top_k, r_top_p, g_seed, four_way, vocab, nstage)
+            table = _request_table(B, r_cfg, r_top_k, r_top_p, g_seed, four_way, vocab, nstage, slots=slots)
             la, ta = self._prepare_rows(B, label_B, cond_type, four_way, 0)
             copy_given = refresh(given_half) if refresh is not None else None
             labels_all.copy_(la)
@@ -1639,22 +1711,30 @@ class ControlVAR(nn.Module):
                 types_all.copy_(ta)
             if copy_given is not None:
                 copy_given()
-            tab_dev.copy_(table.host)                       # seeds, top_k, top_p and every stage's weights: one host-to-device copy
+            tab_dev.copy_(table.host)                       # seeds, top_k, top_p, every stage's weights and the adapter slots: one host-to-device copy
             graph.replay()
             return out.clone()
 
         if refresh is None:
-            def run(label_B, cond_type=None, g_seed=None, cfg=cfg, top_k=top_k, top_p=top_p):
-                return replay(label_B, cond_type, g_seed, cfg, top_k, top_p)
+            def run(label_B, cond_type=None, g_seed=None, cfg=cfg, top_k=top_k, top_p=top_p, adapter=None):
+                return replay(label_B, cond_type, g_seed, cfg, top_k, top_p, adapter=adapter)
         else:
-            def run(label_B, cond_type, given_half, g_seed=None, cfg=cfg, top_k=top_k, top_p=top_p):
-                return replay(label_B, cond_type, g_seed, cfg, top_k, top_p, given_half)
+            def run(label_B, cond_type, given_half, g_seed=None, cfg=cfg, top_k=top_k, top_p=top_p, adapter=None):
+                return replay(label_B, cond_type, g_seed, cfg, top_k, top_p, given_half, adapter=adapter)
         run.graph = graph
-        run.owned = owned                                   # dropped together with the graph when `run` goes away
+        run.owned = owned + ([ad[0]] if ad is not None else [])          # dropped together with the graph when `run` goes away
         return run
 
+    def _check_graph_adapters(self, per_request: bool, adapters: bool):
+        if not adapters:
+            return
+        if not per_request:
+            raise ValueError('adapters=True needs per_request=True: the adapter slots travel with the per-request table')
+        if getattr(self, '_adapter_bank', None) is None:
+            raise RuntimeError('adapters=True: no bank attached - call controlvar_amd.lora.attach_adapters(model, sources) first')
+
     @torch.no_grad()
-    def graphed_generator(self, B: int, cfg=1.5, top_k: int = 0, top_p: float = 0.0, per_request: bool = False):
+    def graphed_generator(self, B: int, cfg=1.5, top_k: int = 0, top_p: float = 0.0, per_request: bool = False, adapters: bool = False):
         """Capture one full `autoregressive_infer_cfg` (10 scales x depth blocks + both VQVAE decodes, ~2.5k launches) in a
         HIP graph and return ``run(label_B, cond_type=None, g_seed=None) -> images``.  Labels, condition types and the
         sampling seed live in static device buffers that are refreshed before each replay, so every call draws new samples.
@@ -1662,9 +1742,11 @@ class ControlVAR(nn.Module):
         per_request=True captures the per-row sampler instead: cfg, top_k, top_p and the seed of every row live in one static table that
         one copy refreshes, and ``run(label_B, cond_type, g_seed=None, cfg=..., top_k=..., top_p=...)`` takes each as a scalar or per row
         (those given here are its defaults) - one graph serves every mix of guidance scales, greedy beside sampled.  Row b of a replay is
-        what autoregressive_infer_cfg(B, ...) gives in per-request mode; everything is validated on the host before a buffer is touched."""
+        what autoregressive_infer_cfg(B, ...) gives in per-request mode; everything is validated on the host before a buffer is touched.
+        adapters=True (with per_request=True, on a model with an adapter bank): run also takes adapter=, one id per row or one int."""
         dev = self.device
         four_way = False
+        self._check_graph_adapters(per_request, adapters)
         if self.sampler == 'torch':
             raise NotImplementedError("graphed_generator captures the counter sampler only: sampler='torch' draws its noise with torch on model.rng "
                                       "between the launches; set model.sampler = 'counter' to capture, or call autoregressive_infer_cfg")
@@ -1674,7 +1756,7 @@ class ControlVAR(nn.Module):
         ty0 = torch.zeros(B, dtype=torch.int64) if self.cfg.mask_factor == 2 else None
         labels_all, types_all = self._prepare_rows(B, lab0, ty0, four_way, 0)
         if per_request:
-            return self._capture_per_request(B, four_way, labels_all, types_all, cfg, top_k, top_p, self._decode_pair)
+            return self._capture_per_request(B, four_way, labels_all, types_all, cfg, top_k, top_p, self._decode_pair, adapters=adapters)
         seed_dev = torch.zeros(1, device=dev, dtype=torch.int64)
         graph, out, owned = self._capture(lambda: self._decode_pair(self._generate_core(B, labels_all, types_all, 0, seed_dev, cfg, top_k, top_p, four_way)))
 
@@ -1695,7 +1777,7 @@ class ControlVAR(nn.Module):
 
     @torch.no_grad()
     def graphed_conditional_generator(self, B: int, given: str = 'control', cfg=(1.5, 1.5, 1.5), top_k: int = 0, top_p: float = 0.0,
-                                      source: str = 'ids', decode: str = 'both', per_request: bool = False):
+                                      source: str = 'ids', decode: str = 'both', per_request: bool = False, adapters: bool = False):
         """Capture one full `conditional_infer_cfg` in a HIP graph - control in, image out (given='control': the control ids are teacher-forced
         as `c_mask=`, the image is generated) or image in, control out (given='image', `c_img=`) - and return
         ``run(label_B, cond_type, given_half, g_seed=None) -> images``.
@@ -1711,6 +1793,7 @@ class ControlVAR(nn.Module):
         g_seed / cfg / top_k / top_p a scalar (cfg: one triple) or per row (cfg: (B, 3)); those given here are the defaults of run."""
         if self.mask_factor != 2:
             raise NotImplementedError('graphed_conditional_generator needs mask_factor == 2 (control_var.py:333)')
+        self._check_graph_adapters(per_request, adapters)
         if self.sampler == 'torch':
             raise NotImplementedError("graphed_conditional_generator captures the counter sampler only: sampler='torch' draws its noise with torch on "
                                       "model.rng between the launches; set model.sampler = 'counter' to capture, or call conditional_infer_cfg")
@@ -1783,7 +1866,8 @@ class ControlVAR(nn.Module):
                 checked = as_given(given_half)
                 return lambda: (pix_buf if pix_buf is not None else ids_buf).copy_(checked)
 
-            run = self._capture_per_request(B, True, labels_all, types_all, cfg, top_k, top_p, finish, teach=teach, prologue=tokenise, refresh=refresh)
+            run = self._capture_per_request(B, True, labels_all, types_all, cfg, top_k, top_p, finish, teach=teach, prologue=tokenise, refresh=refresh,
+                                            adapters=adapters)
             run.ids = lambda: ids_buf.clone()
             return run
         graph, out, owned = self._capture(body)
@@ -1824,7 +1908,7 @@ class ControlVAR(nn.Module):
 
     @torch.no_grad()
     def edit_infer_cfg(self, B: int, label_B, cond_type, *, src_img=None, keep_img=None, src_ctrl=None, keep_ctrl=None, g_seed=None, cfg=1.5,
-                       top_k=0, top_p=0.0, trace: bool = False, more_smooth: bool = False) -> torch.Tensor:
+                       top_k=0, top_p=0.0, trace: bool = False, more_smooth: bool = False, adapter=None) -> torch.Tensor:
         """Region-constrained generation (an addition of this library): keep the source's tokens where a mask says "keep", sample the others in
         their context - in-painting, out-painting, editing under a control map (keep_ctrl=True, the image partly kept), or a consistent joint
         edit (the same region of both halves free).  Returns what autoregressive_infer_cfg returns.
@@ -1837,12 +1921,12 @@ class ControlVAR(nn.Module):
         g_seed / cfg / top_k / top_p: a scalar or one value per row, as in per-request mode (a scalar seed gives identical requests
         identical results).  label_B and cond_type are given per row.  trace=True leaves last_trace as _trace does, 'idx' holding the ids
         AFTER forcing, plus last_trace['forced'], the table.  more_smooth, sampler='torch', the two-pass separate_decoding branch and
-        separator models are refused."""
+        separator models are refused.  adapter: one adapter id per row or one int, as in autoregressive_infer_cfg (lora.attach_adapters)."""
         self._check_edit(label_B, cond_type, more_smooth)
         pns = self.cfg.pyramid.patch_nums
         s_ctrl, k_ctrl = _edit_half('ctrl', src_ctrl, keep_ctrl, B, pns, self.cfg.vocab) if self.cfg.mask_factor == 2 else (None, None)
         s_img, k_img = _edit_half('img', src_img, keep_img, B, pns, self.cfg.vocab)
-        table = _request_table(B, cfg, top_k, top_p, g_seed, False, self.cfg.vocab, len(pns))
+        table = _request_table(B, cfg, top_k, top_p, g_seed, False, self.cfg.vocab, len(pns), slots=self._adapter_slots(adapter, B, 2))
         self._pack(check=True); self.vae_proxy[0]._pack(check=True)
         labels_all, types_all = self._prepare_rows(B, label_B, cond_type, False, 0)
         mask_first = True
@@ -1853,14 +1937,15 @@ class ControlVAR(nn.Module):
         on_dev = [None if t is None else t.to(device=dev, dtype=dt).contiguous() for t, dt in ((s_ctrl, torch.int32), (k_ctrl, torch.uint8),
                                                                                                 (s_img, torch.int32), (k_img, torch.uint8))]
         forced = self._edit_table(B, *on_dev, mask_first)
-        rows = table.views(table.host.to(dev))
-        f_hat = self._generate_core(B, labels_all, types_all, 0, None, None, None, None, False, trace=trace, mask_first=mask_first, rows=rows, forced=forced)
+        tab_dev = table.host.to(dev)
+        f_hat = self._generate_core(B, labels_all, types_all, 0, None, None, None, None, False, trace=trace, mask_first=mask_first, rows=table.views(tab_dev),
+                                    forced=forced, ad=self._adapter_operands(table, tab_dev))
         if trace:
             self.last_trace['forced'] = forced
         return self._decode_pair(f_hat)
 
     @torch.no_grad()
-    def graphed_edit_generator(self, B: int, source: str = 'ids', cfg=1.5, top_k=0, top_p=0.0, decode: str = 'both'):
+    def graphed_edit_generator(self, B: int, source: str = 'ids', cfg=1.5, top_k=0, top_p=0.0, decode: str = 'both', adapters: bool = False):
         """Capture one full `edit_infer_cfg` in a HIP graph and return
         ``run(label_B, cond_type, *, src_img=None, keep_img=None, src_ctrl=None, keep_ctrl=None, g_seed=None, cfg=..., top_k=..., top_p=...) -> images``.
         The keep masks (uint8, all zero = nothing kept), the sources and the request table live in static device buffers refreshed before each
@@ -1877,6 +1962,7 @@ class ControlVAR(nn.Module):
                                       "between the launches; set model.sampler = 'counter' to capture")
         if self.bidirectional:
             raise NotImplementedError('the captured generator fixes the (control, image) order; bidirectional models draw it per call')
+        self._check_graph_adapters(True, adapters)
         for name, val, ok in (('source', source, ('ids', 'pixels')), ('decode', decode, ('both', 'generated'))):
             if val not in ok:
                 raise ValueError(f'{name}={val!r}: one of {" / ".join(ok)}')
@@ -1921,15 +2007,16 @@ class ControlVAR(nn.Module):
             return copy
 
         inner = self._capture_per_request(B, False, labels_all, types_all, cfg, top_k, top_p, finish, teach={'forced': forced}, refresh=refresh,
-                                          prologue=prologue)
+                                          prologue=prologue, adapters=adapters)
 
         if mf == 2:
-            def run(label_B, cond_type, *, src_img=None, keep_img=None, src_ctrl=None, keep_ctrl=None, g_seed=None, cfg=cfg, top_k=top_k, top_p=top_p):
+            def run(label_B, cond_type, *, src_img=None, keep_img=None, src_ctrl=None, keep_ctrl=None, g_seed=None, cfg=cfg, top_k=top_k, top_p=top_p,
+                    adapter=None):
                 return inner(label_B, cond_type, dict(src_img=src_img, keep_img=keep_img, src_ctrl=src_ctrl, keep_ctrl=keep_ctrl), g_seed=g_seed, cfg=cfg,
-                             top_k=top_k, top_p=top_p)
+                             top_k=top_k, top_p=top_p, adapter=adapter)
         else:
-            def run(label_B, cond_type=None, *, src_img=None, keep_img=None, g_seed=None, cfg=cfg, top_k=top_k, top_p=top_p):
-                return inner(label_B, None, dict(src_img=src_img, keep_img=keep_img), g_seed=g_seed, cfg=cfg, top_k=top_k, top_p=top_p)
+            def run(label_B, cond_type=None, *, src_img=None, keep_img=None, g_seed=None, cfg=cfg, top_k=top_k, top_p=top_p, adapter=None):
+                return inner(label_B, None, dict(src_img=src_img, keep_img=keep_img), g_seed=g_seed, cfg=cfg, top_k=top_k, top_p=top_p, adapter=adapter)
         run.graph, run.owned = inner.graph, inner.owned
         run.ids = lambda: tuple(ids_buf[h].clone() for h in halves)          # the sources of the last replay ('pixels': what the tokeniser produced)
         run.forced = lambda: forced.clone()                                  # ... and its forced-token table
@@ -1950,20 +2037,23 @@ class ControlVAR(nn.Module):
     # ---- public API
     @torch.no_grad()
     def autoregressive_infer_cfg(self, B: int, label_B, g_seed: Optional[int] = None, cfg=1.5, top_k=0, top_p=0.0,
-                                 more_smooth=False, cond_type=None, _force_idx=None, _trace=False, _gumbel=None) -> torch.Tensor:
+                                 more_smooth=False, cond_type=None, _force_idx=None, _trace=False, _gumbel=None, adapter=None) -> torch.Tensor:
         """control_var.py:356-565: returns (B, 3, 2 H, H) in [0,1] with H = 16 patch_nums[-1] - (B, 3, 512, 256) for the default list, (B, 3, 1024, 512) for
         PATCH_NUMS_512 (control image on top, RGB below).
-        more_smooth: Gumbel-softmax soft code embeddings (:511-515); `_gumbel` (tests) injects the per-pass noise instead of drawing it."""
-        f_hat = self._generate(B, label_B, g_seed, cfg, top_k, top_p, more_smooth, cond_type, False, None, None, _force_idx, _trace, _gumbel)
+        more_smooth: Gumbel-softmax soft code embeddings (:511-515); `_gumbel` (tests) injects the per-pass noise instead of drawing it.
+        adapter (an addition of this library, lora.attach_adapters): one adapter id per row, or one int; -1 = the base model.  Selects the
+        per-request path, as a per-row cfg does."""
+        f_hat = self._generate(B, label_B, g_seed, cfg, top_k, top_p, more_smooth, cond_type, False, None, None, _force_idx, _trace, _gumbel, adapter=adapter)
         return self._decode_pair(f_hat)
 
     @torch.no_grad()
     def conditional_infer_cfg(self, B: int, label_B, g_seed: Optional[int] = None, cfg=(1.5, 1.5, 1.5), top_k=0, top_p=0.0,
-                              more_smooth=False, cond_type=None, c_mask=None, c_img=None, _force_idx=None, _trace=False, _gumbel=None) -> torch.Tensor:
+                              more_smooth=False, cond_type=None, c_mask=None, c_img=None, _force_idx=None, _trace=False, _gumbel=None,
+                              adapter=None) -> torch.Tensor:
         """control_var.py:223-354: 4-branch CFG with teacher forcing of the control (c_mask) or image (c_img) ids."""
         if self.mask_factor != 2:
             raise NotImplementedError('conditional_infer_cfg needs mask_factor == 2 (control_var.py:333)')
-        f_hat = self._generate(B, label_B, g_seed, cfg, top_k, top_p, more_smooth, cond_type, True, c_mask, c_img, _force_idx, _trace, _gumbel)
+        f_hat = self._generate(B, label_B, g_seed, cfg, top_k, top_p, more_smooth, cond_type, True, c_mask, c_img, _force_idx, _trace, _gumbel, adapter=adapter)
         return self._decode_pair(f_hat)
 
     def forward(self, label_B: torch.LongTensor, x_BLCv_wo_first_l: torch.Tensor, cond_type=None, mask_first=True) -> torch.Tensor:
@@ -2030,17 +2120,17 @@ class VAR(ControlVAR):
 
     @torch.no_grad()
     def autoregressive_infer_cfg(self, B: int, label_B, g_seed: Optional[int] = None, cfg=1.5, top_k=0, top_p=0.0,
-                                 more_smooth=False, _force_idx=None, _trace=False) -> torch.Tensor:
+                                 more_smooth=False, _force_idx=None, _trace=False, adapter=None) -> torch.Tensor:
         """var.py:143-207: returns (B, 3, H, H) in [0,1], H = 16 patch_nums[-1] (256, or 512 with PATCH_NUMS_512)."""
-        f_hat = self._generate(B, label_B, g_seed, cfg, top_k, top_p, more_smooth, None, False, None, None, _force_idx, _trace)
+        f_hat = self._generate(B, label_B, g_seed, cfg, top_k, top_p, more_smooth, None, False, None, None, _force_idx, _trace, adapter=adapter)
         return self._decode_pair(f_hat)
 
     @torch.no_grad()
     def edit_infer_cfg(self, B: int, label_B, *, src_img=None, keep_img=None, g_seed=None, cfg=1.5, top_k=0, top_p=0.0, trace: bool = False,
-                       more_smooth: bool = False) -> torch.Tensor:
+                       more_smooth: bool = False, adapter=None) -> torch.Tensor:
         """ControlVAR.edit_infer_cfg for the one half a plain VAR has: returns (B, 3, H, H) as autoregressive_infer_cfg"""
         return super().edit_infer_cfg(B, label_B, None, src_img=src_img, keep_img=keep_img, g_seed=g_seed, cfg=cfg, top_k=top_k, top_p=top_p, trace=trace,
-                                      more_smooth=more_smooth)
+                                      more_smooth=more_smooth, adapter=adapter)
 
     def conditional_infer_cfg(self, *a, **k):
         raise NotImplementedError('plain VAR has no conditional_infer_cfg (var.py)')

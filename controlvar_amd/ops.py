@@ -549,6 +549,26 @@ def lora_down(x, A, u, *, M: int, K: int, r: int, scale: float, p: float = 0.0, 
     return u
 
 
+def lora_down_rows(x, A_bank, scale, slot, xa, *, R: int, l: int, K: int, kpad: int, ldx: int = 0, ldxa: int = 0, x_copy=None, ld_copy: int = 0,
+                   xa_off: int = 0):
+    """per-row adapters (cvar_lora_down_rows, include/cvar_serve.h): row m of the R * l rows of x uses slot[m // l] (-1: none).  A_bank
+    (n_slots, 16, lda >= K) in x's dtype, scale (n_slots,) float32 and slot (R,) int32 contiguous on x's device.  Columns
+    [K, K + kpad) of xa (+ xa_off elements) receive scale[s] x A_s^T in the slot's 16-column group and zeros everywhere else; x_copy
+    receives x unchanged"""
+    if A_bank.dtype != x.dtype or xa.dtype != x.dtype or (x_copy is not None and x_copy.dtype != x.dtype):
+        raise TypeError('lora_down_rows: x, A_bank, xa and x_copy must share a dtype')
+    if A_bank.ndim != 3 or A_bank.shape[1] != 16 or A_bank.stride(2) != 1 or A_bank.stride(0) != 16 * A_bank.stride(1):
+        raise ValueError('lora_down_rows: A_bank must be (n_slots, 16, k) with dense 16-row slots')
+    n = A_bank.shape[0]
+    for name, t, dtype, shape in (('scale', scale, torch.float32, (n,)), ('slot', slot, torch.int32, (R,))):
+        if t is not None and (not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != x.device):
+            raise ValueError(f'lora_down_rows: {name} must be a contiguous {str(dtype)[6:]} {shape} tensor on {x.device}')
+    check(_lib.load().cvar_lora_down_rows(_ptr(x), ldx or K, _ptr(A_bank), A_bank.stride(1), _ptr(scale), _ptr(slot), n, R, l,
+                                          _ptr(xa) + xa_off * xa.element_size() if xa is not None else None, ldxa or (K + kpad), kpad, _ptr(x_copy),
+                                          ld_copy or K, K, dt(x), _stream()), 'cvar_lora_down_rows')
+    return xa
+
+
 def lora_dx(dx, du, A, *, M: int, K: int, r: int, scale: float, p: float = 0.0, seed: int = 0, tag: int = 0, lddx: int = 0, lddu: int = 0,
             lda: int = 0, du_off: int = 0, aux=None, ldaux: int = 0):
     """dx = (dx + scale * drop'(du A)) * gelu'(aux) in place (cvar_lora_dx); du rows are 16 wide (lddu >= 16, a multiple of 8)"""

@@ -3,7 +3,7 @@
  *
  * The functions live in the same libcvar_hip.so as those of cvar.h.  They are versioned on their own: cvar_serve_version() bumps on
  * any signature change in THIS header, cvar_abi_version() stays the version of cvar.h.  Adding an entry point changes no signature and
- * leaves the version alone: cvar_edit_force_table and cvar_cfg_sample_edit joined at version 1.
+ * leaves the version alone: cvar_edit_force_table, cvar_cfg_sample_edit and cvar_lora_down_rows joined at version 1.
  */
 #ifndef CVAR_SERVE_H
 #define CVAR_SERVE_H
@@ -68,6 +68,30 @@ int cvar_cfg_sample_edit(const float* logits, int B, int nrep, int l, int V,
                          int stage, int n_draw, int32_t* idx_out, float* combined, float* margin, int32_t* kept, int ldv,
                          const float* expo /* must be NULL */, float* soft_out /* must be NULL */,
                          const int32_t* forced, int ldf, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Per-request LoRA adapters: the per-row form of cvar_lora_down for inference (no dropout).  Joined at version 1.
+ * The M = R * l rows of x are R sequences of l rows; row m belongs to sequence m / l and uses the adapter slot[m / l].
+ *   x      [M][ldx]            compute dtype (CVAR_BF16 / CVAR_F32), K columns read;
+ *   A_bank [n_slots][16][lda]  compute dtype, the down matrices of the bank; rows >= an adapter's rank are zero;
+ *   scale  [n_slots] fp32      DEVICE table, alpha / r of every slot;
+ *   slot   [R]       int32     DEVICE table; -1: no adapter.  The values are not checked (they are on the device): the caller keeps
+ *                              them in [-1, n_slots);
+ *   xa     [M][ldxa]           the K-augmented operand: the kernel owns the kpad columns [K, K + kpad) of every row;
+ *   kpad                       a multiple of 16, >= 16 * n_slots (CVAR_EINVAL otherwise);
+ *   x_copy [M][ld_copy]        optional: receives x bit for bit in the same pass (usually xa itself with ld_copy = ldxa).  NULL where the
+ *                              producer already wrote the wide buffer through its ldc (then x == xa, ldx == ldxa is allowed: the
+ *                              kernel reads columns < K and writes columns >= K only).
+ * Columns K + 16 slot .. K + 16 slot + 15 of row m hold scale[slot] * x[m] A_slot^T; EVERY other one of the kpad columns is written as
+ * zero (the buffers of a generation pass are uninitialised, and a NaN there would reach the GEMM); a slot = -1 row gets kpad zeros.
+ * Nothing outside [K, K + kpad) and the copy is touched.
+ * Row m with slot s equals, bit for bit, what cvar_lora_down(p = 0, r = 16, scale = scale[s]) writes for that row with A_bank[s]: both
+ * kernels run one reduction body.  One block serves one (sequence, 16-row chunk), so it stages the A slabs of one adapter only.
+ * n_slots 1..8, R >= 1, l >= 1, a NULL table: CVAR_EINVAL; K, ldx, lda, ldxa (>= K + kpad) and the pointers are checked as
+ * cvar_lora_down checks them (CVAR_EUNSUPPORTED). */
+int cvar_lora_down_rows(const void* x, int64_t ldx, const void* A_bank, int64_t lda, const float* scale /* [n_slots] */,
+                        const int32_t* slot /* [R] */, int n_slots, int R, int l, void* xa, int64_t ldxa, int kpad,
+                        void* x_copy, int64_t ld_copy, int K, int dtype, void* stream);
 
 #ifdef __cplusplus
 }
