@@ -122,6 +122,8 @@ SERVE_SIGNATURES = {
     'cvar_cfg_sample_edit': (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_p]),
     # per-request LoRA adapters: joined at version 1
     'cvar_lora_down_rows': (c_i, [c_p, c_l, c_p, c_l, c_p, c_p, c_i, c_i, c_i, c_p, c_l, c_i, c_p, c_l, c_i, c_i, c_p]),
+    # token log-probabilities: joined at version 1
+    'cvar_score_rows': (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p]),
 }
 
 _lib = None

@@ -466,6 +466,94 @@ __global__ __launch_bounds__(256) void cfg_sample_edit_kernel(const RowSamplePar
     sample_token<false, false>(p);
 }
 
+// ---- token log-probabilities (cvar_score_rows, include/cvar_serve.h) ------------------------------------------------------------------------
+// Scores a GIVEN id per token under the unfiltered CFG-combined distribution: log-probability, entropy, rank and the greedy id.  The combine is
+// combine_logits above (the sampler's text: `combined` and the argmax are the sampler's bits), the parameters of a row come from the same coef
+// table through coef_of.  The order of evaluation depends on nothing but (V, tid): thread tid owns elements tid + 256 j and adds them in
+// increasing j, a 64-lane xor-shuffle tree follows, the four wave partials are added in order 0..3.  No atomics; accurate expf / logf.
+struct ScoreParams {
+    const float* logits;
+    int B, nrep, l, V, ldv;
+    const float* coef;                      // [B][4] fp32, this stage's weights: the sampler's table
+    const int* target;                      // [B][ldt] int32; < 0: the token has no target
+    int ldt, ldo;                           // row strides of target and of the four per-token outputs (>= l)
+    float* combined;
+    float* logprob;
+    float* entropy;
+    int* rank;
+    int* argmax;
+};
+__device__ __forceinline__ const float* coef_of(const ScoreParams& p, long b) { return p.coef + b * 4; }
+
+__global__ __launch_bounds__(256) void cfg_score_rows_kernel(const ScoreParams p) {
+    constexpr int EPT = 16;
+    __shared__ float sb1[4], sb2[4], ssum[4], sent[4];
+    __shared__ int si1[4], scnt[4];
+    const int tid = threadIdx.x;
+    const long bt = blockIdx.x;
+    const long b = bt / p.l, t = bt % p.l;
+    int tgt = p.target[b * p.ldt + t];                             // block-uniform
+    if (tgt >= p.V) tgt = -1;                                      // out of contract (the host checks ids): nothing outside the row is read
+    float v[EPT];
+    Top2 best = {-INFINITY, 0x7fffffff, -INFINITY};
+#pragma unroll
+    for (int j = 0; j < EPT; ++j) {
+        const int e = j * 256 + tid;                               // thread-strided ownership: the row is read once, coalesced
+        float x = -INFINITY;
+        if (e < p.V) {
+            x = combine_logits(p, b, t, e);
+            if (p.combined) p.combined[bt * p.V + e] = x;
+            Top2 cur = {x, e, -INFINITY};
+            best = merge_top2(best, cur);                          // greedy_token's loop order: increasing e per thread
+        }
+        v[j] = x;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        Top2 other;
+        other.b1 = __shfl_xor(best.b1, o, 64); other.i1 = __shfl_xor(best.i1, o, 64); other.b2 = __shfl_xor(best.b2, o, 64);
+        best = merge_top2(best, other);
+    }
+    if ((tid & 63) == 0) { sb1[tid >> 6] = best.b1; si1[tid >> 6] = best.i1; sb2[tid >> 6] = best.b2; }
+    __syncthreads();
+    Top2 r = {sb1[0], si1[0], sb2[0]};
+    for (int w = 1; w < 4; ++w) { Top2 o = {sb1[w], si1[w], sb2[w]}; r = merge_top2(r, o); }
+    const float m = r.b1;
+    // the target's value: every thread evaluates the combine at the target column (a block-uniform load) - the owning lane's bits
+    const float xt = tgt >= 0 ? combine_logits(p, b, t, tgt) : 0.f;
+    float s = 0.f, u = 0.f;
+    int cnt = 0;
+#pragma unroll
+    for (int j = 0; j < EPT; ++j) {
+        const int e = j * 256 + tid;
+        if (e < p.V) {
+            const float d = __fsub_rn(v[j], m);
+            const float ex = expf(d);
+            s = __fadd_rn(s, ex);
+            if (ex != 0.f) u = __fadd_rn(u, __fmul_rn(ex, d));     // a -inf logit carries no mass: 0 * -inf never forms
+            cnt += (v[j] > xt || (v[j] == xt && e < tgt)) ? 1 : 0;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        s = __fadd_rn(s, __shfl_xor(s, o, 64));
+        u = __fadd_rn(u, __shfl_xor(u, o, 64));
+        cnt += __shfl_xor(cnt, o, 64);
+    }
+    if ((tid & 63) == 0) { ssum[tid >> 6] = s; sent[tid >> 6] = u; scnt[tid >> 6] = cnt; }
+    __syncthreads();
+    if (tid == 0) {
+        const float S = __fadd_rn(__fadd_rn(__fadd_rn(ssum[0], ssum[1]), ssum[2]), ssum[3]);
+        const float U = __fadd_rn(__fadd_rn(__fadd_rn(sent[0], sent[1]), sent[2]), sent[3]);
+        const float logS = logf(S);
+        const long o = b * p.ldo + t;
+        if (p.logprob) p.logprob[o] = tgt >= 0 ? __fsub_rn(__fsub_rn(xt, m), logS) : 0.f;
+        if (p.entropy) p.entropy[o] = __fsub_rn(logS, __fdiv_rn(U, S));
+        if (p.rank) p.rank[o] = tgt >= 0 ? (scnt[0] + scnt[1]) + (scnt[2] + scnt[3]) : -1;
+        if (p.argmax) p.argmax[o] = r.i1;
+    }
+}
+
 extern "C" int cvar_cfg_sample(const float* logits, int B, int nrep, int l, int V, const float* coef_host,
                                int top_k, float top_p, uint64_t seed, const uint64_t* seed_dev, int stage, int n_draw,
                                int32_t* idx_out, float* combined, float* margin, int32_t* kept, int ldv,
@@ -510,6 +598,21 @@ extern "C" int cvar_cfg_sample_rows(const float* logits, int B, int nrep, int l,
     p.stage = stage; p.n_draw = n_draw;
     p.idx_out = idx_out; p.combined = combined; p.margin = margin; p.kept = kept;
     hipLaunchKernelGGL(cfg_sample_rows_kernel, dim3((unsigned)((long)B * l)), dim3(256), 0, as_stream(stream), p);
+    CVAR_CHECK_LAUNCH();
+    return CVAR_OK;
+}
+
+extern "C" int cvar_score_rows(const float* logits, int B, int nrep, int l, int V, const float* coef, const int32_t* target, int ldt,
+                               float* combined, float* logprob, float* entropy, int32_t* rank, int32_t* argmax, int ldo, int ldv, void* stream) {
+    if (!logits || !coef || !target || B <= 0 || l <= 0 || V < 1 || ldt < l || (ldo != 0 && ldo < l)) return CVAR_EINVAL;
+    if (!combined && !logprob && !entropy && !rank && !argmax) return CVAR_EINVAL;
+    if (nrep < 1 || nrep > 4 || V > 4096) return CVAR_EUNSUPPORTED;
+    if (ldv != 0 && ldv < V) return CVAR_EINVAL;
+    ScoreParams p;
+    p.logits = logits; p.B = B; p.nrep = nrep; p.l = l; p.V = V; p.ldv = ldv ? ldv : V;
+    p.coef = coef; p.target = (const int*)target; p.ldt = ldt; p.ldo = ldo ? ldo : l;
+    p.combined = combined; p.logprob = logprob; p.entropy = entropy; p.rank = (int*)rank; p.argmax = (int*)argmax;
+    hipLaunchKernelGGL(cfg_score_rows_kernel, dim3((unsigned)((long)B * l)), dim3(256), 0, as_stream(stream), p);
     CVAR_CHECK_LAUNCH();
     return CVAR_OK;
 }

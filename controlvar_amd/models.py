@@ -850,6 +850,95 @@ def _refuse_request_keywords(g_seed, request: dict):
         raise ValueError('g_seed: one integer - this graph was captured with per_request=False; capture it with per_request=True for one seed per row')
 
 
+# ---- token log-probabilities (an addition of this library; include/cvar_serve.h: cvar_score_rows) ---------------------------------
+class TokenScores:
+    """Per-token scores of a generation (``logprobs=True``) or of given tokens (``score_infer_cfg``), all (B, L) with L = sum mask_factor pn^2
+    in the token order of generation: per scale the two halves, control first when mask_first and image first otherwise.
+      logprob  fp32   log-probability of the token's id under the CFG-combined distribution of its row - the UNFILTERED one: a top-k /
+                      top-p kept set is not renormalised over (a token outside the kept set of another request still has its finite score)
+      entropy  fp32   entropy of that distribution
+      rank     int32  the number of codes ahead of the id (0 = the greedy id, lowest index on ties)
+      argmax   int32  the greedy id
+      sampled  bool   False where the token was teacher-forced or kept by an edit; those tokens are scored too (the head computes their
+                      logits anyway)"""
+
+    def __init__(self, logprob, entropy, rank, argmax, patch_nums, mask_factor: int, mask_first: bool, sampled=None, forced=None):
+        self.logprob, self.entropy, self.rank, self.argmax = logprob, entropy, rank, argmax
+        self.patch_nums, self.mask_factor, self.mask_first = tuple(int(p) for p in patch_nums), int(mask_factor), bool(mask_first)
+        self._sampled, self._forced = sampled, forced          # a (B, L) / (L,) bool pattern, or the forced-token table (>= 0: not sampled)
+
+    @property
+    def sampled(self) -> torch.Tensor:
+        """evaluated on first use, so that a generation issues nothing for it"""
+        if self._sampled is None or self._sampled.dim() == 1:
+            if self._forced is not None:
+                s = self._forced < 0
+            else:
+                col = torch.ones(self.logprob.shape[1], dtype=torch.bool) if self._sampled is None else self._sampled
+                s = col.to(self.logprob.device)[None].expand(self.logprob.shape[0], -1).contiguous()
+            self._sampled, self._forced = s, None
+        return self._sampled
+
+    def _bounds(self):
+        b, out = 0, []
+        for pn in self.patch_nums:
+            out.append((b, b + self.mask_factor * pn * pn))
+            b = out[-1][1]
+        return out
+
+    def half_mask(self, half: Optional[str]) -> torch.Tensor:
+        """(L,) bool on the host: the tokens of 'control' / 'image' (None: all) in this object's half order"""
+        if half not in (None, 'control', 'image'):
+            raise ValueError(f"half={half!r}: None, 'control' or 'image'")
+        L = self._bounds()[-1][1]
+        if half is None or (self.mask_factor == 1 and half == 'image'):
+            return torch.ones(L, dtype=torch.bool)
+        if self.mask_factor == 1:
+            raise ValueError("half='control': a plain VAR has the image half only")
+        m = torch.zeros(L, dtype=torch.bool)
+        first = (half == 'control') == self.mask_first
+        for (b, e), pn in zip(self._bounds(), self.patch_nums):
+            m[b:b + pn * pn] = first
+            m[b + pn * pn:e] = not first
+        return m
+
+    def per_scale(self):
+        """one TokenScores per scale, its fields the (B, mask_factor pn^2) column views of this one's"""
+        s = self.sampled
+        return [TokenScores(self.logprob[:, b:e], self.entropy[:, b:e], self.rank[:, b:e], self.argmax[:, b:e], (pn,), self.mask_factor, self.mask_first,
+                            sampled=s[:, b:e]) for (b, e), pn in zip(self._bounds(), self.patch_nums)]
+
+    def total(self, half: Optional[str] = None, sampled_only: bool = False) -> torch.Tensor:
+        """(B,) float64: the sum of the log-probabilities over all tokens, or over one half ('control' / 'image'); sampled_only leaves out
+        the teacher-forced and the kept ones.  With score_infer_cfg(given=g), total(half=<the other half>) is log p(other | g)."""
+        m = self.half_mask(half).to(self.logprob.device)[None]
+        if sampled_only:
+            m = m & self.sampled
+        lp = self.logprob.double()
+        return torch.where(m, lp, torch.zeros((), dtype=lp.dtype, device=lp.device)).sum(dim=1)
+
+
+def _score_buffers(B: int, L: int, dev):
+    """(logprob, entropy, rank, argmax) device buffers (B, L) that the score launch of every scale writes its columns of"""
+    return (torch.empty(B, L, device=dev, dtype=torch.float32), torch.empty(B, L, device=dev, dtype=torch.float32),
+            torch.empty(B, L, device=dev, dtype=torch.int32), torch.empty(B, L, device=dev, dtype=torch.int32))
+
+
+def _score_ids(name: str, ids, B: int, pns, vocab: int) -> torch.Tensor:
+    """one half's ids of a scoring request, checked on the host -> flat integer ids (B, sum pn^2) on the device they came on"""
+    Lsrc = sum(pn * pn for pn in pns)
+    if isinstance(ids, (list, tuple)):
+        want = [(B, pn * pn) for pn in pns]
+        if not all(torch.is_tensor(t) for t in ids) or [tuple(t.shape) for t in ids] != want:
+            raise ValueError(f'{name}: expected {len(pns)} id tensors of shapes {want} (what img_to_idxBl returns)')
+        ids = torch.cat([t.to(ids[0].device) for t in ids], dim=1)
+    if not torch.is_tensor(ids) or tuple(ids.shape) != (B, Lsrc) or ids.is_floating_point() or ids.dtype == torch.bool:
+        raise ValueError(f'{name}: expected integer ids of shape ({B}, {Lsrc}) or a list of (B, pn * pn) tensors, got '
+                         f'{tuple(ids.shape) if torch.is_tensor(ids) else type(ids).__name__}')
+    _check_index_range(ids, 0, vocab - 1, name)
+    return ids
+
+
 # ---- region-constrained generation (an addition of this library; include/cvar_serve.h) --------------------------------------------
 def edit_keep_cells(keep: torch.Tensor, pn: int) -> torch.Tensor:
     """The cell rule of region-constrained generation on the host: keep (B, S, S) bool at latent resolution -> (B, pn * pn) bool, which tokens
@@ -1359,10 +1448,12 @@ class ControlVAR(nn.Module):
 
     @torch.no_grad()
     def _generate(self, B, label_B, g_seed, cfg_scale, top_k, top_p, more_smooth, cond_type, four_way, c_mask, c_img,
-                  force_idx=None, trace: bool = False, gumbel=None, adapter=None):
-        if adapter is not None or _per_request(cfg_scale, top_k, top_p, g_seed, four_way):          # adapter= selects the per-request path, as a per-row cfg does
+                  force_idx=None, trace: bool = False, gumbel=None, adapter=None, logprobs: bool = False):
+        """-> f_hat, or (f_hat, TokenScores) with logprobs=True"""
+        # adapter= and logprobs=True select the per-request path, as a per-row cfg does
+        if adapter is not None or logprobs or _per_request(cfg_scale, top_k, top_p, g_seed, four_way):
             return self._generate_rows(B, label_B, g_seed, cfg_scale, top_k, top_p, more_smooth, cond_type, four_way, c_mask, c_img, force_idx, trace,
-                                       adapter=adapter)
+                                       adapter=adapter, logprobs=logprobs)
         if four_way:
             cfg_scale = tuple(cfg_scale)
         if top_k > self.cfg.vocab:                     # helpers.py:8-10: torch.topk raises on k > V; top_k <= 0 means no top-k filter
@@ -1444,12 +1535,15 @@ class ControlVAR(nn.Module):
 
     @torch.no_grad()
     def _generate_rows(self, B, label_B, g_seed, cfg_scale, top_k, top_p, more_smooth, cond_type, four_way, c_mask, c_img, force_idx=None, trace: bool = False,
-                       adapter=None):
+                       adapter=None, logprobs: bool = False):
         """per-request mode (an addition of this library): any of cfg / top_k / top_p / g_seed given per batch row.  Row b produces exactly
         what the scalar call produces at B = 1 with (label_b, cond_type_b, cfg_b, top_k_b, top_p_b, g_seed = seed_b): combined logits, kept-set
         size, margin, ids and image - bit for bit under deterministic_plan=True (the sampler always is; the plan makes the logits independent
-        of the batch).  A bidirectional model still draws ONE (control, image) order per call from python's `random`, as the scalar path."""
+        of the batch).  A bidirectional model still draws ONE (control, image) order per call from python's `random`, as the scalar path.
+        logprobs=True: one score launch per scale behind the sampling launch and the teacher-forcing overwrites; returns (f_hat, TokenScores)."""
         self._check_per_request(label_B, cond_type, four_way, more_smooth)
+        if logprobs:
+            self._check_logprobs()
         slots = self._adapter_slots(adapter, B, 4 if four_way else 2)
         table = _request_table(B, cfg_scale, top_k, top_p, g_seed, four_way, self.cfg.vocab, len(self.cfg.pyramid.patch_nums), slots=slots)
         self._pack(check=True); self.vae_proxy[0]._pack(check=True)
@@ -1465,22 +1559,60 @@ class ControlVAR(nn.Module):
             raise NotImplementedError('separator: conditional_infer_cfg ignores the special tokens (control_var.py:270-330); only forward(), training '
                                       'and the joint autoregressive_infer_cfg branch are built')
         tab_dev = table.host.to(self.device)              # the request table and the adapter slots: one upload
-        return self._generate_core(B, labels_all, types_all, 0, None, None, None, None, four_way, c_mask, c_img, force_idx, trace, mask_first=mask_first,
-                                   rows=table.views(tab_dev), ad=self._adapter_operands(table, tab_dev))
+        score = _score_buffers(B, self.cfg.pyramid.L, self.device) if logprobs else None
+        f_hat = self._generate_core(B, labels_all, types_all, 0, None, None, None, None, four_way, c_mask, c_img, force_idx, trace, mask_first=mask_first,
+                                    rows=table.views(tab_dev), ad=self._adapter_operands(table, tab_dev), score=score)
+        if not logprobs:
+            return f_hat
+        return f_hat, self._token_scores(score, mask_first, self._sampled_pattern(four_way, c_mask, c_img, force_idx))
+
+    def _check_logprobs(self):
+        """what logprobs=True / score_infer_cfg do not offer beyond _check_per_request's list, said on the host before any device work"""
+        if self.cfg.separator:
+            raise NotImplementedError('token log-probabilities: separator models are not offered (their scales carry special tokens between the halves, '
+                                      'which the (B, L) score layout does not hold)')
+
+    def _token_scores(self, score, mask_first: bool, sampled=None, forced=None) -> TokenScores:
+        return TokenScores(*score, self.cfg.pyramid.patch_nums, self.cfg.mask_factor, mask_first, sampled=sampled, forced=forced)
+
+    def _sampled_pattern(self, four_way: bool, c_mask, c_img, force_idx) -> Optional[torch.Tensor]:
+        """(L,) bool on the host: which tokens of a generation are sampled (None: all).  The four-branch path lays control first."""
+        if force_idx is not None:
+            return torch.zeros(self.cfg.pyramid.L, dtype=torch.bool)
+        if not four_way or (c_mask is None and c_img is None):
+            return None
+        col, b = torch.ones(self.cfg.pyramid.L, dtype=torch.bool), 0
+        for pn in self.cfg.pyramid.patch_nums:
+            n = pn * pn
+            if c_mask is not None:
+                col[b:b + n] = False
+            if c_img is not None:
+                col[b + n:b + 2 * n] = False
+            b += 2 * n
+        return col
 
     @torch.no_grad()
     def _generate_core(self, B, labels_all, types_all, seed, seed_dev, cfg_scale, top_k, top_p, four_way, c_mask=None, c_img=None,
                        force_idx=None, trace: bool = False, mask_first: bool = True, more_smooth: bool = False, gumbel=None, draws=None, rows=None,
-                       forced=None, ad=None):
+                       forced=None, ad=None, score=None, score_only: bool = False):
         """the 10-scale loop on device-resident inputs only (capturable in a HIP graph: no host sync, static shapes).
         draws (sampler='torch'): the noise of each sampling call comes from the caller's torch generator (_TorchDraws).
         rows (per-request mode): device views (seed, top_k, top_p, coef [nstage][B][4]) of a _RequestTable; the sampling call of every scale
         is then the per-row one and cfg_scale / top_k / top_p / seed are not used.
         forced (region-constrained generation, with rows only): device (B, L) int32, the source id of every kept token and -1 elsewhere
         (ops.edit_force_table); the sampling launch of every scale then writes the kept ids itself (ops.cfg_sample_edit)
-        ad (per-request adapters, with rows only): (lora.bank_pack, device slot (R,) int32) handed to _ada and _blocks_and_head"""
+        ad (per-request adapters, with rows only): (lora.bank_pack, device slot (R,) int32) handed to _ada and _blocks_and_head
+        score (token log-probabilities, with rows only): device (logprob, entropy, rank, argmax) buffers (B, L); every scale then issues ONE more
+        launch (ops.score_rows) behind the sampling launch and the overwrites by force_idx / c_mask / c_img / the edit table: it scores the ids of
+        rows 0 .. B-1 - the sample f_hat[:B] returns - under this scale's combine weights rows[3][si] and writes this scale's columns
+        score_only (with score and force_idx, (n_draw B, l) int32 device ids per scale): no sampling launch at all - the score launch is the only
+        consumer of the logits, and the last scale's ids feed nothing"""
         if ad is not None and rows is None:
             raise ValueError('ad: the per-request path only (rows given)')
+        if score is not None and (rows is None or self.cfg.separator):
+            raise ValueError('score: the per-request path only (rows given), without separator tokens')
+        if score_only and (score is None or force_idx is None or trace):
+            raise ValueError('score_only: score buffers and force_idx are required')
         if forced is not None and (rows is None or four_way):
             raise ValueError('forced: the per-request joint path only (rows given, two branches)')
         cfg, P = self.cfg, self._pack()
@@ -1522,7 +1654,9 @@ class ControlVAR(nn.Module):
             mg = torch.empty(B, l, device=dev, dtype=torch.float32) if trace else None
             expo, g_si = self._torch_noise(draws, n_draw * B, l, more_smooth)
             soft = None
-            if forced is not None:
+            if score_only:
+                pass                                                     # nothing is drawn: the ids are force_idx's, taken below
+            elif forced is not None:
                 ops.cfg_sample_edit(logits, B, nrep, l, cfg.vocab, rows[3][si], rows[1], rows[2], rows[0], si, n_draw, idx, forced[:, py.begin[si]:py.end[si]],
                                     comb, mg, ldv=cfg.head_ld)
             elif rows is not None:
@@ -1546,6 +1680,12 @@ class ControlVAR(nn.Module):
                     idx[:3 * B, :pn * pn] = c_mask[si].to(device=dev, dtype=torch.int32).repeat(3, 1)
                 if c_img is not None:
                     idx[:3 * B, pn * pn:] = c_img[si].to(device=dev, dtype=torch.int32).repeat(3, 1)
+            if score is not None:
+                cols = slice(py.begin[si], py.end[si])
+                ops.score_rows(logits, B, nrep, l, cfg.vocab, rows[3][si], idx[:B], None, score[0][:, cols], score[1][:, cols], score[2][:, cols],
+                               score[3][:, cols], ldv=cfg.head_ld)
+                if score_only and si == nstage - 1:
+                    break
             if cfg.separator and py.sp(si):
                 # control_var.py:507-509: the ids drawn at the separator positions are dropped from the THIRD scale on; at the second scale
                 # upstream keeps all 10 ids and slices [:pn^2] / [-pn^2:], so the image half becomes ids 6..9 - replicated literally
@@ -1672,12 +1812,15 @@ class ControlVAR(nn.Module):
 
     @torch.no_grad()
     def _capture_per_request(self, B, four_way, labels_all, types_all, cfg, top_k, top_p, finish, teach=None, refresh=None, prologue=None,
-                             adapters: bool = False):
+                             adapters: bool = False, logprobs: bool = False, sampled=None):
         """per_request=True of the two graphed generators: capture the scale loop with the per-row sampler on a static _RequestTable and return
         run(label_B, cond_type[, given_half], g_seed=None, cfg=..., top_k=..., top_p=...).  refresh(given_half) validates the given half and
         returns the copy into its static buffer (conditional form); prologue() runs inside the graph before the scale loop.
         adapters=True: the adapter launches are captured over the attached bank, the slot of every sequence rides in the same static table,
-        and run takes adapter= (default: every row on the base model)"""
+        and run takes adapter= (default: every row on the base model)
+        logprobs=True: the score launch of every scale is captured too, the (B, L) score buffers are static outputs of the graph, and run
+        returns (images, TokenScores) - copies, as the images are.  sampled: the (L,) host pattern of the sampled tokens (None: all); an edit
+        graph (teach holds the forced-token table) reads it off that table instead"""
         dev, vocab, nstage = self.device, self.cfg.vocab, len(self.cfg.pyramid.patch_nums)
         nrep = 4 if four_way else 2
         slots0 = self._adapter_slots(-1, B, nrep) if adapters else None
@@ -1685,11 +1828,13 @@ class ControlVAR(nn.Module):
         tab_dev = table0.host.to(dev)
         rows = table0.views(tab_dev)
         ad = self._adapter_operands(table0, tab_dev)
+        score = _score_buffers(B, self.cfg.pyramid.L, dev) if logprobs else None
+        forced_tab = (teach or {}).get('forced')
 
         def body():
             if prologue is not None:
                 prologue()
-            return finish(self._generate_core(B, labels_all, types_all, 0, None, None, None, None, four_way, rows=rows, ad=ad, **(teach or {})))
+            return finish(self._generate_core(B, labels_all, types_all, 0, None, None, None, None, four_way, rows=rows, ad=ad, score=score, **(teach or {})))
 
         graph, out, owned = self._capture(body)
 
@@ -1713,6 +1858,9 @@ class ControlVAR(nn.Module):
                 copy_given()
             tab_dev.copy_(table.host)                       # seeds, top_k, top_p, every stage's weights and the adapter slots: one host-to-device copy
             graph.replay()
+            if logprobs:
+                return out.clone(), self._token_scores([t.clone() for t in score], True, sampled=sampled,
+                                                       forced=forced_tab.clone() if forced_tab is not None else None)
             return out.clone()
 
         if refresh is None:
@@ -1725,6 +1873,15 @@ class ControlVAR(nn.Module):
         run.owned = owned + ([ad[0]] if ad is not None else [])          # dropped together with the graph when `run` goes away
         return run
 
+    def _check_graph_logprobs(self, per_request: bool, logprobs: bool, four_way: bool):
+        """logprobs=True of the graphed generators: refused in words before anything is captured"""
+        if not logprobs:
+            return
+        if not per_request:
+            raise ValueError('logprobs=True needs per_request=True: the score launch reads the combine weights of the per-request table')
+        self._check_logprobs()
+        self._check_per_request(0, 0, four_way)
+
     def _check_graph_adapters(self, per_request: bool, adapters: bool):
         if not adapters:
             return
@@ -1734,7 +1891,8 @@ class ControlVAR(nn.Module):
             raise RuntimeError('adapters=True: no bank attached - call controlvar_amd.lora.attach_adapters(model, sources) first')
 
     @torch.no_grad()
-    def graphed_generator(self, B: int, cfg=1.5, top_k: int = 0, top_p: float = 0.0, per_request: bool = False, adapters: bool = False):
+    def graphed_generator(self, B: int, cfg=1.5, top_k: int = 0, top_p: float = 0.0, per_request: bool = False, adapters: bool = False,
+                          logprobs: bool = False):
         """Capture one full `autoregressive_infer_cfg` (10 scales x depth blocks + both VQVAE decodes, ~2.5k launches) in a
         HIP graph and return ``run(label_B, cond_type=None, g_seed=None) -> images``.  Labels, condition types and the
         sampling seed live in static device buffers that are refreshed before each replay, so every call draws new samples.
@@ -1743,10 +1901,13 @@ class ControlVAR(nn.Module):
         one copy refreshes, and ``run(label_B, cond_type, g_seed=None, cfg=..., top_k=..., top_p=...)`` takes each as a scalar or per row
         (those given here are its defaults) - one graph serves every mix of guidance scales, greedy beside sampled.  Row b of a replay is
         what autoregressive_infer_cfg(B, ...) gives in per-request mode; everything is validated on the host before a buffer is touched.
-        adapters=True (with per_request=True, on a model with an adapter bank): run also takes adapter=, one id per row or one int."""
+        adapters=True (with per_request=True, on a model with an adapter bank): run also takes adapter=, one id per row or one int.
+        logprobs=True (with per_request=True): the graph holds the score launches and the (B, L) score buffers, and run returns
+        (images, TokenScores) as autoregressive_infer_cfg(logprobs=True) does."""
         dev = self.device
         four_way = False
         self._check_graph_adapters(per_request, adapters)
+        self._check_graph_logprobs(per_request, logprobs, four_way)
         if self.sampler == 'torch':
             raise NotImplementedError("graphed_generator captures the counter sampler only: sampler='torch' draws its noise with torch on model.rng "
                                       "between the launches; set model.sampler = 'counter' to capture, or call autoregressive_infer_cfg")
@@ -1756,7 +1917,7 @@ class ControlVAR(nn.Module):
         ty0 = torch.zeros(B, dtype=torch.int64) if self.cfg.mask_factor == 2 else None
         labels_all, types_all = self._prepare_rows(B, lab0, ty0, four_way, 0)
         if per_request:
-            return self._capture_per_request(B, four_way, labels_all, types_all, cfg, top_k, top_p, self._decode_pair, adapters=adapters)
+            return self._capture_per_request(B, four_way, labels_all, types_all, cfg, top_k, top_p, self._decode_pair, adapters=adapters, logprobs=logprobs)
         seed_dev = torch.zeros(1, device=dev, dtype=torch.int64)
         graph, out, owned = self._capture(lambda: self._decode_pair(self._generate_core(B, labels_all, types_all, 0, seed_dev, cfg, top_k, top_p, four_way)))
 
@@ -1777,7 +1938,7 @@ class ControlVAR(nn.Module):
 
     @torch.no_grad()
     def graphed_conditional_generator(self, B: int, given: str = 'control', cfg=(1.5, 1.5, 1.5), top_k: int = 0, top_p: float = 0.0,
-                                      source: str = 'ids', decode: str = 'both', per_request: bool = False, adapters: bool = False):
+                                      source: str = 'ids', decode: str = 'both', per_request: bool = False, adapters: bool = False, logprobs: bool = False):
         """Capture one full `conditional_infer_cfg` in a HIP graph - control in, image out (given='control': the control ids are teacher-forced
         as `c_mask=`, the image is generated) or image in, control out (given='image', `c_img=`) - and return
         ``run(label_B, cond_type, given_half, g_seed=None) -> images``.
@@ -1790,10 +1951,12 @@ class ControlVAR(nn.Module):
         buffers refreshed before each replay.  more_smooth is not offered under capture; bidirectional models are captured as they are (the
         four-branch path never draws the order).
         per_request=True: as graphed_generator's - ``run(label_B, cond_type, given_half, g_seed=None, cfg=..., top_k=..., top_p=...)`` with each of
-        g_seed / cfg / top_k / top_p a scalar (cfg: one triple) or per row (cfg: (B, 3)); those given here are the defaults of run."""
+        g_seed / cfg / top_k / top_p a scalar (cfg: one triple) or per row (cfg: (B, 3)); those given here are the defaults of run.
+        logprobs=True (with per_request=True): run returns (images, TokenScores) as conditional_infer_cfg(logprobs=True) does."""
         if self.mask_factor != 2:
             raise NotImplementedError('graphed_conditional_generator needs mask_factor == 2 (control_var.py:333)')
         self._check_graph_adapters(per_request, adapters)
+        self._check_graph_logprobs(per_request, logprobs, True)
         if self.sampler == 'torch':
             raise NotImplementedError("graphed_conditional_generator captures the counter sampler only: sampler='torch' draws its noise with torch on "
                                       "model.rng between the launches; set model.sampler = 'counter' to capture, or call conditional_infer_cfg")
@@ -1867,7 +2030,8 @@ class ControlVAR(nn.Module):
                 return lambda: (pix_buf if pix_buf is not None else ids_buf).copy_(checked)
 
             run = self._capture_per_request(B, True, labels_all, types_all, cfg, top_k, top_p, finish, teach=teach, prologue=tokenise, refresh=refresh,
-                                            adapters=adapters)
+                                            adapters=adapters, logprobs=logprobs, sampled=self._sampled_pattern(True, *(
+                                                (ids_Bl, None) if given == 'control' else (None, ids_Bl)), None))
             run.ids = lambda: ids_buf.clone()
             return run
         graph, out, owned = self._capture(body)
@@ -1908,7 +2072,7 @@ class ControlVAR(nn.Module):
 
     @torch.no_grad()
     def edit_infer_cfg(self, B: int, label_B, cond_type, *, src_img=None, keep_img=None, src_ctrl=None, keep_ctrl=None, g_seed=None, cfg=1.5,
-                       top_k=0, top_p=0.0, trace: bool = False, more_smooth: bool = False, adapter=None) -> torch.Tensor:
+                       top_k=0, top_p=0.0, trace: bool = False, more_smooth: bool = False, adapter=None, logprobs: bool = False):
         """Region-constrained generation (an addition of this library): keep the source's tokens where a mask says "keep", sample the others in
         their context - in-painting, out-painting, editing under a control map (keep_ctrl=True, the image partly kept), or a consistent joint
         edit (the same region of both halves free).  Returns what autoregressive_infer_cfg returns.
@@ -1921,7 +2085,8 @@ class ControlVAR(nn.Module):
         g_seed / cfg / top_k / top_p: a scalar or one value per row, as in per-request mode (a scalar seed gives identical requests
         identical results).  label_B and cond_type are given per row.  trace=True leaves last_trace as _trace does, 'idx' holding the ids
         AFTER forcing, plus last_trace['forced'], the table.  more_smooth, sampler='torch', the two-pass separate_decoding branch and
-        separator models are refused.  adapter: one adapter id per row or one int, as in autoregressive_infer_cfg (lora.attach_adapters)."""
+        separator models are refused.  adapter: one adapter id per row or one int, as in autoregressive_infer_cfg (lora.attach_adapters).
+        logprobs=True: returns (images, TokenScores) as autoregressive_infer_cfg does; `sampled` is False at the kept tokens, which are scored too."""
         self._check_edit(label_B, cond_type, more_smooth)
         pns = self.cfg.pyramid.patch_nums
         s_ctrl, k_ctrl = _edit_half('ctrl', src_ctrl, keep_ctrl, B, pns, self.cfg.vocab) if self.cfg.mask_factor == 2 else (None, None)
@@ -1938,14 +2103,71 @@ class ControlVAR(nn.Module):
                                                                                                 (s_img, torch.int32), (k_img, torch.uint8))]
         forced = self._edit_table(B, *on_dev, mask_first)
         tab_dev = table.host.to(dev)
+        score = _score_buffers(B, self.cfg.pyramid.L, dev) if logprobs else None
         f_hat = self._generate_core(B, labels_all, types_all, 0, None, None, None, None, False, trace=trace, mask_first=mask_first, rows=table.views(tab_dev),
-                                    forced=forced, ad=self._adapter_operands(table, tab_dev))
+                                    forced=forced, ad=self._adapter_operands(table, tab_dev), score=score)
         if trace:
             self.last_trace['forced'] = forced
+        if logprobs:
+            return self._decode_pair(f_hat), self._token_scores(score, mask_first, forced=forced)
         return self._decode_pair(f_hat)
 
+    # ---- token log-probabilities of given tokens
     @torch.no_grad()
-    def graphed_edit_generator(self, B: int, source: str = 'ids', cfg=1.5, top_k=0, top_p=0.0, decode: str = 'both', adapters: bool = False):
+    def score_infer_cfg(self, B: int, label_B, cond_type, *, ids_img, ids_ctrl=None, given: Optional[str] = None, cfg=0.0, adapter=None,
+                        mask_first: bool = True) -> TokenScores:
+        """The likelihood of GIVEN tokens (an addition of this library): teacher-force the whole sample along its ids and score every token
+        under the distribution a generation would have drawn it from.  No sampling launch and no decoder pass is issued: per scale the
+        transformer, the head and one score launch (cvar_score_rows), the only consumer of the logits.  Returns a TokenScores whose `sampled`
+        is all False; the log-probabilities are those of the UNFILTERED CFG-combined distribution.
+        ids_img / ids_ctrl: each half's multi-scale ids, the list of (B, pn^2) tensors vae.img_to_idxBl returns (or one (B, sum pn^2) tensor).
+        given=None: the joint two-branch path of autoregressive_infer_cfg; total() is log p(control, image | label, type).
+        given='control' | 'image': the four-branch path of conditional_infer_cfg (mask_factor 2 only), cfg three numbers (or (B, 3)); all four
+        branch rows carry the given tokens, and total(half=<the other half>) is log p(other | given).
+        cfg = 0 scores under the conditional model alone; a per-row cfg scores under what a generation with that guidance draws from.
+        label_B and cond_type are given per row; adapter as in autoregressive_infer_cfg.  A bidirectional model takes the (control, image)
+        order as mask_first= here instead of drawing it.  Id range and shapes are checked on the host before any device work; more_smooth has
+        no meaning here, and sampler='torch', the two-pass separate_decoding branch and separator models are refused."""
+        if given not in (None, 'control', 'image'):
+            raise ValueError(f"given={given!r}: None (the joint path), 'control' or 'image'")
+        four_way, mf = given is not None, self.cfg.mask_factor
+        if four_way and mf != 2:
+            raise NotImplementedError("score_infer_cfg(given=...) needs mask_factor == 2, as conditional_infer_cfg (control_var.py:333)")
+        self._check_per_request(label_B, cond_type, four_way)
+        self._check_logprobs()
+        if not mask_first and (four_way or not self.bidirectional):
+            raise ValueError('mask_first=False: only a bidirectional model on the joint path (given=None) lays the image half first')
+        pns, vocab = self.cfg.pyramid.patch_nums, self.cfg.vocab
+        img = _score_ids('ids_img', ids_img, B, pns, vocab)
+        if mf == 2:
+            if ids_ctrl is None:
+                raise ValueError('ids_ctrl: the control half is scored too (given= says which half conditions the other) - pass its ids')
+            ctrl = _score_ids('ids_ctrl', ids_ctrl, B, pns, vocab)
+        elif ids_ctrl is not None:
+            raise ValueError('ids_ctrl: a plain VAR has the image half only')
+        if four_way and _host_array(cfg).ndim == 0:
+            cfg = (cfg,) * 3
+        nrep = 4 if four_way else 2
+        table = _request_table(B, cfg, 0, 0.0, 0, four_way, vocab, len(pns), slots=self._adapter_slots(adapter, B, nrep))
+        self._pack(check=True); self.vae_proxy[0]._pack(check=True)
+        labels_all, types_all = self._prepare_rows(B, label_B, cond_type, four_way, 0)
+        dev = self.device
+        halves = [img] if mf == 1 else ([ctrl, img] if mask_first else [img, ctrl])
+        halves = [h.to(device=dev, dtype=torch.int32) for h in halves]
+        force, o = [], 0
+        for pn in pns:
+            ids = torch.cat([h[:, o:o + pn * pn] for h in halves], dim=1)
+            force.append((ids.repeat(4, 1) if four_way else ids).contiguous())
+            o += pn * pn
+        score = _score_buffers(B, self.cfg.pyramid.L, dev)
+        tab_dev = table.host.to(dev)
+        self._generate_core(B, labels_all, types_all, 0, None, None, None, None, four_way, force_idx=force, mask_first=mask_first, rows=table.views(tab_dev),
+                            ad=self._adapter_operands(table, tab_dev), score=score, score_only=True)
+        return self._token_scores(score, mask_first, sampled=torch.zeros(self.cfg.pyramid.L, dtype=torch.bool))
+
+    @torch.no_grad()
+    def graphed_edit_generator(self, B: int, source: str = 'ids', cfg=1.5, top_k=0, top_p=0.0, decode: str = 'both', adapters: bool = False,
+                               logprobs: bool = False):
         """Capture one full `edit_infer_cfg` in a HIP graph and return
         ``run(label_B, cond_type, *, src_img=None, keep_img=None, src_ctrl=None, keep_ctrl=None, g_seed=None, cfg=..., top_k=..., top_p=...) -> images``.
         The keep masks (uint8, all zero = nothing kept), the sources and the request table live in static device buffers refreshed before each
@@ -1956,7 +2178,7 @@ class ControlVAR(nn.Module):
         decode='both': what edit_infer_cfg returns; decode='generated': the image map only, (B, 3, H, H), one decoder pass of B images.
         cfg / top_k / top_p given here are the defaults of run; each and g_seed is a scalar or per row.  Everything is validated on the host
         before the first static buffer is written: a refused run leaves the graph as it was.  Bidirectional models are refused as
-        graphed_generator refuses them."""
+        graphed_generator refuses them.  logprobs=True: run returns (images, TokenScores) as edit_infer_cfg(logprobs=True) does."""
         if self.sampler == 'torch':
             raise NotImplementedError("graphed_edit_generator captures the counter sampler only: sampler='torch' draws its noise with torch on model.rng "
                                       "between the launches; set model.sampler = 'counter' to capture")
@@ -2007,7 +2229,7 @@ class ControlVAR(nn.Module):
             return copy
 
         inner = self._capture_per_request(B, False, labels_all, types_all, cfg, top_k, top_p, finish, teach={'forced': forced}, refresh=refresh,
-                                          prologue=prologue, adapters=adapters)
+                                          prologue=prologue, adapters=adapters, logprobs=logprobs)
 
         if mf == 2:
             def run(label_B, cond_type, *, src_img=None, keep_img=None, src_ctrl=None, keep_ctrl=None, g_seed=None, cfg=cfg, top_k=top_k, top_p=top_p,
@@ -2037,24 +2259,32 @@ class ControlVAR(nn.Module):
     # ---- public API
     @torch.no_grad()
     def autoregressive_infer_cfg(self, B: int, label_B, g_seed: Optional[int] = None, cfg=1.5, top_k=0, top_p=0.0,
-                                 more_smooth=False, cond_type=None, _force_idx=None, _trace=False, _gumbel=None, adapter=None) -> torch.Tensor:
+                                 more_smooth=False, cond_type=None, _force_idx=None, _trace=False, _gumbel=None, adapter=None, logprobs: bool = False):
         """control_var.py:356-565: returns (B, 3, 2 H, H) in [0,1] with H = 16 patch_nums[-1] - (B, 3, 512, 256) for the default list, (B, 3, 1024, 512) for
         PATCH_NUMS_512 (control image on top, RGB below).
         more_smooth: Gumbel-softmax soft code embeddings (:511-515); `_gumbel` (tests) injects the per-pass noise instead of drawing it.
         adapter (an addition of this library, lora.attach_adapters): one adapter id per row, or one int; -1 = the base model.  Selects the
-        per-request path, as a per-row cfg does."""
-        f_hat = self._generate(B, label_B, g_seed, cfg, top_k, top_p, more_smooth, cond_type, False, None, None, _force_idx, _trace, _gumbel, adapter=adapter)
-        return self._decode_pair(f_hat)
+        per-request path, as a per-row cfg does.
+        logprobs=True (an addition of this library): returns (images, scores), scores a TokenScores - log-probability, entropy and rank of every
+        token of the returned sample and the greedy id beside it, (B, L) each, from one more launch per scale (cvar_score_rows).  The
+        log-probabilities are those of the UNFILTERED CFG-combined distribution: the top-k / top-p kept set is not renormalised over.  Selects the
+        per-request path as adapter= does (scalars are broadcast), so its refusals apply; ids and images are bit-identical with and without it."""
+        out = self._generate(B, label_B, g_seed, cfg, top_k, top_p, more_smooth, cond_type, False, None, None, _force_idx, _trace, _gumbel, adapter=adapter,
+                             logprobs=logprobs)
+        return (self._decode_pair(out[0]), out[1]) if logprobs else self._decode_pair(out)
 
     @torch.no_grad()
     def conditional_infer_cfg(self, B: int, label_B, g_seed: Optional[int] = None, cfg=(1.5, 1.5, 1.5), top_k=0, top_p=0.0,
                               more_smooth=False, cond_type=None, c_mask=None, c_img=None, _force_idx=None, _trace=False, _gumbel=None,
-                              adapter=None) -> torch.Tensor:
-        """control_var.py:223-354: 4-branch CFG with teacher forcing of the control (c_mask) or image (c_img) ids."""
+                              adapter=None, logprobs: bool = False):
+        """control_var.py:223-354: 4-branch CFG with teacher forcing of the control (c_mask) or image (c_img) ids.
+        logprobs=True: returns (images, TokenScores) as autoregressive_infer_cfg does (the unfiltered combined distribution of the four branches;
+        tokens in control-first order); `sampled` is False along the teacher-forced half, which is scored too."""
         if self.mask_factor != 2:
             raise NotImplementedError('conditional_infer_cfg needs mask_factor == 2 (control_var.py:333)')
-        f_hat = self._generate(B, label_B, g_seed, cfg, top_k, top_p, more_smooth, cond_type, True, c_mask, c_img, _force_idx, _trace, _gumbel, adapter=adapter)
-        return self._decode_pair(f_hat)
+        out = self._generate(B, label_B, g_seed, cfg, top_k, top_p, more_smooth, cond_type, True, c_mask, c_img, _force_idx, _trace, _gumbel, adapter=adapter,
+                             logprobs=logprobs)
+        return (self._decode_pair(out[0]), out[1]) if logprobs else self._decode_pair(out)
 
     def forward(self, label_B: torch.LongTensor, x_BLCv_wo_first_l: torch.Tensor, cond_type=None, mask_first=True) -> torch.Tensor:
         """control_var.py:568-651 teacher-forced logits (B, L, V) fp32.  Under autograd (grad mode on and trainable
@@ -2120,17 +2350,23 @@ class VAR(ControlVAR):
 
     @torch.no_grad()
     def autoregressive_infer_cfg(self, B: int, label_B, g_seed: Optional[int] = None, cfg=1.5, top_k=0, top_p=0.0,
-                                 more_smooth=False, _force_idx=None, _trace=False, adapter=None) -> torch.Tensor:
-        """var.py:143-207: returns (B, 3, H, H) in [0,1], H = 16 patch_nums[-1] (256, or 512 with PATCH_NUMS_512)."""
-        f_hat = self._generate(B, label_B, g_seed, cfg, top_k, top_p, more_smooth, None, False, None, None, _force_idx, _trace, adapter=adapter)
-        return self._decode_pair(f_hat)
+                                 more_smooth=False, _force_idx=None, _trace=False, adapter=None, logprobs: bool = False):
+        """var.py:143-207: returns (B, 3, H, H) in [0,1], H = 16 patch_nums[-1] (256, or 512 with PATCH_NUMS_512).
+        logprobs=True: (images, TokenScores), as ControlVAR.autoregressive_infer_cfg."""
+        out = self._generate(B, label_B, g_seed, cfg, top_k, top_p, more_smooth, None, False, None, None, _force_idx, _trace, adapter=adapter, logprobs=logprobs)
+        return (self._decode_pair(out[0]), out[1]) if logprobs else self._decode_pair(out)
 
     @torch.no_grad()
     def edit_infer_cfg(self, B: int, label_B, *, src_img=None, keep_img=None, g_seed=None, cfg=1.5, top_k=0, top_p=0.0, trace: bool = False,
-                       more_smooth: bool = False, adapter=None) -> torch.Tensor:
+                       more_smooth: bool = False, adapter=None, logprobs: bool = False):
         """ControlVAR.edit_infer_cfg for the one half a plain VAR has: returns (B, 3, H, H) as autoregressive_infer_cfg"""
         return super().edit_infer_cfg(B, label_B, None, src_img=src_img, keep_img=keep_img, g_seed=g_seed, cfg=cfg, top_k=top_k, top_p=top_p, trace=trace,
-                                      more_smooth=more_smooth, adapter=adapter)
+                                      more_smooth=more_smooth, adapter=adapter, logprobs=logprobs)
+
+    @torch.no_grad()
+    def score_infer_cfg(self, B: int, label_B, *, ids_img, cfg=0.0, adapter=None) -> 'TokenScores':
+        """ControlVAR.score_infer_cfg for the one half a plain VAR has"""
+        return super().score_infer_cfg(B, label_B, None, ids_img=ids_img, cfg=cfg, adapter=adapter)
 
     def conditional_infer_cfg(self, *a, **k):
         raise NotImplementedError('plain VAR has no conditional_infer_cfg (var.py)')

@@ -296,6 +296,38 @@ def cfg_sample_edit(logits: torch.Tensor, B: int, nrep: int, l: int, V: int, coe
     return idx_out
 
 
+def score_rows(logits: torch.Tensor, B: int, nrep: int, l: int, V: int, coef: torch.Tensor, target: torch.Tensor,
+               combined: Optional[torch.Tensor] = None, logprob: Optional[torch.Tensor] = None, entropy: Optional[torch.Tensor] = None,
+               rank: Optional[torch.Tensor] = None, argmax: Optional[torch.Tensor] = None, ldv: int = 0):
+    """Score a given id per token under the CFG-combined distribution (cvar_score_rows, include/cvar_serve.h).  coef (B, 4) float32, the
+    sampler's table of this stage; target: (B, l) int32 on the device of `logits`, unit stride along the tokens - a column slice of a wider
+    table will do (its row stride is handed on as ldt); < 0: no target (logprob 0, rank -1).  Outputs, each optional but not all None:
+    combined (B, l, V) float32 contiguous; logprob / entropy float32 and rank / argmax int32, each (B, l) with unit stride along the tokens
+    and ONE row stride for the four (handed on as ldo): the columns of one scale in (B, L) buffers will do.
+    The log-probabilities are those of the unfiltered combined distribution; a top-k / top-p kept set is not renormalised over."""
+    dev = logits.device
+    if coef is not None and (not torch.is_tensor(coef) or coef.dtype != torch.float32 or tuple(coef.shape) != (B, 4) or not coef.is_contiguous()
+                             or coef.device != dev):
+        raise ValueError(f'score_rows: coef must be a contiguous float32 {(B, 4)} tensor on {dev}')
+
+    def row_stride(name, t, dtype):
+        if (not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != (B, l) or t.stride(1) != 1 or (B > 1 and t.stride(0) < l) or t.device != dev):
+            raise ValueError(f'score_rows: {name} must be {"an" if dtype == torch.int32 else "a"} {str(dtype)[6:]} ({B}, {l}) tensor on {dev} with unit stride '
+                             'along the tokens')
+        return t.stride(0) if B > 1 else max(t.stride(0), l)
+
+    ldt = row_stride('target', target, torch.int32) if target is not None else 0
+    if combined is not None and (not torch.is_tensor(combined) or combined.dtype != torch.float32 or tuple(combined.shape) != (B, l, V)
+                                 or not combined.is_contiguous() or combined.device != dev):
+        raise ValueError(f'score_rows: combined must be a contiguous float32 ({B}, {l}, {V}) tensor on {dev}')
+    ldo = {row_stride(name, t, dtype) for name, t, dtype in (('logprob', logprob, torch.float32), ('entropy', entropy, torch.float32),
+                                                             ('rank', rank, torch.int32), ('argmax', argmax, torch.int32)) if t is not None}
+    if len(ldo) > 1:
+        raise ValueError(f'score_rows: logprob / entropy / rank / argmax must share one row stride, got {sorted(ldo)}')
+    check(_lib.load().cvar_score_rows(_ptr(logits), B, nrep, l, V, _ptr(coef), _ptr(target), int(ldt), _ptr(combined), _ptr(logprob), _ptr(entropy),
+                                      _ptr(rank), _ptr(argmax), int(ldo.pop()) if ldo else 0, int(ldv), _stream()), 'cvar_score_rows')
+
+
 def edit_force_table(keep_ctrl: Optional[torch.Tensor], keep_img: Optional[torch.Tensor], src_ctrl: Optional[torch.Tensor],
                      src_img: Optional[torch.Tensor], patch_nums: Sequence[int], B: int, mask_first: bool, mask_factor: int, forced: torch.Tensor):
     """The forced-token table of every scale in one launch (cvar_edit_force_table, include/cvar_serve.h).  keep_*: (B, S, S) uint8 or None,

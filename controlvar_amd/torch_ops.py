@@ -410,6 +410,26 @@ _define('cfg_sample_edit', '(Tensor logits, int B, int nrep, Tensor coef, Tensor
         lambda logits, B, nrep, coef, top_k, top_p, seed, stage, forced, n_draw=1: logits.new_empty(n_draw * B, logits.shape[1], dtype=torch.int32))
 
 
+def _score_rows(logits, B, nrep, coef, target):
+    """token log-probabilities (include/cvar_serve.h): logits (nrep*B, l, V) fp32, coef (B, 4) fp32 (this stage's weights, the sampler's table),
+    target (B, l) int32 (a column slice of a wider table will do; < 0: no target) -> (logprob, entropy) fp32 and (rank, argmax) int32, each
+    (B, l), under the unfiltered CFG-combined distribution"""
+    if logits.dtype != torch.float32 or logits.dim() != 3 or logits.shape[0] != nrep * B:
+        raise ValueError('score_rows: logits must be float32 (nrep*B, l, V)')
+    _, l, V = logits.shape
+    lp, en = (torch.empty(B, l, device=logits.device, dtype=torch.float32) for _ in range(2))
+    rk, am = (torch.empty(B, l, device=logits.device, dtype=torch.int32) for _ in range(2))
+    K.score_rows(logits.contiguous(), B, nrep, l, V, coef, target, None, lp, en, rk, am)
+    return lp, en, rk, am
+
+
+_define('score_rows', '(Tensor logits, int B, int nrep, Tensor coef, Tensor target) -> (Tensor, Tensor, Tensor, Tensor)',
+        _score_rows,
+        lambda logits, B, nrep, coef, target: (logits.new_empty(B, logits.shape[1]), logits.new_empty(B, logits.shape[1]),
+                                                logits.new_empty(B, logits.shape[1], dtype=torch.int32),
+                                                logits.new_empty(B, logits.shape[1], dtype=torch.int32)))
+
+
 def _edit_force_table(src_img, keep_img, src_ctrl, keep_ctrl, patch_nums, mask_first=True, mask_factor=2):
     """keep masks (B, S, S) uint8 at latent resolution + multi-scale source ids (B, sum pn^2) int32 -> the forced-token table
     (B, mask_factor * sum pn^2) int32 of every scale in one launch: the source id where the cell rule keeps the token, -1 where it is free"""

@@ -3,7 +3,8 @@
  *
  * The functions live in the same libcvar_hip.so as those of cvar.h.  They are versioned on their own: cvar_serve_version() bumps on
  * any signature change in THIS header, cvar_abi_version() stays the version of cvar.h.  Adding an entry point changes no signature and
- * leaves the version alone: cvar_edit_force_table, cvar_cfg_sample_edit and cvar_lora_down_rows joined at version 1.
+ * leaves the version alone: cvar_edit_force_table, cvar_cfg_sample_edit, cvar_lora_down_rows and
+ * cvar_score_rows joined at version 1.
  */
 #ifndef CVAR_SERVE_H
 #define CVAR_SERVE_H
@@ -92,6 +93,33 @@ int cvar_cfg_sample_edit(const float* logits, int B, int nrep, int l, int V,
 int cvar_lora_down_rows(const void* x, int64_t ldx, const void* A_bank, int64_t lda, const float* scale /* [n_slots] */,
                         const int32_t* slot /* [R] */, int n_slots, int R, int l, void* xa, int64_t ldxa, int kpad,
                         void* x_copy, int64_t ld_copy, int K, int dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Token log-probabilities: score a GIVEN id per token under the CFG-combined distribution the sampler draws from.  Joined at version 1.
+ * One workgroup per token (b, t), in the shape of cvar_cfg_sample_rows, and with its inputs:
+ *   logits [nrep*B][l][ldv] fp32, B, nrep 1..4, l, V <= 4096, ldv (0: V; otherwise >= V);
+ *   coef   [B][4] fp32   the device table of THIS stage - the very table the sampler reads;
+ *   target [B][ldt] int32, ldt >= l: token (b, t) reads target[b * ldt + t] (a column slice of a wider table will do).
+ * Outputs, each optional (all five NULL: CVAR_EINVAL), x = the combined row of the token, t_id = its target.  The four per-token outputs
+ * share the row stride ldo (0: l; otherwise >= l): token (b, t) is written at b * ldo + t, so one scale's columns of [B][L] buffers will do.
+ *   combined [B][l][V] fp32  ((c0 l0 + c1 l1) + c2 l2) + c3 l3 with separately rounded products: the sampler's `combined`, bit for bit (one text);
+ *   logprob  [B][l]    fp32  (x_t - m) - logf(S), m = the row maximum, S = sum_e expf(x_e - m) (accurate expf / logf, no fast-math);
+ *   entropy  [B][l]    fp32  logf(S) - (sum_e expf(x_e - m) (x_e - m)) / S; terms with expf(...) == 0 are skipped, so a -inf logit carries
+ *                            zero mass and produces no NaN;
+ *   rank     [B][l]    int32 the number of codes e with x_e > x_t, or x_e == x_t and e < t_id: rank 0 is exactly the greedy kernel's id
+ *                            (the lowest index on ties);
+ *   argmax   [B][l]    int32 the id cvar_cfg_sample gives that token at top_k = 1.
+ * The distribution is the UNFILTERED combined one: a top-k / top-p kept set is not renormalised over.
+ * target < 0: the token has no target - logprob = 0 and rank = -1; entropy, argmax and combined are written as usual.
+ * The order of evaluation is fixed and independent of B and of the slot b: thread tid of 256 owns elements tid + 256 j, j = 0..15, and adds
+ * them in increasing j; a 64-lane xor-shuffle tree follows; the four wave partials are added in order 0..3.  No atomics: row b of a call
+ * equals the B = 1 call on that row, bit for bit.
+ * Out of contract: target values >= V (the caller checks its ids; the kernel reads nothing for them and treats them as "no target"),
+ * NaN logits, and rows whose maximum is not finite.
+ * nrep outside 1..4 or V > 4096: CVAR_EUNSUPPORTED; a NULL logits / coef / target, ldt < l, 0 < ldo < l, V < 1, 0 < ldv < V: CVAR_EINVAL. */
+int cvar_score_rows(const float* logits, int B, int nrep, int l, int V, const float* coef /* [B][4] */,
+                    const int32_t* target /* [B][ldt] */, int ldt, float* combined, float* logprob, float* entropy,
+                    int32_t* rank, int32_t* argmax, int ldo, int ldv, void* stream);
 
 #ifdef __cplusplus
 }
