@@ -133,9 +133,11 @@ __global__ __launch_bounds__(256) void cfg_greedy_kernel(const SampleParams p) {
 // cut keeps the elements whose ascending cumulative probability exceeds 1-p, i.e. v >= tau_p.  Each threshold is found
 // by a 4-pass byte-wise radix select over order-preserving integer keys (count histogram for top-k, probability-mass
 // histogram for top-p).  Masses are quantised to 2^-40 and accumulated as 64-bit integers: exact, order independent,
-// bit-reproducible.  The draw is an inverse-CDF lookup over the kept elements in a fixed (thread-major) order.
-__device__ __forceinline__ unsigned f2key(float f) {           // monotone: a < b  <=>  key(a) < key(b)
-    const unsigned u = __float_as_uint(f);
+// bit-reproducible.  The draw is an inverse-CDF lookup over the kept elements in a fixed (thread-major) order: ascending (e mod 256, e div 256).
+// A mass below 2^-40 of the maximum's quantises to zero: such a token is never drawn and is not counted in `kept` (the sampler's contract).
+__device__ __forceinline__ unsigned f2key(float f) {           // monotone: a < b  <=>  key(a) < key(b), and a == b  <=>  key(a) == key(b):
+    unsigned u = __float_as_uint(f);                           // -0.0 takes the key of +0.0 (they compare equal: a tie with the cut is kept)
+    if (u == 0x80000000u) u = 0u;
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 

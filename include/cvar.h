@@ -204,6 +204,10 @@ int cvar_cos_qk_norm_bwd(const void* qkv, void* dqkv, int dtype, int R, int H, i
  * top-p filtering as the reference, then one draw per row of `n_draw` independent rows from a counter-based
  * generator keyed by (seed, stage, row).  idx_out: [n_draw*B][l] int32.  Optional outputs (may be NULL):
  * combined [B][l][V] fp32, margin [B][l] fp32 (top1 - top2 of the combined logits), kept [B][l] int32.
+ * kept = the number of tokens the draw can return: the top-k / top-p survivors (value thresholds, ties kept, -0.0 == +0.0) whose mass is
+ *   not zero.  Masses are multiples of 2^-40 of the maximum's, rounded down: a token more than 40 ln 2 = 27.73 nats below the row maximum
+ *   (a -inf logit included) has mass zero, is never drawn and is NOT counted - without any filter kept < V on such a row (DESIGN.md section 2,
+ *   "The counter sampler's contract").
  * ldv: row stride of `logits` in floats (0 = V): a head with extra columns behind the V codes (`separator`, control_var.py:202,504).
  * more_smooth (control_var.py:326-330,459-463,511-515; helpers.py:22-36), sampling mode only: with soft_out != NULL also
  *   soft_out[d*B + b][t][:] = softmax_v((combined_v * smooth_mul + g_v) / smooth_tau) . codebook[v][:]  over the top-k / top-p KEPT v
