@@ -11,7 +11,7 @@ scale step runs as a short sequence of fused kernels.  There is no CPU / eager f
 from __future__ import annotations
 
 import math
-from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
+from typing import Any, Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -924,19 +924,30 @@ def _score_buffers(B: int, L: int, dev):
             torch.empty(B, L, device=dev, dtype=torch.int32), torch.empty(B, L, device=dev, dtype=torch.int32))
 
 
-def _score_ids(name: str, ids, B: int, pns, vocab: int) -> torch.Tensor:
-    """one half's ids of a scoring request, checked on the host -> flat integer ids (B, sum pn^2) on the device they came on"""
+def _flat_ids(name: str, ids, B: int, pns, vocab: int, range_name: Optional[str] = None) -> torch.Tensor:
+    """one half's multi-scale ids as every entry point takes them - the list of (B, pn^2) tensors img_to_idxBl returns or one (B, sum pn^2)
+    tensor -, checked on the host -> flat integer ids (B, sum pn^2) on the device they came on"""
     Lsrc = sum(pn * pn for pn in pns)
     if isinstance(ids, (list, tuple)):
         want = [(B, pn * pn) for pn in pns]
         if not all(torch.is_tensor(t) for t in ids) or [tuple(t.shape) for t in ids] != want:
             raise ValueError(f'{name}: expected {len(pns)} id tensors of shapes {want} (what img_to_idxBl returns)')
+        if any(t.is_floating_point() or t.dtype == torch.bool for t in ids):
+            raise ValueError(f'{name}: expected integer ids')
         ids = torch.cat([t.to(ids[0].device) for t in ids], dim=1)
     if not torch.is_tensor(ids) or tuple(ids.shape) != (B, Lsrc) or ids.is_floating_point() or ids.dtype == torch.bool:
         raise ValueError(f'{name}: expected integer ids of shape ({B}, {Lsrc}) or a list of (B, pn * pn) tensors, got '
                          f'{tuple(ids.shape) if torch.is_tensor(ids) else type(ids).__name__}')
-    _check_index_range(ids, 0, vocab - 1, name)
+    _check_index_range(ids, 0, vocab - 1, range_name or name)
     return ids
+
+
+def _pixels(name: str, px, want) -> torch.Tensor:
+    """one half given as pixels, checked on the host"""
+    if not torch.is_tensor(px) or tuple(px.shape) != tuple(want) or not px.is_floating_point():
+        raise ValueError(f'{name}: expected pixels of shape {tuple(want)} (floating point, in [-1, 1]), got '
+                         f'{tuple(px.shape) if torch.is_tensor(px) else type(px).__name__}')
+    return px
 
 
 # ---- region-constrained generation (an addition of this library; include/cvar_serve.h) --------------------------------------------
@@ -961,7 +972,7 @@ def _edit_half(half: str, src, keep, B: int, pns, vocab: int, pixels: bool = Fal
     """one half (img / ctrl) of an edit request, checked on the host -> (source or None, keep mask (B, S, S) uint8 or None).  The source is
     returned as flat integer ids (B, sum pn^2) - or, with pixels=True, as the (B, 3, 16 S, 16 S) pixels it was given as -, on the device it
     came on.  keep: True keeps the whole half, None nothing.  A mask without a source is a ValueError; a source without a mask is unused."""
-    S, Lsrc = pns[-1], sum(pn * pn for pn in pns)
+    S = pns[-1]
     if keep is None:
         mask = None
     elif keep is True:
@@ -976,23 +987,40 @@ def _edit_half(half: str, src, keep, B: int, pns, vocab: int, pixels: bool = Fal
             raise ValueError(f'keep_{half} is given without src_{half}: there is nothing to keep')
         return None, None
     if pixels:
-        want = (B, 3, 16 * S, 16 * S)
-        if not torch.is_tensor(src) or tuple(src.shape) != want or not src.is_floating_point():
-            raise ValueError(f'src_{half}: expected pixels of shape {want} (floating point, in [-1, 1]), got '
-                             f'{tuple(src.shape) if torch.is_tensor(src) else type(src).__name__}')
-        return src, mask
-    if isinstance(src, (list, tuple)):
-        want = [(B, pn * pn) for pn in pns]
-        if not all(torch.is_tensor(t) for t in src) or [tuple(t.shape) for t in src] != want:
-            raise ValueError(f'src_{half}: expected {len(pns)} id tensors of shapes {want} (what img_to_idxBl returns)')
-        if any(t.is_floating_point() or t.dtype == torch.bool for t in src):
-            raise ValueError(f'src_{half}: expected integer ids')
-        src = torch.cat([t.to(src[0].device) for t in src], dim=1)
-    if not torch.is_tensor(src) or tuple(src.shape) != (B, Lsrc) or src.is_floating_point() or src.dtype == torch.bool:
-        raise ValueError(f'src_{half}: expected integer ids of shape ({B}, {Lsrc}) or a list of (B, pn * pn) tensors, got '
-                         f'{tuple(src.shape) if torch.is_tensor(src) else type(src).__name__}')
-    _check_index_range(src, 0, vocab - 1, f'src_{half}')
-    return src, mask
+        return _pixels(f'src_{half}', src, (B, 3, 16 * S, 16 * S)), mask
+    return _flat_ids(f'src_{half}', src, B, pns, vocab), mask
+
+
+class _ScalarDraw(NamedTuple):
+    """how the scale loops draw a scale on the scalar path: one cfg (a triple on the four-branch path), top_k, top_p and seed for the batch.
+    seed_dev: the seed as a device scalar (graphs).  draws (sampler='torch'): the noise of each sampling call comes from the caller's
+    torch generator (_TorchDraws).  gumbel (tests): the per-pass noise of more_smooth, injected instead of drawn."""
+    cfg: Any
+    top_k: int
+    top_p: float
+    seed: int
+    seed_dev: Optional[torch.Tensor] = None
+    more_smooth: bool = False
+    gumbel: Any = None
+    draws: Any = None
+
+
+class _RowDraw(NamedTuple):
+    """... and in per-request mode: rows, the device views (seed, top_k, top_p, coef [nstage][B][4]) of a _RequestTable; the sampling call of
+    every scale is then the per-row one.
+    forced (region-constrained generation): device (B, L) int32, the source id of every kept token and -1 elsewhere (ops.edit_force_table);
+    the sampling launch of every scale then writes the kept ids itself (ops.cfg_sample_edit)
+    ad (per-request adapters): (lora.bank_pack, device slot (R,) int32) handed to _ada and _blocks_and_head
+    score (token log-probabilities): device (logprob, entropy, rank, argmax) buffers (B, L); every scale then issues ONE more launch
+    (ops.score_rows) behind the sampling launch and the overwrites by force_idx / c_mask / c_img / the edit table: it scores the ids of rows
+    0 .. B-1 - the sample f_hat[:B] returns - under this scale's combine weights rows[3][si] and writes this scale's columns
+    sample=False (score_infer_cfg; with score and force_idx, (n_draw B, l) int32 device ids per scale): no sampling launch at all - the score
+    launch is the only consumer of the logits, and the last scale's ids feed nothing"""
+    rows: Any
+    forced: Optional[torch.Tensor] = None
+    ad: Any = None
+    score: Any = None
+    sample: bool = True
 
 
 class ControlVAR(nn.Module):
@@ -1481,28 +1509,38 @@ class ControlVAR(nn.Module):
             if ids is not None:
                 _check_index_range(torch.cat([t.reshape(-1) for t in ids]), 0, self.cfg.vocab - 1, name)
         labels_all, types_all = self._prepare_rows(B, label_B, cond_type, four_way, seed)
-        mask_first = True
-        if self.cfg.mask_factor == 2 and not four_way:
-            # control_var.py:403: python's global `random`, drawn on every call (before the `or`), exactly as upstream -
-            # random.seed(k) before the call reproduces the reference's choice of order
-            import random
-            mask_first = True if (random.random() < 0.5 or not self.bidirectional) else False
+        mask_first = self._draw_order(four_way)
         if self.cfg.separator and (four_way or more_smooth or (self.cfg.separate_decoding and not self.cfg.indep)):
             raise NotImplementedError('separator: conditional_infer_cfg ignores the special tokens (control_var.py:270-330), the two-pass branch fails with a '
                                       'shape error (:481) and more_smooth slices the soft embeddings at shifted positions upstream; only forward(), training '
                                       'and the joint autoregressive_infer_cfg branch are built')
+        how = _ScalarDraw(cfg_scale, top_k, top_p, seed, more_smooth=bool(more_smooth), gumbel=gumbel, draws=draws)
         if self.cfg.separate_decoding and not self.cfg.indep and not four_way:              # control_var.py:428-485
-            f_hat = self._generate_two_pass(B, labels_all, types_all, seed, cfg_scale, top_k, top_p, bool(more_smooth), force_idx, trace, mask_first,
-                                            gumbel, draws=draws)
+            f_hat = self._generate_two_pass(B, labels_all, types_all, how, force_idx, trace, mask_first)
         else:
-            f_hat = self._generate_core(B, labels_all, types_all, seed, None, cfg_scale, top_k, top_p, four_way, c_mask, c_img, force_idx, trace,
-                                        mask_first=mask_first, more_smooth=bool(more_smooth), gumbel=gumbel, draws=draws)
+            f_hat = self._generate_core(B, labels_all, types_all, four_way, how, c_mask, c_img, force_idx, trace, mask_first)
         if draws is not None:
             draws.finish()
         return f_hat
 
+    def _draw_order(self, four_way: bool) -> bool:
+        """mask_first of one call: is the control half laid first?"""
+        if self.cfg.mask_factor != 2 or four_way:
+            return True
+        # control_var.py:403: python's global `random`, drawn on every call (before the `or`), exactly as upstream -
+        # random.seed(k) before the call reproduces the reference's choice of order
+        import random
+        return True if (random.random() < 0.5 or not self.bidirectional) else False
+
     def _check_per_request(self, label_B, cond_type, four_way, more_smooth=False):
         """what per-request mode does not offer, said on the host before any device work"""
+        self._check_per_request_mode(four_way, more_smooth)
+        if label_B is None or (self.cfg.mask_factor == 2 and cond_type is None):
+            raise ValueError('per-request sampling parameters: label_B' + (' and cond_type' if self.cfg.mask_factor == 2 else '') + ' must be given per row - '
+                             'None draws them from the one batch seed of the scalar path, which a batch of requests does not have')
+
+    def _check_per_request_mode(self, four_way, more_smooth=False):
+        """... the part that does not depend on the request"""
         if more_smooth:
             raise NotImplementedError('per-request sampling parameters: more_smooth is not offered (the soft-embedding kernel has no per-row form); pass '
                                       'scalar cfg / top_k / top_p / g_seed, or more_smooth=False')
@@ -1512,9 +1550,6 @@ class ControlVAR(nn.Module):
         if self.cfg.separate_decoding and not self.cfg.indep and not four_way:
             raise NotImplementedError('per-request sampling parameters: the two-pass separate_decoding branch (control_var.py:428-485) is not offered; '
                                       'pass scalar cfg / top_k / top_p / g_seed')
-        if label_B is None or (self.cfg.mask_factor == 2 and cond_type is None):
-            raise ValueError('per-request sampling parameters: label_B' + (' and cond_type' if self.cfg.mask_factor == 2 else '') + ' must be given per row - '
-                             'None draws them from the one batch seed of the scalar path, which a batch of requests does not have')
 
     @torch.no_grad()
     def _adapter_slots(self, adapter, B: int, nrep: int):
@@ -1525,13 +1560,6 @@ class ControlVAR(nn.Module):
         if not lora.has_adapters(self):
             raise RuntimeError('adapter=: no bank attached - call controlvar_amd.lora.attach_adapters(model, sources) first')
         return lora.sequence_slots(lora.adapter_ids(adapter, B, self._adapter_bank['n']), nrep)
-
-    def _adapter_operands(self, table: _RequestTable, dev_buf: torch.Tensor):
-        """(bank pack, device slot table) for _generate_core, or None for a table without slots"""
-        if not table.n_seq:
-            return None
-        from . import lora
-        return lora.bank_pack(self), table.slot_view(dev_buf)
 
     @torch.no_grad()
     def _generate_rows(self, B, label_B, g_seed, cfg_scale, top_k, top_p, more_smooth, cond_type, four_way, c_mask, c_img, force_idx=None, trace: bool = False,
@@ -1546,25 +1574,53 @@ class ControlVAR(nn.Module):
             self._check_logprobs()
         slots = self._adapter_slots(adapter, B, 4 if four_way else 2)
         table = _request_table(B, cfg_scale, top_k, top_p, g_seed, four_way, self.cfg.vocab, len(self.cfg.pyramid.patch_nums), slots=slots)
+        f_hat, scores = self._run_rows(B, label_B, cond_type, four_way, table, c_mask=c_mask, c_img=c_img, force_idx=force_idx, trace=trace,
+                                       logprobs=logprobs, sampled=self._sampled_pattern(four_way, c_mask, c_img, force_idx))
+        return (f_hat, scores) if logprobs else f_hat
+
+    def _row_state(self, B: int, table: _RequestTable, logprobs: bool, forced=None, sample: bool = True):
+        """the device state of one batch of requests -> (the table's device buffer, the _RowDraw over it).  The request table and the
+        adapter slots are one upload; a graph builds this once and refreshes the buffer."""
+        tab_dev = table.host.to(self.device)
+        ad = None
+        if table.n_seq:
+            from . import lora
+            ad = (lora.bank_pack(self), table.slot_view(tab_dev))
+        return tab_dev, _RowDraw(table.views(tab_dev), forced, ad, _score_buffers(B, self.cfg.pyramid.L, self.device) if logprobs else None, sample)
+
+    @torch.no_grad()
+    def _run_rows(self, B, label_B, cond_type, four_way, table: _RequestTable, *, c_mask=None, c_img=None, force_idx=None, trace: bool = False,
+                  logprobs: bool = False, sampled=None, mask_first: Optional[bool] = None, edit=None, score_halves=None):
+        """the per-request runner behind _generate_rows, edit_infer_cfg and score_infer_cfg: the validated table and the entry point's own extras
+        -> (f_hat, TokenScores or None).  mask_first=None draws the (control, image) order (one per call, as the scalar path).
+        edit: the host halves (src_ctrl, keep_ctrl, src_img, keep_img) of _edit_half - the forced-token table is built for the drawn order.
+        score_halves: the flat ids of the halves in token order, checked by _flat_ids - teacher-forced along, scored, nothing sampled."""
         self._pack(check=True); self.vae_proxy[0]._pack(check=True)
         for name, ids in (('c_mask', c_mask), ('c_img', c_img), ('_force_idx', force_idx)):
             if ids is not None:
                 _check_index_range(torch.cat([t.reshape(-1) for t in ids]), 0, self.cfg.vocab - 1, name)
         labels_all, types_all = self._prepare_rows(B, label_B, cond_type, four_way, 0)
-        mask_first = True
-        if self.cfg.mask_factor == 2 and not four_way:
-            import random                                 # control_var.py:403, as _generate
-            mask_first = True if (random.random() < 0.5 or not self.bidirectional) else False
+        if mask_first is None:
+            mask_first = self._draw_order(four_way)
         if self.cfg.separator and four_way:
             raise NotImplementedError('separator: conditional_infer_cfg ignores the special tokens (control_var.py:270-330); only forward(), training '
                                       'and the joint autoregressive_infer_cfg branch are built')
-        tab_dev = table.host.to(self.device)              # the request table and the adapter slots: one upload
-        score = _score_buffers(B, self.cfg.pyramid.L, self.device) if logprobs else None
-        f_hat = self._generate_core(B, labels_all, types_all, 0, None, None, None, None, four_way, c_mask, c_img, force_idx, trace, mask_first=mask_first,
-                                    rows=table.views(tab_dev), ad=self._adapter_operands(table, tab_dev), score=score)
-        if not logprobs:
-            return f_hat
-        return f_hat, self._token_scores(score, mask_first, self._sampled_pattern(four_way, c_mask, c_img, force_idx))
+        dev, forced = self.device, None
+        if edit is not None:
+            forced = self._edit_table(B, *[None if t is None else t.to(device=dev, dtype=dt).contiguous()
+                                           for t, dt in zip(edit, (torch.int32, torch.uint8, torch.int32, torch.uint8))], mask_first)
+        if score_halves is not None:
+            halves = [h.to(device=dev, dtype=torch.int32) for h in score_halves]
+            force_idx, o = [], 0
+            for pn in self.cfg.pyramid.patch_nums:
+                ids = torch.cat([h[:, o:o + pn * pn] for h in halves], dim=1)
+                force_idx.append((ids.repeat(4, 1) if four_way else ids).contiguous())
+                o += pn * pn
+        _, how = self._row_state(B, table, logprobs or score_halves is not None, forced, sample=score_halves is None)
+        f_hat = self._generate_core(B, labels_all, types_all, four_way, how, c_mask, c_img, force_idx, trace, mask_first)
+        if trace and forced is not None:
+            self.last_trace['forced'] = forced
+        return f_hat, (self._token_scores(how.score, mask_first, sampled, forced) if how.score is not None else None)
 
     def _check_logprobs(self):
         """what logprobs=True / score_infer_cfg do not offer beyond _check_per_request's list, said on the host before any device work"""
@@ -1591,30 +1647,58 @@ class ControlVAR(nn.Module):
             b += 2 * n
         return col
 
+    def _draw_scale(self, how, logits, B: int, nrep: int, l: int, si: int, ratio: float, ldv: int, cols, tr, force_idx):
+        """draw the ids of one scale (sampling call si, at `ratio` of the way through the scales) from its logits, as `how` says (_ScalarDraw /
+        _RowDraw) -> (idx (n_draw B, l) int32, the soft embeddings of more_smooth or None).  cols: this scale's columns of the (B, L) tables.
+        tr: the trace to append to.  force_idx (tests, score_infer_cfg) replaces the drawn ids."""
+        cfg, dev = self.cfg, logits.device
+        n_draw = 4 if nrep == 4 else 1
+        idx = torch.empty(n_draw * B, l, device=dev, dtype=torch.int32)
+        comb = torch.empty(B, l, cfg.vocab, device=dev, dtype=torch.float32) if tr is not None else None
+        mg = torch.empty(B, l, device=dev, dtype=torch.float32) if tr is not None else None
+        soft = None
+        if isinstance(how, _RowDraw):
+            seed, top_k, top_p, coef = how.rows                          # _request_table built the weights with the expressions below
+            if not how.sample:
+                pass                                                     # nothing is drawn: the ids are force_idx's, taken below
+            elif how.forced is not None:
+                ops.cfg_sample_edit(logits, B, nrep, l, cfg.vocab, coef[si], top_k, top_p, seed, si, n_draw, idx, how.forced[:, cols], comb, mg, ldv=ldv)
+            else:
+                ops.cfg_sample_rows(logits, B, nrep, l, cfg.vocab, coef[si], top_k, top_p, seed, si, n_draw, idx, comb, mg, ldv=ldv)
+        else:
+            if nrep == 4:
+                t1, t2, t3 = [c * ratio for c in how.cfg]
+                coef = [1 + t1, t2 - t1, t3 - t2, -t3]
+            else:
+                t = how.cfg * ratio
+                coef = [1 + t, -t]
+            expo, g_si = self._torch_noise(how.draws, n_draw * B, l, how.more_smooth)
+            smooth = {}
+            if how.more_smooth and how.top_k != 1:
+                if how.gumbel is not None:
+                    g_si = how.gumbel[si].to(device=dev, dtype=torch.float32).contiguous()      # greedy: the in-place masked softmax is one-hot, i.e. exactly E[idx] (control_var.py:511-515)
+                soft = torch.empty(n_draw * B, l, cfg.cvae, device=dev, dtype=torch.float32)
+                smooth = dict(codebook=self.vae_proxy[0]._pack()['E'], smooth_mul=1.0 + ratio, smooth_tau=max(0.27 * (1 - ratio * 0.95), 0.005),
+                              gumbel=g_si, soft_out=soft)
+            ops.cfg_sample(logits, B, nrep, l, cfg.vocab, coef, how.top_k, how.top_p, how.seed, si, n_draw, idx, comb, mg, seed_dev=how.seed_dev,
+                           ldv=ldv, expo=expo, **smooth)
+        if tr is not None:
+            tr['idx'].append(idx.clone()); tr['margin'].append(mg); tr['logits'].append(comb)
+        if force_idx is not None:
+            idx = force_idx[si].to(device=dev, dtype=torch.int32).contiguous()
+        return idx, soft
+
     @torch.no_grad()
-    def _generate_core(self, B, labels_all, types_all, seed, seed_dev, cfg_scale, top_k, top_p, four_way, c_mask=None, c_img=None,
-                       force_idx=None, trace: bool = False, mask_first: bool = True, more_smooth: bool = False, gumbel=None, draws=None, rows=None,
-                       forced=None, ad=None, score=None, score_only: bool = False):
+    def _generate_core(self, B, labels_all, types_all, four_way, how, c_mask=None, c_img=None, force_idx=None, trace: bool = False,
+                       mask_first: bool = True):
         """the 10-scale loop on device-resident inputs only (capturable in a HIP graph: no host sync, static shapes).
-        draws (sampler='torch'): the noise of each sampling call comes from the caller's torch generator (_TorchDraws).
-        rows (per-request mode): device views (seed, top_k, top_p, coef [nstage][B][4]) of a _RequestTable; the sampling call of every scale
-        is then the per-row one and cfg_scale / top_k / top_p / seed are not used.
-        forced (region-constrained generation, with rows only): device (B, L) int32, the source id of every kept token and -1 elsewhere
-        (ops.edit_force_table); the sampling launch of every scale then writes the kept ids itself (ops.cfg_sample_edit)
-        ad (per-request adapters, with rows only): (lora.bank_pack, device slot (R,) int32) handed to _ada and _blocks_and_head
-        score (token log-probabilities, with rows only): device (logprob, entropy, rank, argmax) buffers (B, L); every scale then issues ONE more
-        launch (ops.score_rows) behind the sampling launch and the overwrites by force_idx / c_mask / c_img / the edit table: it scores the ids of
-        rows 0 .. B-1 - the sample f_hat[:B] returns - under this scale's combine weights rows[3][si] and writes this scale's columns
-        score_only (with score and force_idx, (n_draw B, l) int32 device ids per scale): no sampling launch at all - the score launch is the only
-        consumer of the logits, and the last scale's ids feed nothing"""
-        if ad is not None and rows is None:
-            raise ValueError('ad: the per-request path only (rows given)')
-        if score is not None and (rows is None or self.cfg.separator):
-            raise ValueError('score: the per-request path only (rows given), without separator tokens')
-        if score_only and (score is None or force_idx is None or trace):
+        how: a _ScalarDraw, or a _RowDraw (per-request mode) with what rides on it - the forced-token table, the adapters, the score buffers."""
+        row = isinstance(how, _RowDraw)
+        if row and not how.sample and (how.score is None or force_idx is None or trace):
             raise ValueError('score_only: score buffers and force_idx are required')
-        if forced is not None and (rows is None or four_way):
+        if row and how.forced is not None and (how.rows is None or four_way):
             raise ValueError('forced: the per-request joint path only (rows given, two branches)')
+        ad, score = (how.ad, how.score) if row else (None, None)
         cfg, P = self.cfg, self._pack()
         vae: VQVAE = self.vae_proxy[0]
         py, mf, C = cfg.pyramid, cfg.mask_factor, cfg.C
@@ -1635,56 +1719,21 @@ class ControlVAR(nn.Module):
         # `indep` models hand the rows of the training mask to every inference pass (control_var.py:283,497); those rows hide something
         # only under separate_decoding (otherwise every cached key is visible anyway)
         inf_lvl, inf_holes = attention_levels(cfg) if (cfg.indep and cfg.separate_decoding) else (None, None)
-        Pv = vae._pack()
         for si, pn in enumerate(py.patch_nums):
             l = py.l[si]
             ratio = si / (nstage - 1)
             logits = self._blocks_and_head(x[:R * l], ada, R, l, py.begin[si], py.L, arena, lvl_end=inf_lvl, holes=inf_holes, ad=ad)
-            if rows is not None:
-                coef = None                                              # _request_table built them with the expressions below
-            elif four_way:
-                t1, t2, t3 = [c * ratio for c in cfg_scale]
-                coef = [1 + t1, t2 - t1, t3 - t2, -t3]
-            else:
-                t = cfg_scale * ratio
-                coef = [1 + t, -t]
-            n_draw = 4 if four_way else 1
-            idx = torch.empty(n_draw * B, l, device=dev, dtype=torch.int32)
-            comb = torch.empty(B, l, cfg.vocab, device=dev, dtype=torch.float32) if trace else None
-            mg = torch.empty(B, l, device=dev, dtype=torch.float32) if trace else None
-            expo, g_si = self._torch_noise(draws, n_draw * B, l, more_smooth)
-            soft = None
-            if score_only:
-                pass                                                     # nothing is drawn: the ids are force_idx's, taken below
-            elif forced is not None:
-                ops.cfg_sample_edit(logits, B, nrep, l, cfg.vocab, rows[3][si], rows[1], rows[2], rows[0], si, n_draw, idx, forced[:, py.begin[si]:py.end[si]],
-                                    comb, mg, ldv=cfg.head_ld)
-            elif rows is not None:
-                ops.cfg_sample_rows(logits, B, nrep, l, cfg.vocab, rows[3][si], rows[1], rows[2], rows[0], si, n_draw, idx, comb, mg, ldv=cfg.head_ld)
-            elif more_smooth and top_k != 1:
-                if gumbel is not None:
-                    g_si = gumbel[si].to(device=dev, dtype=torch.float32).contiguous()          # greedy: the in-place masked softmax is one-hot, i.e. exactly E[idx] (control_var.py:511-515)
-                soft = torch.empty(n_draw * B, l, cfg.cvae, device=dev, dtype=torch.float32)
-                ops.cfg_sample(logits, B, nrep, l, cfg.vocab, coef, top_k, top_p, seed, si, n_draw, idx, comb, mg, seed_dev=seed_dev, codebook=Pv['E'],
-                               smooth_mul=1.0 + ratio, smooth_tau=max(0.27 * (1 - ratio * 0.95), 0.005), gumbel=g_si, soft_out=soft,
-                               ldv=cfg.head_ld, expo=expo)
-            else:
-                ops.cfg_sample(logits, B, nrep, l, cfg.vocab, coef, top_k, top_p, seed, si, n_draw, idx, comb, mg, seed_dev=seed_dev, ldv=cfg.head_ld,
-                               expo=expo)
-            if trace:
-                tr['idx'].append(idx.clone()); tr['margin'].append(mg); tr['logits'].append(comb)
-            if force_idx is not None:
-                idx = force_idx[si].to(device=dev, dtype=torch.int32).contiguous()
+            cols = slice(py.begin[si], py.end[si])
+            idx, soft = self._draw_scale(how, logits, B, nrep, l, si, ratio, cfg.head_ld, cols, tr, force_idx)
             if four_way:                                                 # teacher forcing (control_var.py:309-324)
                 if c_mask is not None:
                     idx[:3 * B, :pn * pn] = c_mask[si].to(device=dev, dtype=torch.int32).repeat(3, 1)
                 if c_img is not None:
                     idx[:3 * B, pn * pn:] = c_img[si].to(device=dev, dtype=torch.int32).repeat(3, 1)
             if score is not None:
-                cols = slice(py.begin[si], py.end[si])
-                ops.score_rows(logits, B, nrep, l, cfg.vocab, rows[3][si], idx[:B], None, score[0][:, cols], score[1][:, cols], score[2][:, cols],
+                ops.score_rows(logits, B, nrep, l, cfg.vocab, how.rows[3][si], idx[:B], None, score[0][:, cols], score[1][:, cols], score[2][:, cols],
                                score[3][:, cols], ldv=cfg.head_ld)
-                if score_only and si == nstage - 1:
+                if not how.sample and si == nstage - 1:
                     break
             if cfg.separator and py.sp(si):
                 # control_var.py:507-509: the ids drawn at the separator positions are dropped from the THIRD scale on; at the second scale
@@ -1712,7 +1761,7 @@ class ControlVAR(nn.Module):
         return f_hat[:B]
 
     @torch.no_grad()
-    def _generate_two_pass(self, B, labels_all, types_all, seed, cfg_scale, top_k, top_p, more_smooth, force_idx, trace, mask_first, gumbel, draws=None):
+    def _generate_two_pass(self, B, labels_all, types_all, how: _ScalarDraw, force_idx, trace, mask_first):
         """separate_decoding without indep (control_var.py:428-485): 2 x 10 passes over the same KV arena - per scale first the control
         tokens, then the image tokens, which see their scale's control tokens through the cache (attn_bias=None upstream).  The inputs
         cross over as upstream's do: the image pass of scale k is fed the CONTROL f_hat pooled to pn_k (:467-468), the control pass of
@@ -1721,7 +1770,6 @@ class ControlVAR(nn.Module):
         if cfg.type_pos:
             raise NotImplementedError('type_pos + separate_decoding: upstream indexes patch_nums[si + 1] with si up to 18 (control_var.py:483) and raises')
         vae: VQVAE = self.vae_proxy[0]
-        Pv = vae._pack()
         py, C, dev = cfg.pyramid, cfg.C, self.device
         pns = py.patch_nums
         R = 2 * B
@@ -1744,24 +1792,7 @@ class ControlVAR(nn.Module):
                 x[:R].copy_(xf.view(R, 2, C)[:, si])
             logits = self._blocks_and_head(x[:R * l], ada, R, l, pos, py.L, arena)
             pos += l
-            t = cfg_scale * ratio
-            idx = torch.empty(B, l, device=dev, dtype=torch.int32)
-            comb = torch.empty(B, l, cfg.vocab, device=dev, dtype=torch.float32) if trace else None
-            mg = torch.empty(B, l, device=dev, dtype=torch.float32) if trace else None
-            expo, g_si = self._torch_noise(draws, B, l, more_smooth)
-            soft = None
-            if more_smooth and top_k != 1:
-                if gumbel is not None:
-                    g_si = gumbel[si].to(device=dev, dtype=torch.float32).contiguous()
-                soft = torch.empty(B, l, cfg.cvae, device=dev, dtype=torch.float32)
-                ops.cfg_sample(logits, B, 2, l, cfg.vocab, [1 + t, -t], top_k, top_p, seed, si, 1, idx, comb, mg, codebook=Pv['E'], smooth_mul=1.0 + ratio,
-                               smooth_tau=max(0.27 * (1 - ratio * 0.95), 0.005), gumbel=g_si, soft_out=soft, expo=expo)
-            else:
-                ops.cfg_sample(logits, B, 2, l, cfg.vocab, [1 + t, -t], top_k, top_p, seed, si, 1, idx, comb, mg, expo=expo)
-            if trace:
-                tr['idx'].append(idx.clone()); tr['margin'].append(mg); tr['logits'].append(comb)
-            if force_idx is not None:
-                idx = force_idx[si].to(device=dev, dtype=torch.int32).contiguous()
+            idx, soft = self._draw_scale(how, logits, B, 2, l, si, ratio, 0, None, tr, force_idx)
             if si == 2 * nstage - 1:
                 vae._next_input(k, idx, f[1], B, 1, False, soft=soft)
                 break
@@ -1811,67 +1842,85 @@ class ControlVAR(nn.Module):
         return graph, out, owned
 
     @torch.no_grad()
-    def _capture_per_request(self, B, four_way, labels_all, types_all, cfg, top_k, top_p, finish, teach=None, refresh=None, prologue=None,
-                             adapters: bool = False, logprobs: bool = False, sampled=None):
-        """per_request=True of the two graphed generators: capture the scale loop with the per-row sampler on a static _RequestTable and return
-        run(label_B, cond_type[, given_half], g_seed=None, cfg=..., top_k=..., top_p=...).  refresh(given_half) validates the given half and
-        returns the copy into its static buffer (conditional form); prologue() runs inside the graph before the scale loop.
+    def _graph_runner(self, B, four_way, labels_all, types_all, cfg, top_k, top_p, finish, *, per_request: bool, adapters: bool = False,
+                      logprobs: bool = False, forced=None, teach=None, refresh=None, prologue=None, sampled=None, check_rows: bool = True):
+        """The graphed generators: capture prologue() (inside the graph, before the scale loop), the scale loop and finish() over the static
+        label / type rows, and return replay(label_B, cond_type, given, g_seed, request) -> images, with .graph and .owned.
+        The sampling state lives in a device seed scalar (scalar graphs: cfg, top_k, top_p are baked in and replay refuses every request
+        keyword) or, per_request=True, in the device buffer of a static _RequestTable (request holds cfg / top_k / top_p / adapter; those
+        given here are validated as the defaults).  refresh(given) validates the given half / the edit request and returns the copy into its
+        static buffers.  check_rows (scalar graphs): label_B / cond_type tensors must have shape (B,).
         adapters=True: the adapter launches are captured over the attached bank, the slot of every sequence rides in the same static table,
-        and run takes adapter= (default: every row on the base model)
-        logprobs=True: the score launch of every scale is captured too, the (B, L) score buffers are static outputs of the graph, and run
+        and request['adapter'] chooses (None: every row on the base model)
+        logprobs=True: the score launch of every scale is captured too, the (B, L) score buffers are static outputs of the graph, and replay
         returns (images, TokenScores) - copies, as the images are.  sampled: the (L,) host pattern of the sampled tokens (None: all); an edit
-        graph (teach holds the forced-token table) reads it off that table instead"""
+        graph (forced, the forced-token table) reads it off that table instead"""
         dev, vocab, nstage = self.device, self.cfg.vocab, len(self.cfg.pyramid.patch_nums)
         nrep = 4 if four_way else 2
-        slots0 = self._adapter_slots(-1, B, nrep) if adapters else None
-        table0 = _request_table(B, cfg, top_k, top_p, 0, four_way, vocab, nstage, slots=slots0)         # also validates the defaults
-        tab_dev = table0.host.to(dev)
-        rows = table0.views(tab_dev)
-        ad = self._adapter_operands(table0, tab_dev)
-        score = _score_buffers(B, self.cfg.pyramid.L, dev) if logprobs else None
-        forced_tab = (teach or {}).get('forced')
+        if per_request:
+            slots0 = self._adapter_slots(-1, B, nrep) if adapters else None
+            table0 = _request_table(B, cfg, top_k, top_p, 0, four_way, vocab, nstage, slots=slots0)     # also validates the defaults
+            state, how = self._row_state(B, table0, logprobs, forced)
+        else:
+            state = torch.zeros(1, device=dev, dtype=torch.int64)
+            how = _ScalarDraw(cfg, top_k, top_p, 0, seed_dev=state)
 
         def body():
             if prologue is not None:
                 prologue()
-            return finish(self._generate_core(B, labels_all, types_all, 0, None, None, None, None, four_way, rows=rows, ad=ad, score=score, **(teach or {})))
+            return finish(self._generate_core(B, labels_all, types_all, four_way, how, **(teach or {})))
 
         graph, out, owned = self._capture(body)
 
-        def replay(label_B, cond_type, g_seed, r_cfg, r_top_k, r_top_p, given_half=None, adapter=None):
-            # everything that can refuse runs before the first static buffer is written
-            self._check_per_request(label_B, cond_type, four_way)
-            if adapter is not None and not adapters:
-                raise TypeError('run() got adapter=: this graph was captured without adapters=True, so it holds none of the adapter launches - '
-                                'capture it with adapters=True to choose an adapter per call and per row')
-            slots = self._adapter_slots(-1 if adapter is None else adapter, B, nrep) if adapters else None
+        def check_shapes(label_B, cond_type):
             for name, v in (('label_B', label_B), ('cond_type', cond_type)):
                 if torch.is_tensor(v) and tuple(v.shape) != (B,):
                     raise ValueError(f'{name}: expected shape ({B},), got {tuple(v.shape)}')
-            table = _request_table(B, r_cfg, r_top_k, r_top_p, g_seed, four_way, vocab, nstage, slots=slots)
-            la, ta = self._prepare_rows(B, label_B, cond_type, four_way, 0)
-            copy_given = refresh(given_half) if refresh is not None else None
+
+        def replay(label_B, cond_type, given, g_seed, request):
+            # everything that can refuse runs before the first static buffer is written
+            if per_request:
+                self._check_per_request(label_B, cond_type, four_way)
+                adapter = request['adapter']
+                if adapter is not None and not adapters:
+                    raise TypeError('run() got adapter=: this graph was captured without adapters=True, so it holds none of the adapter launches - '
+                                    'capture it with adapters=True to choose an adapter per call and per row')
+                slots = self._adapter_slots(-1 if adapter is None else adapter, B, nrep) if adapters else None
+                check_shapes(label_B, cond_type)
+                table = _request_table(B, request['cfg'], request['top_k'], request['top_p'], g_seed, four_way, vocab, nstage, slots=slots)
+                la, ta = self._prepare_rows(B, label_B, cond_type, four_way, 0)
+                copy_given = refresh(given) if refresh is not None else None
+            else:
+                _refuse_request_keywords(g_seed, request)
+                if check_rows:
+                    check_shapes(label_B, cond_type)
+                copy_given = refresh(given) if refresh is not None else None
+                seed = int(g_seed) if g_seed is not None else int(torch.empty((), dtype=torch.int64).random_().item())
+                la, ta = self._prepare_rows(B, label_B, cond_type, four_way, seed)
             labels_all.copy_(la)
             if types_all is not None:
                 types_all.copy_(ta)
             if copy_given is not None:
                 copy_given()
-            tab_dev.copy_(table.host)                       # seeds, top_k, top_p, every stage's weights and the adapter slots: one host-to-device copy
+            if per_request:
+                state.copy_(table.host)                     # seeds, top_k, top_p, every stage's weights and the adapter slots: one host-to-device copy
+            else:
+                state.fill_(seed & (2 ** 62 - 1))
             graph.replay()
             if logprobs:
-                return out.clone(), self._token_scores([t.clone() for t in score], True, sampled=sampled,
-                                                       forced=forced_tab.clone() if forced_tab is not None else None)
+                return out.clone(), self._token_scores([t.clone() for t in how.score], True, sampled=sampled,
+                                                       forced=forced.clone() if forced is not None else None)
             return out.clone()
 
-        if refresh is None:
-            def run(label_B, cond_type=None, g_seed=None, cfg=cfg, top_k=top_k, top_p=top_p, adapter=None):
-                return replay(label_B, cond_type, g_seed, cfg, top_k, top_p, adapter=adapter)
-        else:
-            def run(label_B, cond_type, given_half, g_seed=None, cfg=cfg, top_k=top_k, top_p=top_p, adapter=None):
-                return replay(label_B, cond_type, g_seed, cfg, top_k, top_p, given_half, adapter=adapter)
-        run.graph = graph
-        run.owned = owned + ([ad[0]] if ad is not None else [])          # dropped together with the graph when `run` goes away
-        return run
+        replay.graph = graph
+        replay.owned = owned + ([how.ad[0]] if per_request and how.ad is not None else [])      # dropped together with the graph when the runner goes away
+        return replay
+
+    def _finisher(self, decode: str, generated: int):
+        """decode='both': what _decode_pair returns; 'generated': only map `generated` of f_hat, one decoder pass of B images"""
+        if decode == 'both':
+            return self._decode_pair
+        return lambda f_hat: self.vae_proxy[0]._decode(f_hat[:, generated].contiguous(), lo=-1.0, hi=1.0, mul=0.5, add=0.5)
 
     def _check_graph_logprobs(self, per_request: bool, logprobs: bool, four_way: bool):
         """logprobs=True of the graphed generators: refused in words before anything is captured"""
@@ -1880,7 +1929,7 @@ class ControlVAR(nn.Module):
         if not per_request:
             raise ValueError('logprobs=True needs per_request=True: the score launch reads the combine weights of the per-request table')
         self._check_logprobs()
-        self._check_per_request(0, 0, four_way)
+        self._check_per_request_mode(four_way)
 
     def _check_graph_adapters(self, per_request: bool, adapters: bool):
         if not adapters:
@@ -1904,7 +1953,6 @@ class ControlVAR(nn.Module):
         adapters=True (with per_request=True, on a model with an adapter bank): run also takes adapter=, one id per row or one int.
         logprobs=True (with per_request=True): the graph holds the score launches and the (B, L) score buffers, and run returns
         (images, TokenScores) as autoregressive_infer_cfg(logprobs=True) does."""
-        dev = self.device
         four_way = False
         self._check_graph_adapters(per_request, adapters)
         self._check_graph_logprobs(per_request, logprobs, four_way)
@@ -1916,24 +1964,15 @@ class ControlVAR(nn.Module):
         lab0 = torch.zeros(B, dtype=torch.int64)
         ty0 = torch.zeros(B, dtype=torch.int64) if self.cfg.mask_factor == 2 else None
         labels_all, types_all = self._prepare_rows(B, lab0, ty0, four_way, 0)
+        inner = self._graph_runner(B, four_way, labels_all, types_all, cfg, top_k, top_p, self._decode_pair, per_request=per_request, adapters=adapters,
+                                   logprobs=logprobs, check_rows=False)
         if per_request:
-            return self._capture_per_request(B, four_way, labels_all, types_all, cfg, top_k, top_p, self._decode_pair, adapters=adapters, logprobs=logprobs)
-        seed_dev = torch.zeros(1, device=dev, dtype=torch.int64)
-        graph, out, owned = self._capture(lambda: self._decode_pair(self._generate_core(B, labels_all, types_all, 0, seed_dev, cfg, top_k, top_p, four_way)))
-
-        def run(label_B, cond_type=None, g_seed=None, **request):
-            _refuse_request_keywords(g_seed, request)
-            seed = int(g_seed) if g_seed is not None else int(torch.empty((), dtype=torch.int64).random_().item())
-            la, ta = self._prepare_rows(B, label_B, cond_type, four_way, seed)
-            labels_all.copy_(la)
-            if types_all is not None:
-                types_all.copy_(ta)
-            seed_dev.fill_(seed & (2 ** 62 - 1))
-            graph.replay()
-            return out.clone()
-
-        run.graph = graph
-        run.owned = owned                                   # dropped together with the graph when `run` goes away
+            def run(label_B, cond_type=None, g_seed=None, cfg=cfg, top_k=top_k, top_p=top_p, adapter=None):
+                return inner(label_B, cond_type, None, g_seed, dict(cfg=cfg, top_k=top_k, top_p=top_p, adapter=adapter))
+        else:
+            def run(label_B, cond_type=None, g_seed=None, **request):
+                return inner(label_B, cond_type, None, g_seed, request)
+        run.graph, run.owned = inner.graph, inner.owned
         return run
 
     @torch.no_grad()
@@ -1982,75 +2021,33 @@ class ControlVAR(nn.Module):
         pns = self.cfg.pyramid.patch_nums
         Ltot, side_px = sum(pn * pn for pn in pns), 16 * pns[-1]
         labels_all, types_all = self._prepare_rows(B, torch.zeros(B, dtype=torch.int64), torch.zeros(B, dtype=torch.int64), True, 0)
-        seed_dev = torch.zeros(1, device=dev, dtype=torch.int64)
         ids_buf = torch.zeros(B, Ltot, device=dev, dtype=torch.int32)
         pix_buf = torch.zeros(B, 3, side_px, side_px, device=dev, dtype=torch.float32) if source == 'pixels' else None
         ids_Bl = vae._split(ids_buf)                        # per-scale views of the static buffer: what _generate_core teacher-forces from
-        teach = {'c_mask' if given == 'control' else 'c_img': ids_Bl}
+        arg = 'c_mask' if given == 'control' else 'c_img'
 
         def tokenise():
             if pix_buf is not None:
                 ids_buf.copy_(vae._ms_encode(vae._encode_f(pix_buf))[0])
 
-        def finish(f_hat):
-            if decode == 'both':
-                return self._decode_pair(f_hat)
-            return vae._decode(f_hat[:, 1 if given == 'control' else 0].contiguous(), lo=-1.0, hi=1.0, mul=0.5, add=0.5)
-
-        def body():
-            tokenise()
-            return finish(self._generate_core(B, labels_all, types_all, 0, seed_dev, cfg, top_k, top_p, True, **teach))
-
-        def as_rows(name, v):
-            if torch.is_tensor(v) and tuple(v.shape) != (B,):
-                raise ValueError(f'{name}: expected shape ({B},), got {tuple(v.shape)}')
-            return v
-
-        def as_given(given_half):
-            """the given half as run() takes it, checked on the host -> what is copied into the static pixel / id buffer"""
+        def refresh(given_half):
+            """the given half as run() takes it, checked on the host -> the copy into the static pixel / id buffer"""
             if pix_buf is not None:
-                if not torch.is_tensor(given_half) or tuple(given_half.shape) != tuple(pix_buf.shape) or not given_half.is_floating_point():
-                    raise ValueError(f'given_half: expected pixels of shape {tuple(pix_buf.shape)} (floating point, in [-1, 1]), got '
-                                     f'{tuple(given_half.shape) if torch.is_tensor(given_half) else type(given_half).__name__}')
+                checked = _pixels('given_half', given_half, pix_buf.shape)
             else:
-                if isinstance(given_half, (list, tuple)):
-                    want = [(B, pn * pn) for pn in pns]
-                    if not all(torch.is_tensor(t) for t in given_half) or [tuple(t.shape) for t in given_half] != want:
-                        raise ValueError(f'given_half: expected {len(pns)} id tensors of shapes {want}')
-                    given_half = torch.cat([t.to(given_half[0].device) for t in given_half], dim=1)
-                if not torch.is_tensor(given_half) or tuple(given_half.shape) != (B, Ltot) or given_half.is_floating_point() or given_half.dtype == torch.bool:
-                    raise ValueError(f'given_half: expected integer ids of shape ({B}, {Ltot}) or a list of (B, pn * pn) tensors, got '
-                                     f'{tuple(given_half.shape) if torch.is_tensor(given_half) else type(given_half).__name__}')
-                _check_index_range(given_half, 0, self.cfg.vocab - 1, 'c_mask' if given == 'control' else 'c_img')
-            return given_half
+                checked = _flat_ids('given_half', given_half, B, pns, self.cfg.vocab, arg)
+            return lambda: (pix_buf if pix_buf is not None else ids_buf).copy_(checked)
 
+        inner = self._graph_runner(B, True, labels_all, types_all, cfg, top_k, top_p, self._finisher(decode, 1 if given == 'control' else 0),
+                                   per_request=per_request, adapters=adapters, logprobs=logprobs, teach={arg: ids_Bl}, refresh=refresh, prologue=tokenise,
+                                   sampled=self._sampled_pattern(True, *((ids_Bl, None) if given == 'control' else (None, ids_Bl)), None))
         if per_request:
-            def refresh(given_half):
-                checked = as_given(given_half)
-                return lambda: (pix_buf if pix_buf is not None else ids_buf).copy_(checked)
-
-            run = self._capture_per_request(B, True, labels_all, types_all, cfg, top_k, top_p, finish, teach=teach, prologue=tokenise, refresh=refresh,
-                                            adapters=adapters, logprobs=logprobs, sampled=self._sampled_pattern(True, *(
-                                                (ids_Bl, None) if given == 'control' else (None, ids_Bl)), None))
-            run.ids = lambda: ids_buf.clone()
-            return run
-        graph, out, owned = self._capture(body)
-
-        def run(label_B, cond_type, given_half, g_seed=None, **request):
-            _refuse_request_keywords(g_seed, request)
-            label_B, cond_type = as_rows('label_B', label_B), as_rows('cond_type', cond_type)
-            given_half = as_given(given_half)
-            seed = int(g_seed) if g_seed is not None else int(torch.empty((), dtype=torch.int64).random_().item())
-            la, ta = self._prepare_rows(B, label_B, cond_type, True, seed)
-            labels_all.copy_(la)
-            types_all.copy_(ta)
-            (pix_buf if pix_buf is not None else ids_buf).copy_(given_half)
-            seed_dev.fill_(seed & (2 ** 62 - 1))
-            graph.replay()
-            return out.clone()
-
-        run.graph = graph
-        run.owned = owned                                   # dropped together with the graph when `run` goes away
+            def run(label_B, cond_type, given_half, g_seed=None, cfg=cfg, top_k=top_k, top_p=top_p, adapter=None):
+                return inner(label_B, cond_type, given_half, g_seed, dict(cfg=cfg, top_k=top_k, top_p=top_p, adapter=adapter))
+        else:
+            def run(label_B, cond_type, given_half, g_seed=None, **request):
+                return inner(label_B, cond_type, given_half, g_seed, request)
+        run.graph, run.owned = inner.graph, inner.owned
         run.ids = lambda: ids_buf.clone()                   # the given half's ids of the last replay ('pixels': what the graph's tokeniser produced)
         return run
 
@@ -2092,25 +2089,8 @@ class ControlVAR(nn.Module):
         s_ctrl, k_ctrl = _edit_half('ctrl', src_ctrl, keep_ctrl, B, pns, self.cfg.vocab) if self.cfg.mask_factor == 2 else (None, None)
         s_img, k_img = _edit_half('img', src_img, keep_img, B, pns, self.cfg.vocab)
         table = _request_table(B, cfg, top_k, top_p, g_seed, False, self.cfg.vocab, len(pns), slots=self._adapter_slots(adapter, B, 2))
-        self._pack(check=True); self.vae_proxy[0]._pack(check=True)
-        labels_all, types_all = self._prepare_rows(B, label_B, cond_type, False, 0)
-        mask_first = True
-        if self.cfg.mask_factor == 2:
-            import random                                 # control_var.py:403, as _generate_rows: the table below is built for the drawn order
-            mask_first = True if (random.random() < 0.5 or not self.bidirectional) else False
-        dev = self.device
-        on_dev = [None if t is None else t.to(device=dev, dtype=dt).contiguous() for t, dt in ((s_ctrl, torch.int32), (k_ctrl, torch.uint8),
-                                                                                                (s_img, torch.int32), (k_img, torch.uint8))]
-        forced = self._edit_table(B, *on_dev, mask_first)
-        tab_dev = table.host.to(dev)
-        score = _score_buffers(B, self.cfg.pyramid.L, dev) if logprobs else None
-        f_hat = self._generate_core(B, labels_all, types_all, 0, None, None, None, None, False, trace=trace, mask_first=mask_first, rows=table.views(tab_dev),
-                                    forced=forced, ad=self._adapter_operands(table, tab_dev), score=score)
-        if trace:
-            self.last_trace['forced'] = forced
-        if logprobs:
-            return self._decode_pair(f_hat), self._token_scores(score, mask_first, forced=forced)
-        return self._decode_pair(f_hat)
+        f_hat, scores = self._run_rows(B, label_B, cond_type, False, table, trace=trace, logprobs=logprobs, edit=(s_ctrl, k_ctrl, s_img, k_img))
+        return self._images(f_hat, scores)
 
     # ---- token log-probabilities of given tokens
     @torch.no_grad()
@@ -2138,32 +2118,20 @@ class ControlVAR(nn.Module):
         if not mask_first and (four_way or not self.bidirectional):
             raise ValueError('mask_first=False: only a bidirectional model on the joint path (given=None) lays the image half first')
         pns, vocab = self.cfg.pyramid.patch_nums, self.cfg.vocab
-        img = _score_ids('ids_img', ids_img, B, pns, vocab)
+        img = _flat_ids('ids_img', ids_img, B, pns, vocab)
         if mf == 2:
             if ids_ctrl is None:
                 raise ValueError('ids_ctrl: the control half is scored too (given= says which half conditions the other) - pass its ids')
-            ctrl = _score_ids('ids_ctrl', ids_ctrl, B, pns, vocab)
+            ctrl = _flat_ids('ids_ctrl', ids_ctrl, B, pns, vocab)
         elif ids_ctrl is not None:
             raise ValueError('ids_ctrl: a plain VAR has the image half only')
         if four_way and _host_array(cfg).ndim == 0:
             cfg = (cfg,) * 3
         nrep = 4 if four_way else 2
         table = _request_table(B, cfg, 0, 0.0, 0, four_way, vocab, len(pns), slots=self._adapter_slots(adapter, B, nrep))
-        self._pack(check=True); self.vae_proxy[0]._pack(check=True)
-        labels_all, types_all = self._prepare_rows(B, label_B, cond_type, four_way, 0)
-        dev = self.device
         halves = [img] if mf == 1 else ([ctrl, img] if mask_first else [img, ctrl])
-        halves = [h.to(device=dev, dtype=torch.int32) for h in halves]
-        force, o = [], 0
-        for pn in pns:
-            ids = torch.cat([h[:, o:o + pn * pn] for h in halves], dim=1)
-            force.append((ids.repeat(4, 1) if four_way else ids).contiguous())
-            o += pn * pn
-        score = _score_buffers(B, self.cfg.pyramid.L, dev)
-        tab_dev = table.host.to(dev)
-        self._generate_core(B, labels_all, types_all, 0, None, None, None, None, four_way, force_idx=force, mask_first=mask_first, rows=table.views(tab_dev),
-                            ad=self._adapter_operands(table, tab_dev), score=score, score_only=True)
-        return self._token_scores(score, mask_first, sampled=torch.zeros(self.cfg.pyramid.L, dtype=torch.bool))
+        return self._run_rows(B, label_B, cond_type, four_way, table, sampled=torch.zeros(self.cfg.pyramid.L, dtype=torch.bool), mask_first=mask_first,
+                              score_halves=halves)[1]
 
     @torch.no_grad()
     def graphed_edit_generator(self, B: int, source: str = 'ids', cfg=1.5, top_k=0, top_p=0.0, decode: str = 'both', adapters: bool = False,
@@ -2210,11 +2178,6 @@ class ControlVAR(nn.Module):
                     ids_buf[h].copy_(vae._ms_encode(vae._encode_f(pix_buf[h]))[0])
             self._edit_table(B, ids_buf.get('ctrl'), keep_buf.get('ctrl'), ids_buf['img'], keep_buf['img'], True, forced)
 
-        def finish(f_hat):
-            if decode == 'both':
-                return self._decode_pair(f_hat)
-            return vae._decode(f_hat[:, mf - 1].contiguous(), lo=-1.0, hi=1.0, mul=0.5, add=0.5)
-
         def refresh(request):
             checked = {h: _edit_half(h, request.get('src_' + h), request.get('keep_' + h), B, pns, self.cfg.vocab, pixels) for h in halves}
 
@@ -2228,21 +2191,25 @@ class ControlVAR(nn.Module):
                         keep_buf[h].copy_(mask)
             return copy
 
-        inner = self._capture_per_request(B, False, labels_all, types_all, cfg, top_k, top_p, finish, teach={'forced': forced}, refresh=refresh,
-                                          prologue=prologue, adapters=adapters, logprobs=logprobs)
+        inner = self._graph_runner(B, False, labels_all, types_all, cfg, top_k, top_p, self._finisher(decode, mf - 1), per_request=True, adapters=adapters,
+                                   logprobs=logprobs, forced=forced, refresh=refresh, prologue=prologue)
 
         if mf == 2:
             def run(label_B, cond_type, *, src_img=None, keep_img=None, src_ctrl=None, keep_ctrl=None, g_seed=None, cfg=cfg, top_k=top_k, top_p=top_p,
                     adapter=None):
-                return inner(label_B, cond_type, dict(src_img=src_img, keep_img=keep_img, src_ctrl=src_ctrl, keep_ctrl=keep_ctrl), g_seed=g_seed, cfg=cfg,
-                             top_k=top_k, top_p=top_p, adapter=adapter)
+                return inner(label_B, cond_type, dict(src_img=src_img, keep_img=keep_img, src_ctrl=src_ctrl, keep_ctrl=keep_ctrl), g_seed,
+                             dict(cfg=cfg, top_k=top_k, top_p=top_p, adapter=adapter))
         else:
             def run(label_B, cond_type=None, *, src_img=None, keep_img=None, g_seed=None, cfg=cfg, top_k=top_k, top_p=top_p, adapter=None):
-                return inner(label_B, None, dict(src_img=src_img, keep_img=keep_img), g_seed=g_seed, cfg=cfg, top_k=top_k, top_p=top_p, adapter=adapter)
+                return inner(label_B, None, dict(src_img=src_img, keep_img=keep_img), g_seed, dict(cfg=cfg, top_k=top_k, top_p=top_p, adapter=adapter))
         run.graph, run.owned = inner.graph, inner.owned
         run.ids = lambda: tuple(ids_buf[h].clone() for h in halves)          # the sources of the last replay ('pixels': what the tokeniser produced)
         run.forced = lambda: forced.clone()                                  # ... and its forced-token table
         return run
+
+    def _images(self, f_hat: torch.Tensor, scores: Optional[TokenScores] = None):
+        """what the public generation calls return: the decoded images, or (images, scores) under logprobs=True"""
+        return self._decode_pair(f_hat) if scores is None else (self._decode_pair(f_hat), scores)
 
     def _decode_pair(self, f_hat: torch.Tensor) -> torch.Tensor:
         vae: VQVAE = self.vae_proxy[0]
@@ -2271,7 +2238,7 @@ class ControlVAR(nn.Module):
         per-request path as adapter= does (scalars are broadcast), so its refusals apply; ids and images are bit-identical with and without it."""
         out = self._generate(B, label_B, g_seed, cfg, top_k, top_p, more_smooth, cond_type, False, None, None, _force_idx, _trace, _gumbel, adapter=adapter,
                              logprobs=logprobs)
-        return (self._decode_pair(out[0]), out[1]) if logprobs else self._decode_pair(out)
+        return self._images(*out) if logprobs else self._images(out)
 
     @torch.no_grad()
     def conditional_infer_cfg(self, B: int, label_B, g_seed: Optional[int] = None, cfg=(1.5, 1.5, 1.5), top_k=0, top_p=0.0,
@@ -2284,7 +2251,7 @@ class ControlVAR(nn.Module):
             raise NotImplementedError('conditional_infer_cfg needs mask_factor == 2 (control_var.py:333)')
         out = self._generate(B, label_B, g_seed, cfg, top_k, top_p, more_smooth, cond_type, True, c_mask, c_img, _force_idx, _trace, _gumbel, adapter=adapter,
                              logprobs=logprobs)
-        return (self._decode_pair(out[0]), out[1]) if logprobs else self._decode_pair(out)
+        return self._images(*out) if logprobs else self._images(out)
 
     def forward(self, label_B: torch.LongTensor, x_BLCv_wo_first_l: torch.Tensor, cond_type=None, mask_first=True) -> torch.Tensor:
         """control_var.py:568-651 teacher-forced logits (B, L, V) fp32.  Under autograd (grad mode on and trainable
@@ -2354,7 +2321,7 @@ class VAR(ControlVAR):
         """var.py:143-207: returns (B, 3, H, H) in [0,1], H = 16 patch_nums[-1] (256, or 512 with PATCH_NUMS_512).
         logprobs=True: (images, TokenScores), as ControlVAR.autoregressive_infer_cfg."""
         out = self._generate(B, label_B, g_seed, cfg, top_k, top_p, more_smooth, None, False, None, None, _force_idx, _trace, adapter=adapter, logprobs=logprobs)
-        return (self._decode_pair(out[0]), out[1]) if logprobs else self._decode_pair(out)
+        return self._images(*out) if logprobs else self._images(out)
 
     @torch.no_grad()
     def edit_infer_cfg(self, B: int, label_B, *, src_img=None, keep_img=None, g_seed=None, cfg=1.5, top_k=0, top_p=0.0, trace: bool = False,

@@ -201,9 +201,9 @@ def test_plain_var_has_the_image_half_only():
 def test_generate_core_refuses_a_table_without_rows_or_with_four_branches(model):
     forced = torch.full((2, model.cfg.pyramid.L), -1, dtype=torch.int32)
     with pytest.raises(ValueError, match='forced: the per-request joint path only'):
-        model._generate_core(2, None, None, 0, None, 1.5, 0, 0.0, False, forced=forced)
+        model._generate_core(2, None, None, False, models._RowDraw(None, forced=forced))
     with pytest.raises(ValueError, match='forced: the per-request joint path only'):
-        model._generate_core(2, None, None, 0, None, None, None, None, True, forced=forced, rows=(None, None, None, None))
+        model._generate_core(2, None, None, True, models._RowDraw((None, None, None, None), forced=forced))
 
 
 # --------------------------------------------------------------------------------------------------------------- the torch ops
