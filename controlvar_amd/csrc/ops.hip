@@ -350,7 +350,17 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const T* __restrict__ x, 
     for (int i = threadIdx.x; i < 2 * C; i += 256) {
         const int c = i >> 1, which = i & 1, cg2 = c / VEC, e = c % VEC;
         float a = 0.f;
-        for (int k = 0; k < PL; ++k) a += sred[((long)(e * PL + k) * ncg + cg2) * 2 + which];      // same order over k as before: bit-identical
+        if (PL <= 64 || (PL & 3)) {
+            for (int k = 0; k < PL; ++k) a += sred[((long)(e * PL + k) * ncg + cg2) * 2 + which];      // same order over k as before: bit-identical
+        } else {
+            // C / VEC <= 2 (128 or 256 pixel lanes, one pixel each in a 128-pixel chunk): four interleaved sums.  One running fp32 sum over that many
+            // squares of bf16-grid values stalls on round-to-even ties (-17 u on the variance at C = 8, HW = 1030); every wider shape keeps its bits.
+            float a4[4] = {0.f, 0.f, 0.f, 0.f};
+            for (int k = 0; k < PL; k += 4)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) a4[j] += sred[((long)(e * PL + k + j) * ncg + cg2) * 2 + which];
+            a = (a4[0] + a4[1]) + (a4[2] + a4[3]);
+        }
         partial[(((long)b * nchunk + chunk) * C) * 2 + i] = a;
     }
 }

@@ -16,10 +16,13 @@ constexpr int RED_S = 8;      // row segments of the per-sequence column reducti
 constexpr int RED_S_MAX = 64;
 static inline int red_segments(int R, int l, int target) { return max(1, min(min(RED_S_MAX, (target + R - 1) / max(R, 1)), (l + 3) / 4)); }
 static inline int red_segments_max(int R) { return max(RED_S, red_segments(R, 1 << 20, max(CVAR_RED_TARGET, CVAR_GG_TARGET))); }
+// row statistics (mean, rstd) of the two-kernel LayerNorm backward, rounded up to whole 16-byte vectors: the segment partials behind them stay
+// 16-byte aligned for an odd row count too (2 M floats put them at an 8-byte address and every odd M fell back to the scalar column kernel)
+static inline int64_t ln_stats_floats(int64_t M) { return (2 * M + 3) & ~(int64_t)3; }
 // floats of workspace the per-sequence reductions (cvar_gated_grad, cvar_ln_modulate_bwd) may use for M = R * l rows
 extern "C" int64_t cvar_train_ws_floats(int64_t M, int R, int C) {
     if (M <= 0 || R <= 0 || C <= 0) return 0;
-    return 2 * M + 2 * (int64_t)red_segments_max(R) * R * C;
+    return ln_stats_floats(M) + 2 * (int64_t)red_segments_max(R) * R * C;
 }
 
 // x[m,c] += gate[r,c] * rowscale[r] * f[m,c]          (x + drop_path(gamma * f(x)), basic_var.py:208-209)
@@ -468,7 +471,7 @@ extern "C" int cvar_ln_modulate_bwd(const float* x, const void* dy, int dtype, c
     if (ws_floats < cvar_train_ws_floats(M, M / rows_per, C)) return CVAR_EINVAL;            // ABI 16
     const int R = M / rows_per;
     float* stats = ws;
-    float* partial = ws + 2 * (size_t)M;
+    float* partial = ws + ln_stats_floats(M);
     dim3 b256(256);
     int nseg = RED_S;
     if (dtype == CVAR_BF16) {

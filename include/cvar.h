@@ -303,8 +303,9 @@ int cvar_resample_sep(const float* in, const float* wy, const float* wx, float* 
  * x[m,:] += gate[m / gate_rows,:] * rowscale[m / gate_rows] * f[m,:]   (x + drop_path(gamma * f), basic_var.py:208-209) */
 int cvar_gate_residual(float* x, const void* f, int dtype, const float* gate, int64_t ldg, int gate_rows,
                        const float* rowscale, int64_t M, int C, void* stream);
-/* floats of workspace the two per-sequence reductions below may use for M = R * l rows (row statistics + one partial row per row
- * segment: the sequences are cut into enough segments that R * segments blocks fill the 256 CUs) */
+/* floats of workspace the two per-sequence reductions below may use for M = R * l rows (row statistics, rounded up to whole 16-byte
+ * vectors so that the partials behind them keep the workspace's alignment for an odd M, + one partial row per row segment: the sequences
+ * are cut into enough segments that R * segments blocks fill the 256 CUs) */
 int64_t cvar_train_ws_floats(int64_t M, int R, int C);
 /* df = dx * gate * rowscale;  dgate[r,:] = rowscale[r] * sum_{m in r} dx[m,:] * f[m,:].  ws: cvar_train_ws_floats(R*l, R, C) floats;
  * ws_floats (ABI 16) = floats the caller allocated: smaller than that -> CVAR_EINVAL instead of an out-of-bounds device write. */
@@ -314,6 +315,8 @@ int cvar_gelu(const void* a, void* h, int dtype, int64_t n, void* stream);      
 int cvar_gelu_bwd(const void* a, void* dh, int dtype, int64_t n, void* stream);       /* dh *= gelu_tanh'(a) */
 /* backward of cvar_ln_modulate: dx_out = dx_in + dLN(dy * (1+scale)); dscale[r,:] = sum dy*xhat; dshift[r,:] = sum dy.
  * bf16 dy: ONE pass over x, dy, dx_in (row in registers, column sums carried per wave, folded through LDS in a fixed order).
+ * That path needs C % 4 == 0, C <= 2048, ld_ada % 4 == 0, x, scale, dx_in, dx_out and ws 16-byte aligned and dy 8-byte aligned; any other
+ * call is served by a row kernel + a column kernel that read x and dy twice (same results to rounding, not the same bits).
  * ws: cvar_train_ws_floats(M, M / rows_per, C) floats, ws_floats as above (ABI 16). */
 int cvar_ln_modulate_bwd(const float* x, const void* dy, int dtype, const float* scale, int64_t ld_ada, int rows_per,
                          const float* dx_in, float* dx_out, float* dscale, float* dshift, int64_t ldo,
