@@ -683,6 +683,11 @@ extern "C" int cvar_silu_bwd(const float* cond, const float* dsilu, float* dcond
 // ---- optimizer ----------------------------------------------------------------------------------------------------
 // torch.optim.AdamW step on one tensor: g' = g * gscale (all-reduce mean and clip folded in), p *= 1 - lr*wd,
 // m = b1 m + (1-b1) g', v = b2 v + (1-b2) g'^2, p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps)
+// bc1 = 1 - b1^step and sqrt(bc2) = sqrt(1 - b2^step) come from the host, computed in double from the float betas (as torch.optim.AdamW
+// does) and rounded to float once.  1.0f - powf(b2, step) cancels: at b2 = 0.999 and step 2 its rounding is 1.5e-5 of bc2 and moved
+// every parameter by up to 30 x 2^-24 of the step's terms (10 x at step 7); at b2 = 0.95 the float form was harmless.
+static inline float adam_bc1(float beta1, int step) { return (float)(1.0 - pow((double)beta1, (double)step)); }
+static inline float adam_bc2_sqrt(float beta2, int step) { return (float)sqrt(1.0 - pow((double)beta2, (double)step)); }
 __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long n,
                              float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt, const float* __restrict__ gscale_dev, float gscale) {
     const float gs = gscale * (gscale_dev ? gscale_dev[0] : 1.0f);
@@ -698,8 +703,7 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
 extern "C" int cvar_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                           float weight_decay, int step, const float* gscale_dev, float gscale, void* stream) {
     if (!p || !g || !m || !v || n <= 0 || step < 1) return CVAR_EINVAL;
-    const float bc1 = 1.0f - powf(beta1, (float)step);
-    const float bc2s = sqrtf(1.0f - powf(beta2, (float)step));
+    const float bc1 = adam_bc1(beta1, step), bc2s = adam_bc2_sqrt(beta2, step);
     hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)min((int64_t)4096, (n + 255) / 256)), dim3(256), 0, as_stream(stream), p, g, m, v, (long)n, lr, beta1,
                        beta2, eps, weight_decay, bc1, bc2s, gscale_dev, gscale);
     CVAR_CHECK_LAUNCH();
@@ -790,8 +794,7 @@ extern "C" int cvar_adamw_multi(const void* table_dev, int n_tensors, const floa
         return CVAR_EINVAL;
     AdamGroups gr;
     for (int i = 0; i < 8; ++i) { gr.lr[i] = i < n_groups ? lr_by_group_host[i] : 0.f; gr.wd[i] = i < n_groups ? wd_by_group_host[i] : 0.f; }
-    const float bc1 = 1.0f - powf(beta1, (float)step);
-    const float bc2s = sqrtf(1.0f - powf(beta2, (float)step));
+    const float bc1 = adam_bc1(beta1, step), bc2s = adam_bc2_sqrt(beta2, step);
     hipLaunchKernelGGL(adamw_multi_kernel, dim3(128, (unsigned)n_tensors), dim3(256), 0, as_stream(stream), (const AdamTensor*)table_dev, gr, beta1, beta2,
                        eps, bc1, bc2s, gscale_dev, gscale);
     CVAR_CHECK_LAUNCH();

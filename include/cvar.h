@@ -334,14 +334,18 @@ int cvar_colsum(const void* A, int dtype, int64_t lda, float* out, int64_t M, in
  * weight-gradient GEMM needs anyway - contiguous rows instead of a strided column walk. */
 int cvar_rowsum(const void* A, int dtype, int64_t lda, float* out, int nrows, int ncols, int accumulate, void* stream);
 /* token cross-entropy (CrossEntropyLoss(reduction='none'), train_control_var_hpu.py:135,231) fused with its gradient:
- * loss_tok[m] = logsumexp(logits[m,:]) - logits[m,target[m]];  dlogits = (softmax - onehot) * weight[m] * gscale (optional). */
+ * loss_tok[m] = logsumexp(logits[m,:]) - logits[m,target[m]];  dlogits = (softmax - onehot) * weight[m] * gscale (optional).
+ * weight may be NULL (all ones), dlogits may be NULL (loss only).  target[m] must lie in [0, V): it indexes the row unchecked. */
 int cvar_ce_fwd_bwd(const float* logits, const int32_t* target, const float* weight, float gscale, float* loss_tok,
                     void* dlogits, int out_dtype, int64_t M, int V, void* stream);
 /* dst[idx[i],:] += src[i,:] in row order (nn.Embedding gradients of class_emb / cond_embed). */
 int cvar_scatter_add_rows(const float* src, int64_t ld_src, const int32_t* idx, float* dst, int n, int C, void* stream);
 int cvar_silu_bwd(const float* cond, const float* dsilu, float* dcond, int64_t n, void* stream);
 /* torch.optim.AdamW step of one tensor (train_control_var_hpu.py:631-633); gradient scaled by gscale * gscale_dev[0]
- * (all-reduce mean and clip_grad_norm_ coefficient folded in). */
+ * (all-reduce mean and clip_grad_norm_ coefficient folded in):
+ *   g' = g gscale,  p *= 1 - lr wd,  m = b1 m + (1 - b1) g',  v = b2 v + (1 - b2) g'^2,  p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps).
+ * The bias corrections bc1 = 1 - b1^step and sqrt(bc2) = sqrt(1 - b2^step) are formed on the host in double from the float betas and
+ * rounded to float once (in float, 1 - powf(0.999, step) loses up to 1.5e-5 of bc2 at small steps).  The same holds for cvar_adamw_multi. */
 int cvar_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                float weight_decay, int step, const float* gscale_dev, float gscale, void* stream);
 /* gradient norm (clip_grad_norm_, train_control_var_hpu.py:244-245): 256 double partial sums per tensor, then
