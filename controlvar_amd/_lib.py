@@ -124,6 +124,8 @@ SERVE_SIGNATURES = {
     'cvar_lora_down_rows': (c_i, [c_p, c_l, c_p, c_l, c_p, c_p, c_i, c_i, c_i, c_p, c_l, c_i, c_p, c_l, c_i, c_i, c_p]),
     # token log-probabilities: joined at version 1
     'cvar_score_rows': (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p]),
+    # split-bf16 transformer mode (gemm_precision='bf16x3'): joined at version 1
+    'cvar_ln_modulate_split3': (c_i, [c_p, c_p, c_p, c_l, c_i, c_p, c_i, c_i, c_f, c_p]),
 }
 
 _lib = None

@@ -6,6 +6,9 @@
 // ------------------------------------------------------------------------------------------------
 // NV = float4 vectors per lane (C <= NV*256); TAIL = the last vector is only partly populated (C % 256 != 0).
 // All loads of a row are issued back to back (no per-vector branches), so a wave has NV 16-byte loads in flight.
+// TO = bf16x3_t: the row leaves as the split-bf16 operand [hi(C) | lo(C) | hi(C)] of out[M][3 C] (cvar_ln_modulate_split3; split3_store below).
+struct bf16x3_t { bf16_t v; };
+__device__ __forceinline__ void split3_store(bf16_t* __restrict__ o, const float* y, int C);
 template <typename TO, int NV, bool TAIL>
 __global__ __launch_bounds__(256) void ln_modulate_kernel(const float* __restrict__ x, const float* __restrict__ scale,
                                                          const float* __restrict__ shift, long ld_ada, int rows_per,
@@ -40,7 +43,7 @@ __global__ __launch_bounds__(256) void ln_modulate_kernel(const float* __restric
         for (int e = 0; e < 4; ++e) { v[i][e] = ok ? v[i][e] - mean : 0.f; q += v[i][e] * v[i][e]; }
     }
     const float rstd = rsqrtf(wave_sum(q) / (float)C + eps);
-    TO* orow = out + (long)row * C;
+    TO* orow = out + (long)row * C * (std::is_same<TO, bf16x3_t>::value ? 3 : 1);
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
         const int c = (i * 64 + lane) * 4;
@@ -48,7 +51,9 @@ __global__ __launch_bounds__(256) void ln_modulate_kernel(const float* __restric
         float y[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) y[e] = (v[i][e] * rstd) * (1.0f + a[i][e]) + b[i][e];
-        if constexpr (sizeof(TO) == 4) {
+        if constexpr (std::is_same<TO, bf16x3_t>::value) {
+            split3_store((bf16_t*)orow + c, y, C);
+        } else if constexpr (sizeof(TO) == 4) {
             f32x4_t o = {y[0], y[1], y[2], y[3]};
             *(f32x4_t*)(orow + c) = o;
         } else {
@@ -92,6 +97,14 @@ extern "C" int cvar_ln_modulate(const float* x, const float* scale, const float*
     if (out_dtype == CVAR_BF16) return ln_dispatch<bf16_t>(x, scale, shift, (long)ld_ada, rows_per, (bf16_t*)out, M, C, eps, as_stream(stream));
     if (out_dtype == CVAR_F32) return ln_dispatch<float>(x, scale, shift, (long)ld_ada, rows_per, (float*)out, M, C, eps, as_stream(stream));
     return CVAR_EUNSUPPORTED;
+}
+
+// cvar_ln_modulate with the split store (include/cvar_serve.h): bit for bit cvar_split3(cvar_ln_modulate(..., CVAR_F32)) without the fp32 row in between
+extern "C" int cvar_ln_modulate_split3(const float* x, const float* scale, const float* shift, int64_t ld_ada, int rows_per,
+                                       void* out, int M, int C, float eps, void* stream) {
+    if (!x || !scale || !shift || !out || M <= 0 || rows_per <= 0) return CVAR_EINVAL;
+    if (C % 4 || C > 2048 || ld_ada % 4 || (((uintptr_t)x | (uintptr_t)scale | (uintptr_t)shift) & 15) || ((uintptr_t)out & 7)) return CVAR_EUNSUPPORTED;
+    return ln_dispatch<bf16x3_t>(x, scale, shift, (long)ld_ada, rows_per, (bf16x3_t*)out, M, C, eps, as_stream(stream));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -551,7 +564,7 @@ extern "C" int cvar_groupnorm_silu(const void* x, int dtype, const float* weight
 // contraction kernel.  These two kernels produce the activation side: from an fp32 tensor as it is, or from GroupNorm (+ SiLU) of it (the apply pass of
 // cvar_groupnorm_silu in fp32 arithmetic with the exact quotient, as the fp32 parity mode runs it).  Cpad >= 3 C pads a pixel's row with zeros (the image conv: 3 -> 4
 // channels fp32, 12 split channels padded to 16).
-__device__ __forceinline__ void split3_store(bf16_t* __restrict__ o, const float* y, int C) {
+__device__ __forceinline__ void split3_store(bf16_t* __restrict__ o, const float* y, int C) {     // (declared in front of ln_modulate_kernel)
     float hi[4], lo[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) { const bf16_t h = f32_to_bf16(y[e]); hi[e] = bf16_to_f32(h); lo[e] = y[e] - hi[e]; }

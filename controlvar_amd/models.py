@@ -1023,6 +1023,35 @@ class _RowDraw(NamedTuple):
     sample: bool = True
 
 
+GEMM_PRECISIONS = (None, 'bf16x3')
+_X3_NO_BANK = ("gemm_precision='bf16x3': the per-request adapter bank (attach_adapters / adapter=) is not offered - its K-augmented operands [W | B_0 ...] do not "
+               "compose with the three K segments of the split product; merge one adapter with add_lora, or run the bank on gemm_precision=None")
+
+
+def _split_weight_rows(w: torch.Tensor) -> torch.Tensor:
+    """fp32 [..., N, K] -> bf16 [..., N, 3 K] rows [w_hi | w_hi | w_lo], hi = bf16(w), lo = bf16(w - hi): the weight side of the split product
+    (activation rows are [hi | lo | hi]: cvar_split3 / cvar_ln_modulate_split3)"""
+    w = w.float()
+    hi = w.to(torch.bfloat16)
+    lo = (w - hi.float()).to(torch.bfloat16)
+    return torch.cat((hi, hi, lo), dim=-1).contiguous()
+
+
+class _Pack(dict):
+    """the packed copies; `lazy` holds makers of entries that are built on first use (the fp32 matrices of a gemm_precision='bf16x3' model: only
+    forward() and training read them)"""
+
+    def __init__(self):
+        super().__init__()
+        self.lazy: Dict[str, Any] = {}
+
+    def __missing__(self, key):
+        if key not in self.lazy:
+            raise KeyError(key)
+        v = self[key] = self.lazy.pop(key)()
+        return v
+
+
 class ControlVAR(nn.Module):
     """Joint (control, image) next-scale transformer (reference: models/control_var.py:23-689).
 
@@ -1044,8 +1073,14 @@ class ControlVAR(nn.Module):
                  drop_path_rate=0., layer_scale=-1., tau=4, cos_attn=False, patch_nums=DEFAULT_PATCH_NUMS,
                  flash_if_available=True, fused_if_available=True, mask_factor=2, bidirectional=False, separate_decoding=False,
                  separator=False, type_pos=False, indep=True, multi_cond=False,
-                 compute_dtype=None, init_seed: int = 0, deterministic_plan: bool = False, sampler: str = 'counter'):
-        """deterministic_plan (an addition of this library): every transformer GEMM runs on the unsliced tile kernels whatever its row count - no small-M weight-streaming
+                 compute_dtype=None, init_seed: int = 0, deterministic_plan: bool = False, sampler: str = 'counter', gemm_precision: Optional[str] = None):
+        """gemm_precision (an addition of this library; fp32 models only; also settable: ``model.gemm_precision = 'bf16x3'``): None = the linear layers run
+        in compute_dtype; 'bf16x3' = the fp32 model with its six GEMM families (ada, qkv, proj, fc1, fc2, head) taken as split-bf16 products on the bf16
+        matrix pipe - operands carried as hi + lo in bf16, three products per multiply as three K segments of one bf16 GEMM, fp32 accumulation and fp32
+        outputs (include/cvar_serve.h).  Everything else - residual stream, adaLN, K/V arena, attention, sampler, quantizer, VQVAE - is the
+        fp32 mode's, through the same kernels.  Inference only: forward() and training on such a model run the fp32 path.
+
+        deterministic_plan (an addition of this library): every transformer GEMM runs on the unsliced tile kernels whatever its row count - no small-M weight-streaming
         kernel, no K slices - so the fp32 summation order of a row does not depend on how many rows ride beside it, and one (label, condition, g_seed) in batch row 0 gives
         the same logits and tokens BIT FOR BIT at any batch size (default False: the small-M plans are 2.0x / 1.24x / 1.05x faster at B = 1 / 8 / 32 and move bf16 logits by ~5e-3 of
         max|logit| between batch sizes; tests/test_gpu_configs.py).  Can also be flipped on a built model: ``model.deterministic_plan = True``.
@@ -1109,6 +1144,8 @@ class ControlVAR(nn.Module):
         _register_tree(self, var_state_shapes(cfg), synth_var_state(cfg, init_seed), requires_grad=True)
         self._packed = None
         self._arena = None
+        self._gemm_precision = None
+        self.gemm_precision = gemm_precision
         self.last_trace: Optional[dict] = None
 
     # ---- plumbing
@@ -1139,6 +1176,25 @@ class ControlVAR(nn.Module):
         if value not in SAMPLERS:
             raise ValueError(f'sampler must be one of {SAMPLERS}, got {value!r}')
         self._sampler = value
+
+    @property
+    def gemm_precision(self) -> Optional[str]:
+        return self._gemm_precision
+
+    @gemm_precision.setter
+    def gemm_precision(self, value: Optional[str]):
+        if value not in GEMM_PRECISIONS:
+            raise ValueError(f'gemm_precision must be one of {GEMM_PRECISIONS}, got {value!r}')
+        if value is not None and self.compute_dtype != torch.float32:
+            raise ValueError(f"gemm_precision={value!r} needs a compute_dtype=torch.float32 model: it is the fp32 model with split-bf16 linear layers, "
+                             f"and this model computes in {self.compute_dtype} (build it with compute_dtype=torch.float32)")
+        if value is not None and getattr(self, '_adapter_bank', None) is not None:
+            raise NotImplementedError(_X3_NO_BANK)
+        if value != self._gemm_precision:       # the packed matrices and the arena key belong to the mode
+            self._packed = None
+            self._packed_base = None
+            self._arena = None
+        self._gemm_precision = value
 
     @property
     def rng(self) -> torch.Generator:
@@ -1214,26 +1270,43 @@ class ControlVAR(nn.Module):
         self._pack_base_gen = getattr(self, '_pack_base_gen', 0) + 1
         return self._packed_base
 
-    def _build_pack(self, old, fresh: Sequence[str], lora):
+    def _build_pack(self, old, fresh: Sequence[str], lora, host: bool = False):
+        """host=True: build the copies where the parameters are, CPU included (the layout tests; nothing on the CPU computes with them)"""
         dev, T, cfg = self.device, self.compute_dtype, self.cfg
-        if dev.type != 'cuda':
-            raise RuntimeError('controlvar_amd models compute on the GPU only; call .to("cuda") first')
-        ops.ensure_splitk_workspace(dev)
+        if not host:
+            if dev.type != 'cuda':
+                raise RuntimeError('controlvar_amd models compute on the GPU only; call .to("cuda") first')
+            ops.ensure_splitk_workspace(dev)
         sd = {k: v.detach() for k, v in self.state_dict().items()}
         if getattr(self, '_lora', None) is not None:
             from .lora import merged_state
             sd = merged_state(sd, self._lora) if lora is not None else {k: v for k, v in sd.items() if '.lora_' not in k}
         C, depth = cfg.C, cfg.depth
-        P: Dict[str, Any] = {}
+        P: Dict[str, Any] = _Pack()
         blk = lambda i, s: sd[f'blocks.{i}.{s}']
-        P['w_qkv'] = old['w_qkv'] if 'w_qkv' in fresh else torch.stack([blk(i, 'attn.mat_qkv.weight') for i in range(depth)]).to(T).contiguous()
+        x3 = self.gemm_precision == 'bf16x3'
+
+        def matrix(key, make):
+            """one stacked weight matrix, GEMM-ready: in compute dtype, or (gemm_precision='bf16x3') as split rows [w_hi | w_hi | w_lo] under key + '_x3' - the
+            fp32 copy is then built only when forward() / training ask for it (both copies of every matrix are never held from the start)"""
+            if key in fresh:
+                P[key] = old[key]
+            elif x3:
+                P[key + '_x3'] = _split_weight_rows(make())
+                P.lazy[key] = lambda: make().to(T).contiguous()
+            else:
+                P[key] = make().to(T).contiguous()
+
+        stack = lambda name: (lambda: torch.stack([blk(i, name) for i in range(depth)]))
+        matrix('w_qkv', stack('attn.mat_qkv.weight'))
         P['b_qkv'] = torch.stack([torch.cat((blk(i, 'attn.q_bias'), torch.zeros_like(blk(i, 'attn.q_bias')), blk(i, 'attn.v_bias')))
                                   for i in range(depth)]).float().contiguous()
-        P['w_proj'] = old['w_proj'] if 'w_proj' in fresh else torch.stack([blk(i, 'attn.proj.weight') for i in range(depth)]).to(T).contiguous()
+        matrix('w_proj', stack('attn.proj.weight'))
         P['b_proj'] = torch.stack([blk(i, 'attn.proj.bias') for i in range(depth)]).float().contiguous()
-        P['w_fc1'] = old['w_fc1'] if 'w_fc1' in fresh else torch.stack([blk(i, 'ffn.fc1.weight') for i in range(depth)]).to(T).contiguous()
+        matrix('w_fc1', stack('ffn.fc1.weight'))
+        P['hid'] = blk(0, 'ffn.fc1.weight').shape[0]
         P['b_fc1'] = torch.stack([blk(i, 'ffn.fc1.bias') for i in range(depth)]).float().contiguous()
-        P['w_fc2'] = old['w_fc2'] if 'w_fc2' in fresh else torch.stack([blk(i, 'ffn.fc2.weight') for i in range(depth)]).to(T).contiguous()
+        matrix('w_fc2', stack('ffn.fc2.weight'))
         P['b_fc2'] = torch.stack([blk(i, 'ffn.fc2.bias') for i in range(depth)]).float().contiguous()
         # every ada_lin of the model in ONE weight: rows [i*6C,(i+1)*6C) = block i, last 2C rows = head_nm
         head_w, head_b = ('head.1.weight', 'head.1.bias') if cfg.sa_block else ('head.weight', 'head.bias')
@@ -1245,7 +1318,7 @@ class ControlVAR(nn.Module):
             gam = (lambda i, k: blk(i, k)) if cfg.layer_scale >= 0 else (lambda i, k: one)
             b_blk = [torch.cat([gam(i, 'gamma1'), gam(i, 'gamma2'), blk(i, 'norm1.weight') - 1, blk(i, 'norm2.weight') - 1,
                                 blk(i, 'norm1.bias'), blk(i, 'norm2.bias')]) for i in range(depth)]
-            w_all = torch.zeros(depth * 6 * C + 2 * C, C, device=dev)
+            make_ada = lambda: torch.zeros(depth * 6 * C + 2 * C, C, device=dev)
             b_all = torch.cat(b_blk + [sd['head.0.weight'] - 1, sd['head.0.bias']])
         elif cfg.shared_aln:
             # (ada_gss + SharedAdaLin(cond)) of block i (basic_var.py:204-205) == a Linear whose weight is the shared one and whose
@@ -1256,17 +1329,17 @@ class ControlVAR(nn.Module):
             w_blk = [blk(i, 'ada_lin.1.weight') for i in range(depth)]
             b_blk = [blk(i, 'ada_lin.1.bias') for i in range(depth)]
         if not cfg.sa_block:
-            w_all = None if 'w_ada' in fresh else torch.cat(w_blk + [sd['head_nm.ada_lin.1.weight']])
+            make_ada = lambda: torch.cat(w_blk + [sd['head_nm.ada_lin.1.weight']])
             b_all = torch.cat(b_blk + [sd['head_nm.ada_lin.1.bias']])
-        P['w_ada'] = old['w_ada'] if 'w_ada' in fresh else w_all.to(T).contiguous()
+        matrix('w_ada', make_ada)
         P['b_ada'] = b_all.float().contiguous()
         P['n_ada'] = depth * 6 * C + 2 * C
         hw, hb = sd[head_w], sd[head_b].float()
+        make_head = lambda: hw
         if cfg.head_ld != hw.shape[0]:               # separator: V + 18 = 4114 columns -> padded to 4120 (zero weight, -1e30 bias: softmax weight exactly 0)
-            if 'w_head' not in fresh:
-                hw = torch.cat((hw, hw.new_zeros(cfg.head_ld - hw.shape[0], hw.shape[1])))
+            make_head = lambda: torch.cat((hw, hw.new_zeros(cfg.head_ld - hw.shape[0], hw.shape[1])))
             hb = torch.cat((hb, hb.new_full((cfg.head_ld - hb.shape[0],), -1e30)))
-        P['w_head'] = old['w_head'] if 'w_head' in fresh else hw.to(T).contiguous()
+        matrix('w_head', make_head)
         P['b_head'] = hb.contiguous()
         P['special'] = sd['special_embed.weight'].float().contiguous() if cfg.separator else None
         P['sp_rows'] = {}
@@ -1337,7 +1410,7 @@ class ControlVAR(nn.Module):
         like the reference's cache of k and v only, basic_var.py:108-111) of the calling stream (generations running concurrently on
         different streams must not share it)"""
         sid = torch.cuda.current_stream(self.device).cuda_stream
-        key = (R, Lmax, self.compute_dtype)
+        key = (R, Lmax, self.compute_dtype, self.gemm_precision)
         if self._arena is None:
             self._arena = {}
         ent = self._arena.get(sid)
@@ -1346,17 +1419,22 @@ class ControlVAR(nn.Module):
         return ent[1]
 
     # ---- one pass of all blocks + head over l new tokens per sequence
-    def _blocks_and_head(self, x, ada, R: int, l: int, q_off: int, Lmax: int, arena, lvl_end=None, holes=None, ad=None):
+    def _blocks_and_head(self, x, ada, R: int, l: int, q_off: int, Lmax: int, arena, lvl_end=None, holes=None, ad=None, x3: Optional[bool] = None):
         """x: (R*l, C) fp32 residual stream (updated in place).  Returns logits (R*l, V) fp32.
         ad (per-request adapters): (lora.bank_pack, slot (R,) int32 on the device).  proj / fc1 / fc2 then run over the K-augmented weights
         [W | B_0 .. B_{n-1} | 0] with an operand that ops.lora_down_rows widened by each row's own s x A^T; without it the launches are
-        exactly the adapter-free ones."""
+        exactly the adapter-free ones.
+        x3: None = the model's gemm_precision decides; False = the compute-dtype path whatever the mode (forward(): the fp32 matrices are then built on first use)."""
         P, cfg = self._pack(), self.cfg
         C, H, T = cfg.C, cfg.H, self.compute_dtype
         M = R * l
-        hid = P['w_fc1'].shape[1]
+        hid = P['hid']
         n_ada = P['n_ada']
         dev = x.device
+        if (self.gemm_precision == 'bf16x3') if x3 is None else x3:
+            if ad is not None:
+                raise NotImplementedError(_X3_NO_BANK)
+            return self._blocks_and_head_x3(P, x, ada, R, l, q_off, Lmax, arena, lvl_end, holes)
         u = torch.empty(M, C, device=dev, dtype=T)
         o = torch.empty(M, C, device=dev, dtype=T)
         kx = 0 if ad is None else ad[0]['kx']
@@ -1414,8 +1492,61 @@ class ControlVAR(nn.Module):
         ops.gemm(u, P['w_head'], logits, M=M, N=cfg.head_ld, K=C, bias=P['b_head'], small_m=sm, split_k=sm)
         return logits
 
-    def _ada(self, cond: torch.Tensor, R: int, ad=None):
+    def _blocks_and_head_x3(self, P, x, ada, R: int, l: int, q_off: int, Lmax: int, arena, lvl_end, holes):
+        """_blocks_and_head of gemm_precision='bf16x3': the fp32 pass - fp32 residual stream, arena and query scratch, unscaled queries, the exact row-wise
+        attention - with every GEMM as ONE bf16 cvar_gemm over K' = 3 K: activation rows [hi | lo | hi] against weight rows [w_hi | w_hi | w_lo], fp32 output
+        with the fp32 mode's epilogue.  The adaLN rows leave cvar_ln_modulate_split3 split (no fp32 row); the attention output and the GELU output are fp32
+        round trips through cvar_split3 (the next lever).  ln_out of the GEMM makes bf16 / fp32 rows only, so adaLN is its own launch at every M."""
+        cfg = self.cfg
+        C, H, hid, n_ada = cfg.C, cfg.H, P['hid'], P['n_ada']
+        M, dev = R * l, x.device
+        bf, f32 = torch.bfloat16, torch.float32
+        u3 = torch.empty(M, 3 * C, device=dev, dtype=bf)            # split adaLN rows: operand of qkv / fc1 / head
+        o = torch.empty(M, C, device=dev, dtype=f32)
+        o3 = torch.empty(M, 3 * C, device=dev, dtype=bf)
+        hbuf = torch.empty(M, hid, device=dev, dtype=f32)
+        h3 = torch.empty(M, 3 * hid, device=dev, dtype=bf)
+        qs = torch.empty(M, C, device=dev, dtype=f32)
+        arena_stride = R * Lmax * 2 * C
+        sm = not self.deterministic_plan
+        ah = cfg.depth * 6 * C
+        ops.ln_modulate_split3(x, ada, 2 * C, 4 * C, n_ada, l, u3, M, C, cfg.norm_eps)
+        for i in range(cfg.depth):
+            a0 = i * 6 * C
+            ops.gemm(u3, P['w_qkv_x3'], arena, M=M, N=3 * C, K=3 * C, w_off=i * 3 * C * 3 * C, bias=P['b_qkv'][i], c_off=i * arena_stride,
+                     ldc=2 * C, remap=(l, Lmax, q_off), split=(qs, C, C), small_m=sm, split_k=sm)
+            if cfg.uses_cos_attn:
+                ops.cos_qk_norm(arena, R, H, Lmax, q_off, l, P['scale_mul'], qkv_off=i * arena_stride, sm_off=i * H, q=qs, q_mul=1.0)
+            ops.attention(arena, o, R, H, Lmax, q_off, l, float(cfg.attn_scale), lvl_end, qkv_off=i * arena_stride, holes=holes, q=qs, prescaled=False)
+            ops.split3(o, o3, M, C)
+            ops.gemm(o3, P['w_proj_x3'], x, M=M, N=C, K=3 * C, w_off=i * C * 3 * C, bias=P['b_proj'][i], gate=ada, gate_off=a0, ldg=n_ada, gate_rows=l,
+                     residual=x, small_m=sm, split_k=sm)
+            ops.ln_modulate_split3(x, ada, a0 + 3 * C, a0 + 5 * C, n_ada, l, u3, M, C, cfg.norm_eps)
+            ops.gemm(u3, P['w_fc1_x3'], hbuf, M=M, N=hid, K=3 * C, w_off=i * hid * 3 * C, bias=P['b_fc1'][i], act=ACT_GELU_TANH, small_m=sm, split_k=sm)
+            ops.split3(hbuf, h3, M, hid)
+            ops.gemm(h3, P['w_fc2_x3'], x, M=M, N=C, K=3 * hid, w_off=i * C * 3 * hid, bias=P['b_fc2'][i], gate=ada, gate_off=a0 + C, ldg=n_ada,
+                     gate_rows=l, residual=x, small_m=sm, split_k=sm)
+            a1 = a0 + 6 * C
+            sc, sh = (a1 + 2 * C, a1 + 4 * C) if i + 1 < cfg.depth else (ah, ah + C)
+            ops.ln_modulate_split3(x, ada, sc, sh, n_ada, l, u3, M, C, cfg.norm_eps)
+        logits = torch.empty(M, cfg.head_ld, device=dev, dtype=f32)
+        ops.gemm(u3, P['w_head_x3'], logits, M=M, N=cfg.head_ld, K=3 * C, bias=P['b_head'], small_m=sm, split_k=sm)
+        return logits
+
+    def _ada(self, cond: torch.Tensor, R: int, ad=None, x3: Optional[bool] = None):
         P = self._pack()
+        if (self.gemm_precision == 'bf16x3') if x3 is None else x3:
+            if ad is not None:
+                raise NotImplementedError(_X3_NO_BANK)
+            C = self.cfg.C
+            cs = torch.empty(R, C, device=cond.device, dtype=torch.float32)
+            ops.silu_cast(cond, cs)
+            cs3 = torch.empty(R, 3 * C, device=cond.device, dtype=torch.bfloat16)
+            ops.split3(cs, cs3, R, C)
+            ada = torch.empty(R, P['n_ada'], device=cond.device, dtype=torch.float32)
+            sm = not self.deterministic_plan
+            ops.gemm(cs3, P['w_ada_x3'], ada, M=R, N=P['n_ada'], K=3 * C, bias=P['b_ada'], small_m=sm, split_k=sm)
+            return ada
         cs = torch.empty(R, self.cfg.C, device=cond.device, dtype=self.compute_dtype)
         ops.silu_cast(cond, cs)
         ada = torch.empty(R, P['n_ada'], device=cond.device, dtype=torch.float32)
@@ -1556,6 +1687,8 @@ class ControlVAR(nn.Module):
         """``adapter=`` -> the slot of every sequence (host int32, nrep * B), or None when it is not given; refuses on the host"""
         if adapter is None:
             return None
+        if self.gemm_precision == 'bf16x3':
+            raise NotImplementedError(_X3_NO_BANK)
         from . import lora
         if not lora.has_adapters(self):
             raise RuntimeError('adapter=: no bank attached - call controlvar_amd.lora.attach_adapters(model, sources) first')
@@ -1936,6 +2069,8 @@ class ControlVAR(nn.Module):
             return
         if not per_request:
             raise ValueError('adapters=True needs per_request=True: the adapter slots travel with the per-request table')
+        if self.gemm_precision == 'bf16x3':
+            raise NotImplementedError(_X3_NO_BANK)
         if getattr(self, '_adapter_bank', None) is None:
             raise RuntimeError('adapters=True: no bank attached - call controlvar_amd.lora.attach_adapters(model, sources) first')
 
@@ -2291,10 +2426,10 @@ class ControlVAR(nn.Module):
         if tok.shape[1] != len(py.code_positions()) - py.first_l:
             raise AssertionError(f'teacher-forcing input has {tok.shape[1]} tokens, expected {len(py.code_positions()) - py.first_l}')       # control_var.py:617
         self._embed_teacher_forced(P, tok, x, B, table, mask_first)
-        ada = self._ada(cond, B)
+        ada = self._ada(cond, B, x3=False)              # forward() is the compute-dtype path in every gemm_precision
         arena = self._get_arena(B, py.L)
         lvl_end, holes = attention_levels(cfg)
-        logits = self._blocks_and_head(x, ada, B, py.L, 0, py.L, arena, lvl_end=lvl_end, holes=holes)
+        logits = self._blocks_and_head(x, ada, B, py.L, 0, py.L, arena, lvl_end=lvl_end, holes=holes, x3=False)
         return logits.view(B, py.L, cfg.head_ld)[:, :, :cfg.head_out]
 
 
@@ -2306,14 +2441,14 @@ class VAR(ControlVAR):
                  cond_drop_rate=0.1, depth=16, embed_dim=1024, num_heads=16, mlp_ratio=4., drop_rate=0., attn_drop_rate=0.,
                  drop_path_rate=0., layer_scale=-1., tau=4, cos_attn=False, patch_nums=DEFAULT_PATCH_NUMS,
                  flash_if_available=True, fused_if_available=True, compute_dtype=None, init_seed: int = 0, deterministic_plan: bool = False,
-                 sampler: str = 'counter'):
+                 sampler: str = 'counter', gemm_precision: Optional[str] = None):
         super().__init__(vae_local, num_classes=num_classes, norm_eps=norm_eps, aln=aln, aln_gamma_init=aln_gamma_init,
                          shared_aln=shared_aln, cond_drop_rate=cond_drop_rate, depth=depth, embed_dim=embed_dim, num_heads=num_heads,
                          mlp_ratio=mlp_ratio, drop_rate=drop_rate, attn_drop_rate=attn_drop_rate, drop_path_rate=drop_path_rate,
                          layer_scale=layer_scale, tau=tau, cos_attn=cos_attn, patch_nums=patch_nums,
                          flash_if_available=flash_if_available, fused_if_available=fused_if_available, mask_factor=1,
                          multi_cond=False, compute_dtype=compute_dtype, init_seed=init_seed, deterministic_plan=deterministic_plan,
-                         sampler=sampler)
+                         sampler=sampler, gemm_precision=gemm_precision)
 
     @torch.no_grad()
     def autoregressive_infer_cfg(self, B: int, label_B, g_seed: Optional[int] = None, cfg=1.5, top_k=0, top_p=0.0,

@@ -179,6 +179,16 @@ def ln_modulate(x: torch.Tensor, ada: torch.Tensor, scale_off: int, shift_off: i
     return out
 
 
+def ln_modulate_split3(x: torch.Tensor, ada: torch.Tensor, scale_off: int, shift_off: int, ld_ada: int, rows_per: int,
+                       out: torch.Tensor, M: int, Cdim: int, eps: float):
+    """ln_modulate with the split store: bf16 out[M][3 C] = [hi | lo | hi] of the fp32 adaLN row, bit for bit split3(ln_modulate(fp32 out))
+    (cvar_ln_modulate_split3, include/cvar_serve.h)"""
+    base = _ptr(ada)
+    check(_lib.load().cvar_ln_modulate_split3(_ptr(x), base + 4 * scale_off, base + 4 * shift_off, ld_ada, rows_per,
+                                              _ptr(out), M, Cdim, eps, _stream()), 'cvar_ln_modulate_split3')
+    return out
+
+
 def silu_cast(x: torch.Tensor, out: torch.Tensor):
     check(_lib.load().cvar_silu_cast(_ptr(x), _ptr(out), dt(out), x.numel(), _stream()), 'cvar_silu_cast')
     return out

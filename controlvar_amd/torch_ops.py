@@ -187,6 +187,27 @@ _define('ln_modulate', '(Tensor x, Tensor scale, Tensor shift, int rows_per, flo
         lambda x, scale, shift, rows_per, eps, out_dtype: x.new_empty(x.shape, dtype=out_dtype))
 
 
+def _ln_modulate_split3(x, scale, shift, rows_per, eps):
+    C = x.shape[-1]
+    x2 = x.reshape(-1, C).float().contiguous()
+    sc, sh = _rows2d(scale, C), _rows2d(shift, C)
+    if sc.stride(0) != sh.stride(0):
+        sc, sh = sc.contiguous(), sh.contiguous()
+    M = x2.shape[0]
+    if sc.shape[0] * rows_per < M:
+        raise ValueError(f'ln_modulate_split3: {sc.shape[0]} modulation rows x rows_per {rows_per} < {M} tokens')
+    out = torch.empty(M, 3 * C, device=x.device, dtype=torch.bfloat16)
+    from . import _lib
+    _lib.check(_lib.load().cvar_ln_modulate_split3(x2.data_ptr(), sc.data_ptr(), sh.data_ptr(), sc.stride(0) if sc.shape[0] > 1 else 0, rows_per,
+                                                  out.data_ptr(), M, C, eps, K._stream()), 'cvar_ln_modulate_split3')
+    return out.view(*x.shape[:-1], 3 * C)
+
+
+# inference only (the activation side of a split-bf16 product, include/cvar_serve.h): no autograd formula
+_define('ln_modulate_split3', '(Tensor x, Tensor scale, Tensor shift, int rows_per, float eps) -> Tensor', _ln_modulate_split3,
+        lambda x, scale, shift, rows_per, eps: x.new_empty((*x.shape[:-1], 3 * x.shape[-1]), dtype=torch.bfloat16))
+
+
 def _ln_modulate_bwd(x, dy, scale, rows_per, eps):
     """-> (dx, dscale (R, C), dshift (R, C)) of out = LN(x) * (1 + scale) + shift"""
     C = x.shape[-1]

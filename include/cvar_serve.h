@@ -3,8 +3,8 @@
  *
  * The functions live in the same libcvar_hip.so as those of cvar.h.  They are versioned on their own: cvar_serve_version() bumps on
  * any signature change in THIS header, cvar_abi_version() stays the version of cvar.h.  Adding an entry point changes no signature and
- * leaves the version alone: cvar_edit_force_table, cvar_cfg_sample_edit, cvar_lora_down_rows and
- * cvar_score_rows joined at version 1.
+ * leaves the version alone: cvar_edit_force_table, cvar_cfg_sample_edit, cvar_lora_down_rows,
+ * cvar_score_rows and cvar_ln_modulate_split3 joined at version 1.
  */
 #ifndef CVAR_SERVE_H
 #define CVAR_SERVE_H
@@ -120,6 +120,24 @@ int cvar_lora_down_rows(const void* x, int64_t ldx, const void* A_bank, int64_t 
 int cvar_score_rows(const float* logits, int B, int nrep, int l, int V, const float* coef /* [B][4] */,
                     const int32_t* target /* [B][ldt] */, int ldt, float* combined, float* logprob, float* entropy,
                     int32_t* rank, int32_t* argmax, int ldo, int ldv, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Split-bf16 transformer mode (`gemm_precision='bf16x3'` of an fp32 model).  Joined at version 1.
+ * The contract of the mode, stated once:
+ *   - a value x is carried as hi = bf16(x), lo = bf16(x - hi) (round to nearest even; x - hi is exact in fp32), so it is used to
+ *     |x - hi - lo| <= 2^-17 |x|;
+ *   - a product a w is taken as a_hi w_hi + a_lo w_hi + a_hi w_lo: the only dropped term is a_lo w_lo <= 2^-16 |a w|;
+ *   - the three products are three K segments of ONE bf16 cvar_gemm over K' = 3 K with an fp32 output: activation rows
+ *     [hi(K) | lo(K) | hi(K)] (lda = 3 K: what cvar_split3 and this entry point write), weight rows [w_hi(K) | w_hi(K) | w_lo(K)] (ldw = 3 K),
+ *     accumulated in fp32 in the K order of whichever bf16 kernel cvar_gemm picks for the call (segment 0 first, then 1, then 2 inside a K slice);
+ *   - everything else of the model - residual stream, adaLN table, K/V arena, attention, sampler, quantizer - is the fp32 mode's.
+ * cvar_ln_modulate_split3 is cvar_ln_modulate with that store: y = LN(x[m]) * (1 + scale) + shift in cvar_ln_modulate's fp32 arithmetic and order
+ * (one wave per row, the row in registers), then out[m] = [hi(y) | lo(y) | hi(y)], out [M][3 C] bf16.  Bit for bit
+ * cvar_split3(cvar_ln_modulate(..., CVAR_F32)) in one pass: the fp32 row is never written.
+ * Arguments and refusals as cvar_ln_modulate (C % 4 == 0, C <= 2048, ld_ada % 4 == 0; NULL pointers, M <= 0 or rows_per <= 0: CVAR_EINVAL);
+ * x, scale and shift 16-byte aligned, out 8-byte aligned.  A refused call writes nothing. */
+int cvar_ln_modulate_split3(const float* x, const float* scale, const float* shift, int64_t ld_ada, int rows_per,
+                            void* out_bf16 /* [M][3 C] */, int M, int C, float eps, void* stream);
 
 #ifdef __cplusplus
 }
