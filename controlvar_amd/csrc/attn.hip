@@ -61,7 +61,38 @@ __device__ __forceinline__ int range_full_prefix(const P& p, int pos_lo, int pos
     return best;
 }
 
-__device__ __forceinline__ int kv_len_of(const AttnParams& p, int pos) { return vis_of(p, pos).kvlen; }
+template <typename P>
+__device__ __forceinline__ int kv_len_of(const P& p, int pos) { return vis_of(p, pos).kvlen; }
+// does any level of the launch have a hole (picks the HOLES instantiations)
+template <typename P>
+static bool has_holes(const P& p) {
+    bool holes = false;
+    for (int i = 0; i < p.n_lvl; ++i) holes = holes || p.hole_lo[i] < p.hole_hi[i];
+    return holes;
+}
+
+// compile-time flags of the MFMA kernels' tile bodies (MASK, FIRST)
+typedef std::integral_constant<bool, true> Yes;
+typedef std::integral_constant<bool, false> No;
+
+// MFMA kernels, operand fragments of one 64-element head row: k-step ks of a 32x32x16 product takes the row's 16-byte chunk 2 ks + hi (hi = lane >> 5)
+__device__ __forceinline__ void load_row_frags(bf16x8_t (&f)[4], const bf16_t* row, int hi) {
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) f[ks] = *(const bf16x8_t*)(row + (2 * ks + hi) * 8);
+}
+// MFMA kernels, output tail: a lane's two 32x32 accumulator blocks (transposed products: the lane owns ONE output row, register 4 g + e of block db is its
+// element 32 db + 8 g + 4 hi + e) times a factor, as bf16
+__device__ __forceinline__ void store_acc_row(bf16_t* row, const f32x16_t (&acc)[2], float factor, int hi) {
+#pragma unroll
+    for (int db = 0; db < 2; ++db)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            float ov[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) ov[e] = acc[db][4 * g + e] * factor;
+            *(bf16x4_t*)(row + 32 * db + 8 * g + 4 * hi) = pack_bf16x4(ov);
+        }
+}
 
 template <typename T>
 __global__ __launch_bounds__(256) void attn_rowwise_kernel(const AttnParams p) {
@@ -162,9 +193,8 @@ __global__ __launch_bounds__(256) void attn_rowwise_kernel(const AttnParams p) {
 }
 
 // (a template takes its launch bounds from the FIRST declaration: without them here the kernels are compiled for 1024-thread groups, 128 VGPRs)
-template <bool HOLES, bool QPRE> __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void attn_mfma_bf16_kernel(const AttnParams p);
+template <bool HOLES, bool QPRE, int G> __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(G == 1 ? 3 : 2, G == 1 ? 3 : 2))) void attn_mfma_bf16_kernel(const AttnParams p);
 template <bool HOLES> __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void attn_mfma_bf16_v1_kernel(const AttnParams p);
-template <bool HOLES> __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_mfma_bf16_q64_kernel(const AttnParams p);
 #ifndef CVAR_ATTN_Q64
 #define CVAR_ATTN_Q64 1
 #endif
@@ -196,6 +226,22 @@ static int fill_levels(P& p, const int* lvl_end_host, int n_lvl, const int* hole
     return CVAR_OK;
 }
 
+// launch of the bf16 MFMA forward: picks QPRE and G (the v1 kernel has neither)
+template <bool HOLES>
+static void launch_attn_mfma(const AttnParams& p, bool qpre, bool v1, hipStream_t st) {
+    const dim3 block(256);
+    if (v1) { hipLaunchKernelGGL(attn_mfma_bf16_v1_kernel<HOLES>, dim3(cdiv(p.l, 128), p.H, p.R), block, 0, st, p); return; }
+    // prescaled queries, long scales: 64 queries per wave (K / V fragments, tiles and barriers shared by two query groups)
+    // (only where the last 256-query workgroup is nearly full: l = 512 runs 1.371 -> 1.285 ms per call at B = 128, l = 338 - 82 queries in its second workgroup -
+    //  0.685 -> 0.82 ms and stays on 32 queries per wave; profiles/r04_attn_ablation.txt)
+    // and only where the halved workgroup count still fills the chip twice over (a B = 1 generation has 48 (row, head) pairs)
+    const bool g2 = CVAR_ATTN_Q64 && qpre && p.l >= CVAR_ATTN_Q64_MINL && cdiv(p.l, 256) * 256 - p.l < 64 && (long)cdiv(p.l, 256) * p.H * p.R >= 512;
+    const dim3 grid((unsigned)((long)cdiv(p.l, g2 ? 256 : 128) * p.H * p.R));
+    if (g2) hipLaunchKernelGGL((attn_mfma_bf16_kernel<HOLES, true, 2>), grid, block, 0, st, p);
+    else if (qpre) hipLaunchKernelGGL((attn_mfma_bf16_kernel<HOLES, true, 1>), grid, block, 0, st, p);
+    else hipLaunchKernelGGL((attn_mfma_bf16_kernel<HOLES, false, 1>), grid, block, 0, st, p);
+}
+
 static int cvar_attention_impl(const void* qkv, const void* q, int dtype, int R, int H, int Lmax, int q_off, int l, float scale,
                                const int* lvl_end_host, int n_lvl, const int* hole_host, void* out, float* lse, void* stream, int impl) {
     if (!qkv || !out || R <= 0 || H <= 0 || l <= 0 || q_off < 0 || q_off + l > Lmax) return CVAR_EINVAL;
@@ -217,33 +263,11 @@ static int cvar_attention_impl(const void* qkv, const void* q, int dtype, int R,
         for (int i = 0; i < p.n_lvl; ++i)
             if (p.hole_lo[i] <= 0 && p.hole_hi[i] >= 64) return CVAR_EUNSUPPORTED;
     if (dtype == CVAR_BF16 && impl != 1) {
-        bool holes = false;
-        for (int i = 0; i < p.n_lvl; ++i) holes = holes || p.hole_lo[i] < p.hole_hi[i];
-        if (impl == 2) {                                   // round-2 kernel (A/B reference)
-            if (qpre) return CVAR_EUNSUPPORTED;
-            if (holes) hipLaunchKernelGGL(attn_mfma_bf16_v1_kernel<true>, dim3(cdiv(l, 128), H, R), dim3(256), 0, as_stream(stream), p);
-            else hipLaunchKernelGGL(attn_mfma_bf16_v1_kernel<false>, dim3(cdiv(l, 128), H, R), dim3(256), 0, as_stream(stream), p);
-            CVAR_CHECK_LAUNCH();
-            return CVAR_OK;
-        }
-        const long nblk = (long)cdiv(l, 128) * H * R;
-        if (nblk > 0x7fffffffL) return CVAR_EUNSUPPORTED;
-        const dim3 grid((unsigned)nblk), block(256);
-        // prescaled queries, long scales: 64 queries per wave (K / V fragments, tiles and barriers shared by two query groups)
-        // (only where the last 256-query workgroup is nearly full: l = 512 runs 1.371 -> 1.285 ms per call at B = 128, l = 338 - 82 queries in its second workgroup -
-        //  0.685 -> 0.82 ms and stays on the 128-query kernel; profiles/r04_attn_ablation.txt)
-        // and only where the halved workgroup count still fills the chip twice over (a B = 1 generation has 48 (row, head) pairs)
-        if (CVAR_ATTN_Q64 && qpre && l >= CVAR_ATTN_Q64_MINL && cdiv(l, 256) * 256 - l < 64 && (long)cdiv(l, 256) * H * R >= 512) {
-            const dim3 grid64((unsigned)((long)cdiv(l, 256) * H * R));
-            if (holes) hipLaunchKernelGGL((attn_mfma_bf16_q64_kernel<true>), grid64, block, 0, as_stream(stream), p);
-            else hipLaunchKernelGGL((attn_mfma_bf16_q64_kernel<false>), grid64, block, 0, as_stream(stream), p);
-            CVAR_CHECK_LAUNCH();
-            return CVAR_OK;
-        }
-        if (holes) { if (qpre) hipLaunchKernelGGL((attn_mfma_bf16_kernel<true, true>), grid, block, 0, as_stream(stream), p);
-                     else hipLaunchKernelGGL((attn_mfma_bf16_kernel<true, false>), grid, block, 0, as_stream(stream), p); }
-        else { if (qpre) hipLaunchKernelGGL((attn_mfma_bf16_kernel<false, true>), grid, block, 0, as_stream(stream), p);
-               else hipLaunchKernelGGL((attn_mfma_bf16_kernel<false, false>), grid, block, 0, as_stream(stream), p); }
+        const bool v1 = impl == 2;                         // round-2 kernel (A/B reference)
+        if (v1 && qpre) return CVAR_EUNSUPPORTED;
+        if (!v1 && (long)cdiv(l, 128) * H * R > 0x7fffffffL) return CVAR_EUNSUPPORTED;        // 1-D grid
+        if (has_holes(p)) launch_attn_mfma<true>(p, qpre, v1, as_stream(stream));
+        else launch_attn_mfma<false>(p, qpre, v1, as_stream(stream));
         CVAR_CHECK_LAUNCH();
         return CVAR_OK;
     }
@@ -296,11 +320,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     const int kv_end = kv_len_of(p, p.q_off + min(p.l, (int)(blockIdx.x + 1) * 128) - 1);
 
     bf16x8_t qf[4];
-    {
-        const bf16_t* qp = (const bf16_t*)p.q + (r * p.q_rows + (p.q_off + qrow - p.q_pos0)) * (long)p.ldq + h * D;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) qf[ks] = *(const bf16x8_t*)(qp + (2 * ks + hi) * 8);
-    }
+    load_row_frags(qf, (const bf16_t*)p.q + (r * p.q_rows + (p.q_off + qrow - p.q_pos0)) * (long)p.ldq + h * D, hi);
     // staging maps
     const int k_key = tid >> 3, k_chunk = tid & 7;                       // K: keys k_key and k_key+32, chunk k_chunk
     const int v_kp = 16 * (w >> 1) + (lane & 15), v_chunk = 4 * (w & 1) + (lane >> 4);   // V: keys 2*v_kp, 2*v_kp+1
@@ -408,36 +428,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
                 }
         __syncthreads();
     };
-    typedef std::integral_constant<bool, true> MaskOn;
-    typedef std::integral_constant<bool, false> MaskOff;
     load_tile(0);
     int kt0 = 0;
     // wave_min_kv is wave-uniform per construction but tiles are shared by the workgroup (barriers inside): the split point
     // must be the same for all four waves, so it is taken over the workgroup's first query
     const int wg_min_kv = range_full_prefix(p, p.q_off + min((int)blockIdx.x * 128, p.l - 1), p.q_off + min(p.l, (int)(blockIdx.x + 1) * 128) - 1);
-    for (; kt0 + KT <= wg_min_kv && kt0 < kv_end; kt0 += KT) tile(kt0, MaskOff{});
-    for (; kt0 < kv_end; kt0 += KT) tile(kt0, MaskOn{});
+    for (; kt0 + KT <= wg_min_kv && kt0 < kv_end; kt0 += KT) tile(kt0, No{});
+    for (; kt0 < kv_end; kt0 += KT) tile(kt0, Yes{});
     lsum += __shfl_xor(lsum, 32, 64);
     if (qi < p.l) {
         if (p.lse && hi == 0) p.lse[(r * p.H + h) * (long)p.l + qi] = (m + log2f(lsum)) * 0.6931471805599453f;
-        const float inv = 1.0f / lsum;
-        bf16_t* op = (bf16_t*)p.out + (r * p.l + qi) * (long)(p.H * D) + h * D;
-#pragma unroll
-        for (int db = 0; db < 2; ++db)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                float ov[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) ov[e] = o[db][4 * g + e] * inv;
-                *(bf16x4_t*)(op + 32 * db + 8 * g + 4 * hi) = pack_bf16x4(ov);
-            }
+        store_acc_row((bf16_t*)p.out + (r * p.l + qi) * (long)(p.H * D) + h * D, o, 1.0f / lsum, hi);
     }
 }
 
 // ================================================================================================
 // attn_mfma_bf16_kernel: flash-style attention on the matrix cores (bf16 in, fp32 accumulate), head_dim 64.
 //
-// Per workgroup: 4 waves x 32 queries of one (row, head); KV tiles of 64 keys.  Per wave and tile:
+// Per workgroup: 4 waves x G groups of 32 queries of one (row, head) - 128 G queries; KV tiles of 64 keys.  Per wave, group and tile:
 //   S^T = K . Q^T   (swapped product: each lane then holds 32 scores of ONE query -> the row max / row sum are
 //                    31 in-lane ops + one cross-half shuffle, no LDS)
 //   P   = 2^(...)   in fp32, packed to bf16 straight into the B-operand layout of the next product
@@ -457,6 +465,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 //   instead of those plus one fma - the vector pipe is what bounds this kernel (VALU-busy 81 %, MFMA-busy 32 % in round 2), the matrix
 //   pipe has room for the 2 extra MFMAs per tile.  m~ moves only when a tile's maximum exceeds it by more than THR (= 2 + |m~|/64 in the
 //   log2 domain: P <= 4 ... ), then the tile's scores, O and the row sum are shifted by the same exact delta.
+// G = 2 (round 4, second half; QPRE only, scales of >= 256 queries - the rule is in launch_attn_mfma): TWO 32-query groups per wave, a workgroup owns 256
+//   queries.  Every K fragment read out of LDS, every transposed V fragment, every K / V tile a CU pulls and every barrier then serve 64 queries of the wave
+//   instead of 32: the ablation table (profiles/r04_attn_ablation.txt) puts the tile traffic at 23 % and the kernel at ~13 B per clock and CU.  Costs ~100
+//   registers: two waves per SIMD instead of three (<= 168 VGPRs: the softmax phase of one wave overlaps the MFMA phases of the other two, +10 % over 2).
+//   Same arithmetic per query as G = 1 (same tile order, same shift rule per 32-query group): bit-identical output.
 // Workgroup -> (query block, head, row): 1-D grid; the query blocks of one (row, head) - which stream the same K/V - are given block
 //   ids congruent mod 8, i.e. the same XCD / L2, and adjacent in dispatch order.
 // ================================================================================================
@@ -465,10 +478,10 @@ __device__ __forceinline__ s16x4_t lds_tr16_b64(const char* lds_ptr) {
     return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)lds_ptr);
 }
 
-// 3 waves per SIMD (<= 168 VGPRs): the softmax phase of one wave overlaps the MFMA phases of the other two (+10 % over 2)
-template <bool HOLES, bool QPRE>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void attn_mfma_bf16_kernel(const AttnParams p) {
-    constexpr int D = 64, KT = 64;
+template <bool HOLES, bool QPRE, int G>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(G == 1 ? 3 : 2, G == 1 ? 3 : 2))) void attn_mfma_bf16_kernel(const AttnParams p) {
+    static_assert(G == 1 || (G == 2 && QPRE), "two query groups per wave: prescaled queries only");
+    constexpr int D = 64, KT = 64, QB = 128 * G;         // QB: queries per workgroup
     // one K and one V tile, two barriers per tile.  (Two buffers and one barrier per tile: 7 % SLOWER - profiles/r03_attn_ab3_lds_double_buffer_rejected.txt.)
     constexpr int TILE_B = KT * 128;
     __shared__ __attribute__((aligned(1024))) char KVs[2 * TILE_B];
@@ -477,7 +490,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int lrow = lane & 31, hi = lane >> 5, sw = (lane >> 1) & 7;
     // ---- block id -> (query block, pair = row * H + head)
-    const int nqb = (p.l + 127) >> 7, pairs = p.R * p.H;
+    const int nqb = (unsigned)(p.l + QB - 1) / QB, pairs = p.R * p.H;
     int qb, pair;
     {
         const int id = blockIdx.x;
@@ -491,19 +504,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     const bf16_t* kbase = base + p.k_col + h * D;
     const bf16_t* vbase = base + p.v_col + h * D;
 
-    const int q0 = qb * 128 + w * 32;
+    const int q0 = qb * QB + w * 32 * G;
     const bool active = q0 < p.l;                     // a wave without a single query of the scale only helps staging the tiles
-    const int qi = q0 + lrow;
-    const int qrow = min(qi, p.l - 1);
-    const Vis vis = vis_of(p, p.q_off + qrow);
-    const int kv_end = kv_len_of(p, p.q_off + min(p.l, (qb + 1) * 128) - 1);
-
-    bf16x8_t qf[4];
-    {
-        const bf16_t* qp = (const bf16_t*)p.q + (r * p.q_rows + (p.q_off + qrow - p.q_pos0)) * (long)p.ldq + h * D;
+    int qi[G];
+    Vis vis[G];
+    bf16x8_t qf[G][4];
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks) qf[ks] = *(const bf16x8_t*)(qp + (2 * ks + hi) * 8);
+    for (int g = 0; g < G; ++g) {
+        qi[g] = q0 + 32 * g + lrow;
+        const int qrow = min(qi[g], p.l - 1);
+        vis[g] = vis_of(p, p.q_off + qrow);
+        load_row_frags(qf[g], (const bf16_t*)p.q + (r * p.q_rows + (p.q_off + qrow - p.q_pos0)) * (long)p.ldq + h * D, hi);
     }
+    const int kv_end = kv_len_of(p, p.q_off + min(p.l, (qb + 1) * QB) - 1);
+
     // staging map (K and V alike): thread -> keys k_key and k_key + 32, 16-byte chunk k_chunk of the 128-byte head row
     const int k_key = tid >> 3, k_chunk = tid & 7;
     bf16x8_t kreg[2], vreg[2];
@@ -541,18 +555,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 #pragma unroll
     for (int db = 0; db < 2; ++db) v_lane[db] = Vs + (4 * hi + v_jrow) * 128 + (((2 * db + v_g) ^ v_jrow) << 5) + (lane & 3) * 8;
 
-    f32x16_t o[2];
-#pragma unroll
-    for (int db = 0; db < 2; ++db)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) o[db][i] = 0.f;
-    float m = QPRE ? 0.f : -INFINITY;                      // QPRE: m~ (a bf16 value), the shift the bias k-step applies
-    const float c2 = p.scale * 1.4426950408889634f;
-    float lsum = 0.f;
+    f32x16_t o[G][2];
+    float m[G], lsum[G];                                   // QPRE: m is m~ (a bf16 value), the shift the bias k-step applies
     // QPRE: operands of the bias k-step.  A: k index 0 is a column of ones (lanes hi == 0, element 0), B: k index 0 holds -m~ of the lane's query
     const short one_bf = hi == 0 ? (short)0x3f80 : (short)0;
     const bf16x8_t k_ones = {one_bf, 0, 0, 0, 0, 0, 0, 0};
-    bf16x8_t q_m = {0, 0, 0, 0, 0, 0, 0, 0};
+    bf16x8_t q_m[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+#pragma unroll
+        for (int db = 0; db < 2; ++db)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) o[g][db][i] = 0.f;
+        m[g] = QPRE ? 0.f : -INFINITY;
+        lsum[g] = 0.f;
+        q_m[g] = bf16x8_t{0, 0, 0, 0, 0, 0, 0, 0};
+    }
+    const float c2 = p.scale * 1.4426950408889634f;
 
     // One KV tile.  MASK is a compile-time flag: tiles that every query of the wave sees completely (all but the last one at
     // inference, all but the level-boundary ones under the training mask) run without any per-score compare / select - left
@@ -562,261 +581,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         __syncthreads();
         if (kt0 + KT < kv_end) load_tile(kt0 + KT);
         if (active) {
-        // ---- S^T = K Q^T (+ the bias k-step: - m~), invisible keys -> -inf
-        f32x16_t s[2];
-        auto scores = [&]() {
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb) {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) s[kb][i] = 0.f;
-                if constexpr (QPRE && !decltype(FIRST)::value) s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k_ones, q_m, s[kb], 0, 0, 0);
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) {
-                    const bf16x8_t kf = *(const bf16x8_t*)(Ks + (32 * kb + lrow) * 128 + (((2 * ks + hi) ^ sw) << 4));
-                    s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], s[kb], 0, 0, 0);
-                }
-            }
-            if constexpr (decltype(MASK)::value) {
-#pragma unroll
-                for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) {
-                        const int key = kt0 + 32 * kb + (i & 3) + 8 * (i >> 2) + 4 * hi;
-                        if (!vis_key_t<HOLES>(vis, key)) s[kb][i] = -INFINITY;
-                    }
-            }
-        };
-        auto row_max = [&]() {
-            float tmax = -INFINITY;
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) tmax = fmaxf(tmax, s[kb][i]);
-            return fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-        };
-        bf16x8_t pf[2][2];
-        scores();
-        if constexpr (QPRE) {
-            // The accumulators hold s - m~ (log2 domain) and P = 2^that.  m~ is set by the first tile (its exact maximum, rounded to bf16) and
-            // moves later only when a tile's maximum exceeds it by more than 2 + |m~|/64; everything still at the old shift - the tile's
-            // scores, O, the row sum - then moves by the same delta = m~_new - m~_old (both bf16 values: the fp32 difference is exact).
-            auto shift = [&](bool always) {
-                const float tmax = row_max();
-                const bool need = always || tmax > 2.0f + fabsf(m) * 0.015625f;
-                const float m_new = need ? bf16_to_f32(f32_to_bf16(m + tmax)) : m;
-                const float delta = m_new - m;
-                if (!always) {           // the first tile has nothing to rescale (O = row sum = 0) - and its delta may be hugely NEGATIVE (every score
-                                         // far below zero): 2^-delta would be +inf and 0 * inf a NaN.  Later deltas are >= 0: alpha <= 1.
-                    const float alpha = __builtin_amdgcn_exp2f(-delta);
-                    lsum *= alpha;
-#pragma unroll
-                    for (int db = 0; db < 2; ++db)
-#pragma unroll
-                        for (int i = 0; i < 16; ++i) o[db][i] *= alpha;
-                }
-#pragma unroll
-                for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) s[kb][i] -= delta;
-                m = m_new;
-                q_m[0] = hi == 0 ? (short)f32_to_bf16(-m_new) : (short)0;
-            };
-            // (Tried and rejected, profiles/r03_attn_ab4_optimistic_max_rejected.txt: no maximum at all on the hot path - P is bounded by the
-            // tile's row sum, a wave-uniform test of the sum sends the rare tile through a careful second pass.  16 v_max3 fewer per tile,
-            // but the second copy of the tile body costs registers (spills around the loops) and the short scales lose 20-30 %.)
-            if (decltype(FIRST)::value) shift(true);
-            else if (__any(row_max() > 2.0f + fabsf(m) * 0.015625f)) shift(false);
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    float pr[8];
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        pr[j] = __builtin_amdgcn_exp2f(s[kb][8 * t + j]);
-                        lsum += pr[j];
-                    }
-                    pf[kb][t] = pack_bf16x8(pr);
-                }
-        } else {
-            // softmax bookkeeping in the exp2 domain: p = 2^(s*c - m), c = scale*log2(e)  (one fma + one v_exp_f32 per score)
-            const float tmax = row_max();
-            float m_new = fmaxf(m, tmax * c2);                  // c2 > 0; without holes finite from the first tile on (key 0 is visible)
-            if constexpr (HOLES) m_new = fmaxf(m_new, FA_M_FLOOR);      // see FA_M_FLOOR
-            if (!__all(m_new == m)) {                           // rescale only when some row's running max moved (exact skip)
-                const float alpha = __builtin_amdgcn_exp2f(m - m_new);
-                lsum *= alpha;
-#pragma unroll
-                for (int db = 0; db < 2; ++db)
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) o[db][i] *= alpha;
-                m = m_new;
-            }
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    float pr[8];
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        pr[j] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[kb][8 * t + j], c2, -m));
-                        lsum += pr[j];
-                    }
-                    pf[kb][t] = pack_bf16x8(pr);
-                }
-        }
-        // ---- O^T += V^T P^T
-#pragma unroll
-        for (int db = 0; db < 2; ++db)
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    const char* vp = v_lane[db] + (32 * kb + 16 * t) * 128;
-                    const s16x4_t v0 = lds_tr16_b64(vp);
-                    const s16x4_t v1 = lds_tr16_b64(vp + 8 * 128);
-                    const bf16x8_t vf = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-                    o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf[kb][t], o[db], 0, 0, 0);
-                }
-        }
-        __syncthreads();
-    };
-    typedef std::integral_constant<bool, true> Yes;
-    typedef std::integral_constant<bool, false> No;
-    load_tile(0);
-    int kt0 = 0;
-    // wave_min_kv is wave-uniform per construction but tiles are shared by the workgroup (barriers inside): the split point
-    // must be the same for all four waves, so it is taken over the workgroup's first query
-    const int wg_min_kv = range_full_prefix(p, p.q_off + min(qb * 128, p.l - 1), p.q_off + min(p.l, (qb + 1) * 128) - 1);
-    if constexpr (QPRE) {                                  // the first tile sets m~ unconditionally
-        if (KT <= wg_min_kv) tile(0, No{}, Yes{}); else tile(0, Yes{}, Yes{});
-        kt0 = KT;
-    }
-    for (; kt0 + KT <= wg_min_kv && kt0 < kv_end; kt0 += KT) tile(kt0, No{}, No{});
-    for (; kt0 < kv_end; kt0 += KT) tile(kt0, Yes{}, No{});
-    lsum += __shfl_xor(lsum, 32, 64);
-    if (qi < p.l) {
-        if (p.lse && hi == 0) p.lse[(r * p.H + h) * (long)p.l + qi] = (m + log2f(lsum)) * 0.6931471805599453f;
-        const float inv = 1.0f / lsum;
-        bf16_t* op = (bf16_t*)p.out + (r * p.l + qi) * (long)(p.H * D) + h * D;
-#pragma unroll
-        for (int db = 0; db < 2; ++db)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                float ov[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) ov[e] = o[db][4 * g + e] * inv;
-                *(bf16x4_t*)(op + 32 * db + 8 * g + 4 * hi) = pack_bf16x4(ov);
-            }
-    }
-}
-
-
-// ================================================================================================
-// attn_mfma_bf16_q64_kernel (round 4, second half; inference form with prescaled queries, scales of >= 256 queries): the QPRE kernel above with TWO 32-query
-// groups per wave - a workgroup owns 256 queries of one (row, head).  Every K fragment read out of LDS, every transposed V fragment, every K / V tile a CU
-// pulls and every barrier now serve 64 queries of the wave instead of 32: the ablation table (profiles/r04_attn_ablation.txt) puts the tile traffic at 23 %
-// and the kernel at ~13 B per clock and CU.  Costs ~100 registers: two waves per SIMD instead of three.  Same arithmetic per query as the kernel above
-// (same tile order, same shift rule per 32-query group): bit-identical output.
-// ================================================================================================
-template <bool HOLES>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_mfma_bf16_q64_kernel(const AttnParams p) {
-    constexpr int D = 64, KT = 64, G = 2;
-    constexpr int TILE_B = KT * 128;
-    __shared__ __attribute__((aligned(16))) char KVs[2 * TILE_B];
-    char* const Ks = KVs;
-    char* const Vs = KVs + TILE_B;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int lrow = lane & 31, hi = lane >> 5, sw = (lane >> 1) & 7;
-    const int nqb = (p.l + 255) >> 8, pairs = p.R * p.H;
-    int qb, pair;
-    {
-        const int id = blockIdx.x;
-        if ((pairs & 7) == 0) { const int xcd = id & 7, local = id >> 3; qb = local % nqb; pair = (local / nqb) * 8 + xcd; }
-        else { qb = id % nqb; pair = id / nqb; }
-    }
-    const int h = pair % p.H;
-    const long r = pair / p.H;
-    const int C3 = p.ldkv;
-    const bf16_t* base = (const bf16_t*)p.qkv + r * (long)p.Lmax * C3;
-    const bf16_t* kbase = base + p.k_col + h * D;
-    const bf16_t* vbase = base + p.v_col + h * D;
-
-    const int q0 = qb * 256 + w * 64;
-    const bool active = q0 < p.l;
-    int qi[G];
-    Vis vis[G];
-    bf16x8_t qf[G][4];
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        qi[g] = q0 + 32 * g + lrow;
-        const int qrow = min(qi[g], p.l - 1);
-        vis[g] = vis_of(p, p.q_off + qrow);
-        const bf16_t* qp = (const bf16_t*)p.q + (r * p.q_rows + (p.q_off + qrow - p.q_pos0)) * (long)p.ldq + h * D;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) qf[g][ks] = *(const bf16x8_t*)(qp + (2 * ks + hi) * 8);
-    }
-    const int kv_end = kv_len_of(p, p.q_off + min(p.l, (qb + 1) * 256) - 1);
-
-    const int k_key = tid >> 3, k_chunk = tid & 7;
-    bf16x8_t kreg[2], vreg[2];
-    const int row_bytes = C3 * 2;
-    const int rec = (kv_end - 1) * row_bytes + 128;
-    const __amdgpu_buffer_rsrc_t k_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)kbase, 0, rec, 0x00020000);
-    const __amdgpu_buffer_rsrc_t v_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)vbase, 0, rec, 0x00020000);
-    int ld_off[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) ld_off[i] = (k_key + 32 * i) * row_bytes + k_chunk * 16;
-    typedef int v4i_t __attribute__((ext_vector_type(4)));
-    auto load_tile = [&](int kt0) {
-        const int so = kt0 * row_bytes;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            kreg[i] = __builtin_bit_cast(bf16x8_t, (v4i_t)__builtin_amdgcn_raw_buffer_load_b128(k_rsrc, ld_off[i], so, 0));
-            vreg[i] = __builtin_bit_cast(bf16x8_t, (v4i_t)__builtin_amdgcn_raw_buffer_load_b128(v_rsrc, ld_off[i], so, 0));
-        }
-    };
-    auto store_tile = [&]() {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int key = k_key + 32 * i;
-            *(bf16x8_t*)(Ks + key * 128 + ((k_chunk ^ ((key >> 1) & 7)) << 4)) = kreg[i];
-            *(bf16x8_t*)(Vs + key * 128 + ((((k_chunk >> 1) ^ (key & 3)) << 5) | ((k_chunk & 1) << 4))) = vreg[i];
-        }
-    };
-    const int v_jrow = (lane & 15) >> 2, v_g = (lane >> 4) & 1;
-    const char* v_lane[2];
-#pragma unroll
-    for (int db = 0; db < 2; ++db) v_lane[db] = Vs + (4 * hi + v_jrow) * 128 + (((2 * db + v_g) ^ v_jrow) << 5) + (lane & 3) * 8;
-
-    f32x16_t o[G][2];
-#pragma unroll
-    for (int g = 0; g < G; ++g)
-#pragma unroll
-        for (int db = 0; db < 2; ++db)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) o[g][db][i] = 0.f;
-    float m[G] = {0.f, 0.f}, lsum[G] = {0.f, 0.f};
-    const short one_bf = hi == 0 ? (short)0x3f80 : (short)0;
-    const bf16x8_t k_ones = {one_bf, 0, 0, 0, 0, 0, 0, 0};
-    bf16x8_t q_m[G];
-#pragma unroll
-    for (int g = 0; g < G; ++g) q_m[g] = bf16x8_t{0, 0, 0, 0, 0, 0, 0, 0};
-
-    auto tile = [&](int kt0, auto MASK, auto FIRST) {
-        store_tile();
-        __syncthreads();
-        if (kt0 + KT < kv_end) load_tile(kt0 + KT);
-        if (active) {
+        // ---- S^T = K Q^T (+ the bias k-step: - m~) for all G query groups off ONE K fragment
         f32x16_t s[G][2];
-        // ---- S^T = K Q^T for both query groups off ONE K fragment
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
 #pragma unroll
             for (int g = 0; g < G; ++g) {
 #pragma unroll
                 for (int i = 0; i < 16; ++i) s[g][kb][i] = 0.f;
-                if constexpr (!decltype(FIRST)::value) s[g][kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k_ones, q_m[g], s[g][kb], 0, 0, 0);
+                if constexpr (QPRE && !decltype(FIRST)::value) s[g][kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k_ones, q_m[g], s[g][kb], 0, 0, 0);
             }
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
@@ -825,6 +598,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 for (int g = 0; g < G; ++g) s[g][kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[g][ks], s[g][kb], 0, 0, 0);
             }
         }
+        // ---- softmax of each group: invisible keys -> -inf, running maximum, P = 2^(...) packed to bf16
         bf16x8_t pf[G][2][2];
 #pragma unroll
         for (int g = 0; g < G; ++g) {
@@ -845,28 +619,46 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     for (int i = 0; i < 16; ++i) tmax = fmaxf(tmax, s[g][kb][i]);
                 return fmaxf(tmax, __shfl_xor(tmax, 32, 64));
             };
-            auto shift = [&](bool always) {
-                const float tmax = row_max();
-                const bool need = always || tmax > 2.0f + fabsf(m[g]) * 0.015625f;
-                const float m_new = need ? bf16_to_f32(f32_to_bf16(m[g] + tmax)) : m[g];
-                const float delta = m_new - m[g];
-                if (!always) {
-                    const float alpha = __builtin_amdgcn_exp2f(-delta);
-                    lsum[g] *= alpha;
+            auto rescale = [&](float alpha) {               // the row sum and O move to a new shift
+                lsum[g] *= alpha;
 #pragma unroll
-                    for (int db = 0; db < 2; ++db)
+                for (int db = 0; db < 2; ++db)
 #pragma unroll
-                        for (int i = 0; i < 16; ++i) o[g][db][i] *= alpha;
-                }
-#pragma unroll
-                for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) s[g][kb][i] -= delta;
-                m[g] = m_new;
-                q_m[g][0] = hi == 0 ? (short)f32_to_bf16(-m_new) : (short)0;
+                    for (int i = 0; i < 16; ++i) o[g][db][i] *= alpha;
             };
-            if (decltype(FIRST)::value) shift(true);
-            else if (__any(row_max() > 2.0f + fabsf(m[g]) * 0.015625f)) shift(false);
+            if constexpr (QPRE) {
+                // The accumulators hold s - m~ (log2 domain) and P = 2^that.  m~ is set by the first tile (its exact maximum, rounded to bf16) and
+                // moves later only when a tile's maximum exceeds it by more than 2 + |m~|/64; everything still at the old shift - the tile's
+                // scores, O, the row sum - then moves by the same delta = m~_new - m~_old (both bf16 values: the fp32 difference is exact).
+                auto shift = [&](bool always) {
+                    const float tmax = row_max();
+                    const bool need = always || tmax > 2.0f + fabsf(m[g]) * 0.015625f;
+                    const float m_new = need ? bf16_to_f32(f32_to_bf16(m[g] + tmax)) : m[g];
+                    const float delta = m_new - m[g];
+                    // the first tile has nothing to rescale (O = row sum = 0) - and its delta may be hugely NEGATIVE (every score far below
+                    // zero): 2^-delta would be +inf and 0 * inf a NaN.  Later deltas are >= 0: alpha <= 1.
+                    if (!always) rescale(__builtin_amdgcn_exp2f(-delta));
+#pragma unroll
+                    for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                        for (int i = 0; i < 16; ++i) s[g][kb][i] -= delta;
+                    m[g] = m_new;
+                    q_m[g][0] = hi == 0 ? (short)f32_to_bf16(-m_new) : (short)0;
+                };
+                // (Tried and rejected, profiles/r03_attn_ab4_optimistic_max_rejected.txt: no maximum at all on the hot path - P is bounded by the
+                // tile's row sum, a wave-uniform test of the sum sends the rare tile through a careful second pass.  16 v_max3 fewer per tile,
+                // but the second copy of the tile body costs registers (spills around the loops) and the short scales lose 20-30 %.)
+                if (decltype(FIRST)::value) shift(true);
+                else if (__any(row_max() > 2.0f + fabsf(m[g]) * 0.015625f)) shift(false);
+            } else {
+                // softmax bookkeeping in the exp2 domain: p = 2^(s*c - m), c = scale*log2(e)  (one fma + one v_exp_f32 per score)
+                float m_new = fmaxf(m[g], row_max() * c2);          // c2 > 0; without holes finite from the first tile on (key 0 is visible)
+                if constexpr (HOLES) m_new = fmaxf(m_new, FA_M_FLOOR);      // see FA_M_FLOOR
+                if (!__all(m_new == m[g])) {                        // rescale only when some row's running max moved (exact skip)
+                    rescale(__builtin_amdgcn_exp2f(m[g] - m_new));
+                    m[g] = m_new;
+                }
+            }
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
@@ -874,13 +666,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     float pr[8];
 #pragma unroll
                     for (int j = 0; j < 8; ++j) {
-                        pr[j] = __builtin_amdgcn_exp2f(s[g][kb][8 * t + j]);
+                        float x = s[g][kb][8 * t + j];
+                        if constexpr (!QPRE) x = __builtin_fmaf(x, c2, -m[g]);
+                        pr[j] = __builtin_amdgcn_exp2f(x);
                         lsum[g] += pr[j];
                     }
                     pf[g][kb][t] = pack_bf16x8(pr);
                 }
         }
-        // ---- O^T += V^T P^T for both groups off ONE transposed V fragment
+        // ---- O^T += V^T P^T for all G groups off ONE transposed V fragment
 #pragma unroll
         for (int db = 0; db < 2; ++db)
 #pragma unroll
@@ -897,13 +691,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         }
         __syncthreads();
     };
-    typedef std::integral_constant<bool, true> Yes;
-    typedef std::integral_constant<bool, false> No;
     load_tile(0);
     int kt0 = 0;
-    const int wg_min_kv = range_full_prefix(p, p.q_off + min(qb * 256, p.l - 1), p.q_off + min(p.l, (qb + 1) * 256) - 1);
-    if (KT <= wg_min_kv) tile(0, No{}, Yes{}); else tile(0, Yes{}, Yes{});
-    kt0 = KT;
+    // wave_min_kv is wave-uniform per construction but tiles are shared by the workgroup (barriers inside): the split point
+    // must be the same for all four waves, so it is taken over the workgroup's first query
+    const int wg_min_kv = range_full_prefix(p, p.q_off + min(qb * QB, p.l - 1), p.q_off + min(p.l, (qb + 1) * QB) - 1);
+    if constexpr (QPRE) {                                  // the first tile sets m~ unconditionally
+        if (KT <= wg_min_kv) tile(0, No{}, Yes{}); else tile(0, Yes{}, Yes{});
+        kt0 = KT;
+    }
     for (; kt0 + KT <= wg_min_kv && kt0 < kv_end; kt0 += KT) tile(kt0, No{}, No{});
     for (; kt0 < kv_end; kt0 += KT) tile(kt0, Yes{}, No{});
 #pragma unroll
@@ -911,36 +707,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const float ls = lsum[g] + __shfl_xor(lsum[g], 32, 64);
         if (qi[g] < p.l) {
             if (p.lse && hi == 0) p.lse[(r * p.H + h) * (long)p.l + qi[g]] = (m[g] + log2f(ls)) * 0.6931471805599453f;
-            const float inv = 1.0f / ls;
-            bf16_t* op = (bf16_t*)p.out + (r * p.l + qi[g]) * (long)(p.H * D) + h * D;
-#pragma unroll
-            for (int db = 0; db < 2; ++db)
-#pragma unroll
-                for (int gg = 0; gg < 4; ++gg) {
-                    float ov[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) ov[e] = o[g][db][4 * gg + e] * inv;
-                    *(bf16x4_t*)(op + 32 * db + 8 * gg + 4 * hi) = pack_bf16x4(ov);
-                }
+            store_acc_row((bf16_t*)p.out + (r * p.l + qi[g]) * (long)(p.H * D) + h * D, o[g], 1.0f / ls, hi);
         }
     }
 }
-
-
-// ================================================================================================
-// attn_mfma_bf16_pipe_kernel (round 4; the inference kernel behind cvar_attention_prescaled): the QPRE kernel above, software-pipelined
-// INSIDE a wave.  profiles/r03_attn_pmc_table.txt: matrix-busy 0.45 + vector-busy 0.57 ~ 1 - the three waves of a SIMD sit in the same
-// phase (two workgroup barriers per tile keep them there), so the matrix pipe idles during everybody's softmax and the vector pipe during
-// everybody's MFMAs.  Here a wave's instruction stream itself alternates between the two pipes: while the softmax of tile t runs on the
-// vector pipe (row maximum, 64 v_exp, row sum, packing), the matrix pipe computes S^T of tile t+1 (K runs one tile ahead of V in LDS) and
-// the PV products of the P fragments already packed.  The order is written out: 13 MFMA tokens (5 QK^T steps of the next tile's second
-// key block, 8 PV steps) are dealt over 8 softmax chunks of 4 scores, each slot pinned with sched_barrier(0); LDS fragments are read one
-// token ahead.  The second score block costs 32 VGPRs: 2 waves per SIMD instead of 3.
-//   step t:   region 1   QK^T(t+1), key block 0 (bias step with the CURRENT m~ + 4 k-steps)   ||  mask(t), row maximum(t)
-//             [rare]     m~ moves: scores(t), O, row sum and the block of tile t+1 just computed shift by the same exact delta
-//             region 2   QK^T(t+1), key block 1 + PV(t)                                       ||  exp / row sum / pack of tile t
-//             barrier - K(t+2), V(t+1) registers -> LDS - barrier - global loads of K(t+3), V(t+2)
-// ================================================================================================
 
 extern "C" int cvar_attention_rowwise(const void* qkv, const void* q, int dtype, int R, int H, int Lmax, int q_off, int l, float scale,
                                       const int* lvl_end_host, int n_lvl, const int* hole_host, void* out, float* lse, void* stream) {
@@ -974,7 +744,6 @@ struct AttnBwdParams {
     int lvl_end[CVAR_ATTN_MAX_LVL];
     int hole_lo[CVAR_ATTN_MAX_LVL], hole_hi[CVAR_ATTN_MAX_LVL];
 };
-__device__ __forceinline__ int kv_len_of_b(const AttnBwdParams& p, int pos) { return vis_of(p, pos).kvlen; }
 // first query position (relative to q_off) that can see key position `key`
 __device__ __forceinline__ int first_query_of(const AttnBwdParams& p, int key) {
     if (p.n_lvl == 0) return 0;
@@ -1017,7 +786,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const AttnBwdParams p)
     const int pos = p.q_off + qrow;
     const Vis vis = vis_of(p, pos);
     const int kvlen = vis.kvlen;
-    const int kv_end = kv_len_of_b(p, p.q_off + min(p.l, (int)(blockIdx.x + 1) * 256) - 1);
+    const int kv_end = kv_len_of(p, p.q_off + min(p.l, (int)(blockIdx.x + 1) * 256) - 1);
     float q[D], dO[D], dq[D];
     {
         const T* qp = base + (long)pos * C3 + h * D;
@@ -1167,9 +936,7 @@ static int cvar_attention_bwd_impl(const void* qkv, int dtype, const void* o, co
     if (dtype == CVAR_BF16) {
         hipLaunchKernelGGL(attn_bwd_prep_kernel<bf16_t>, dim3(cdiv(tot, 256)), dim3(256), 0, st, p);
         if (impl == 0) {
-            bool holes = false;
-            for (int i = 0; i < p.n_lvl; ++i) holes = holes || p.hole_lo[i] < p.hole_hi[i];
-            if (holes) {
+            if (has_holes(p)) {
                 hipLaunchKernelGGL(attn_bwd_dq_mfma_kernel<true>, dim3(cdiv(l, 128), H, R), dim3(256), 0, st, p);
                 hipLaunchKernelGGL(attn_bwd_dkv_mfma_kernel<true>, dim3(cdiv(l, 128), H, R), dim3(256), 0, st, p);
             } else {
@@ -1268,14 +1035,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     const int qrow = min(qi, p.l - 1);
     const Vis vis = vis_of(p, p.q_off + qrow);
     const int wave_min_kv = range_full_prefix(p, p.q_off + min(q0, p.l - 1), p.q_off + min(q0 + 31, p.l - 1));
-    const int kv_end = kv_len_of_b(p, p.q_off + min(p.l, (int)(blockIdx.x + 1) * 128) - 1);
+    const int kv_end = kv_len_of(p, p.q_off + min(p.l, (int)(blockIdx.x + 1) * 128) - 1);
     bf16x8_t qf[4], of[4];
-    {
-        const bf16_t* qp = base + (long)(p.q_off + qrow) * C3 + h * D;
-        const bf16_t* dp = (const bf16_t*)p.dout + (r * p.l + qrow) * (long)(p.H * D) + h * D;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) { qf[ks] = *(const bf16x8_t*)(qp + (2 * ks + hi) * 8); of[ks] = *(const bf16x8_t*)(dp + (2 * ks + hi) * 8); }
-    }
+    load_row_frags(qf, base + (long)(p.q_off + qrow) * C3 + h * D, hi);
+    load_row_frags(of, (const bf16_t*)p.dout + (r * p.l + qrow) * (long)(p.H * D) + h * D, hi);
     const float c2 = p.scale * 1.4426950408889634f;
     const float lse2 = p.lse[(r * p.H + h) * (long)p.l + qrow] * 1.4426950408889634f;
     const float Dq = p.dsum[(r * p.H + h) * (long)p.l + qrow];
@@ -1328,8 +1091,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
                     dq[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bw_tr_frag(k2_lane[db], 32 * kb + 16 * t), dsf[t], dq[db], 0, 0, 0);
         }
     };
-    typedef std::integral_constant<bool, true> Yes;
-    typedef std::integral_constant<bool, false> No;
     BwRows kv_k = bw_load_rows(kbase, C3, 0, kv_end, tid), kv_v = bw_load_rows(vbase, C3, 0, kv_end, tid);
     for (int kt0 = 0; kt0 < kv_end; kt0 += KT) {
         bw_store(Ks, kv_k, tid);
@@ -1342,18 +1103,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         if (kt0 + KT > wave_min_kv) compute(kt0, Yes{}); else compute(kt0, No{});      // wave-uniform; no barrier inside
         __syncthreads();
     }
-    if (qi < p.l) {
-        bf16_t* op = (bf16_t*)p.dqkv + (r * p.Lmax + p.q_off + qi) * (long)C3 + h * D;
-#pragma unroll
-        for (int db = 0; db < 2; ++db)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                float ov[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) ov[e] = dq[db][4 * g + e] * p.scale;
-                *(bf16x4_t*)(op + 32 * db + 8 * g + 4 * hi) = pack_bf16x4(ov);
-            }
-    }
+    if (qi < p.l) store_acc_row((bf16_t*)p.dqkv + (r * p.Lmax + p.q_off + qi) * (long)C3 + h * D, dq, p.scale, hi);
 }
 
 template <bool HOLES>
@@ -1379,12 +1129,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int krow = min(kj, nkeys - 1);
     const int key_hi = min((int)(blockIdx.x + 1) * 128, nkeys);      // one past the workgroup's last key
     bf16x8_t kf[4], vf[4];
-    {
-        const bf16_t* kp = base + (long)krow * C3 + p.H * D + h * D;
-        const bf16_t* vp = kp + p.H * D;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) { kf[ks] = *(const bf16x8_t*)(kp + (2 * ks + hi) * 8); vf[ks] = *(const bf16x8_t*)(vp + (2 * ks + hi) * 8); }
-    }
+    load_row_frags(kf, base + (long)krow * C3 + p.H * D + h * D, hi);
+    load_row_frags(vf, base + (long)krow * C3 + 2 * p.H * D + h * D, hi);
     const float c2 = p.scale * 1.4426950408889634f;
     const BwTrLane q2_lane[2] = {bw_tr_lane(Qs, lane, 0), bw_tr_lane(Qs, lane, 1)};
     const BwTrLane o2_lane[2] = {bw_tr_lane(Os, lane, 0), bw_tr_lane(Os, lane, 1)};
@@ -1457,8 +1203,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 }
         }
     };
-    typedef std::integral_constant<bool, true> Yes;
-    typedef std::integral_constant<bool, false> No;
 
     const int q_begin = first_query_of(p, blockIdx.x * 128);            // first query that sees the block's first key
     const int qt_first = (q_begin / QT) * QT;
@@ -1508,17 +1252,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     for (; qt0 < p.l; qt0 += QT) tile(qt0, Yes{});
     if (kj < nkeys) {
         bf16_t* kp = (bf16_t*)p.dqkv + (r * p.Lmax + kj) * (long)C3 + p.H * D + h * D;
-        bf16_t* vp = kp + p.H * D;
-#pragma unroll
-        for (int db = 0; db < 2; ++db)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                float a[4], b[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { a[e] = dk[db][4 * g + e] * p.scale; b[e] = dv[db][4 * g + e]; }
-                *(bf16x4_t*)(kp + 32 * db + 8 * g + 4 * hi) = pack_bf16x4(a);
-                *(bf16x4_t*)(vp + 32 * db + 8 * g + 4 * hi) = pack_bf16x4(b);
-            }
+        store_acc_row(kp, dk, p.scale, hi);
+        store_acc_row(kp + p.H * D, dv, 1.0f, hi);
     }
 }
 

@@ -1,6 +1,6 @@
 // Microbenchmark (round 5): do the matrix pipe and the vector pipe of ONE SIMD overlap across two waves, and does a barrier-enforced
 // ping-pong (one wave in its MFMA segment while its SIMD partner is in its softmax segment) get there?  The loop body is the instruction mix of
-// attn_mfma_bf16_q64_kernel per 64-key tile and wave (two 32-query groups): 18 QK^T MFMAs (32x32x16) -> softmax over 64 scores per lane
+// attn_mfma_bf16_kernel<HOLES, QPRE, G = 2> per 64-key tile and wave (two 32-query groups): 18 QK^T MFMAs (32x32x16) -> softmax over 64 scores per lane
 // (exp2, row sum, pack to bf16; running maximum test) -> 16 PV MFMAs, with constant K / V fragments in registers (no LDS, no global traffic).
 //   mode 0: one wave per SIMD (256 threads, LDS-limited to one workgroup per CU)
 //   mode 1: two free-running waves per SIMD (two 256-thread workgroups per CU)

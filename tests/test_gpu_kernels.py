@@ -909,13 +909,15 @@ def test_gemm_with_the_adaln_of_the_next_op_is_bit_identical_to_two_calls(gpu_de
         assert (x1 - x2).abs().max() < 1e-3 * max(1.0, float(want.abs().max()))
 
 
-@pytest.mark.parametrize('q_off,l,levels', [(848, 512, None), (0, 512, (2, 10, 28, 60, 110, 182, 310, 512))])
-def test_attention_64_queries_per_wave_kernel_equals_the_128_query_kernel_bit_for_bit(gpu_device, q_off, l, levels):
+@pytest.mark.parametrize('R,H,Lmax,q_off,l,levels,holes', [
+    (12, 24, 1360, 848, 512, None, None), (12, 24, 1360, 0, 512, (2, 10, 28, 60, 110, 182, 310, 512), None),
+    # the HOLES instantiation of G = 2: 8 rows x 64 heads x 1 workgroup of 256 queries = 512 against 2 x 64 x 1 (not 512: G = 1, two workgroups of 128 each)
+    (8, 64, 256, 56, 200, (56, 156, 256), ((0, 0), (20, 56), (56, 156)))], ids=['848-512-None', '0-512-levels1', '56-200-holes'])
+def test_attention_64_queries_per_wave_kernel_equals_the_128_query_kernel_bit_for_bit(gpu_device, R, H, Lmax, q_off, l, levels, holes):
     """cvar_attention_prescaled sends scales whose last 256-query workgroup is nearly full AND whose grid still fills the chip (>= 512 workgroups) to
-    attn_mfma_bf16_q64_kernel (two 32-query groups per wave share every K / V fragment, tile and barrier); everything else runs the 128-query kernel.  Same
-    arithmetic per query: rows 0:2 of an R = 12 call (24 heads x 12 rows x 2 workgroups = 576: the 64-query kernel) equal an R = 2 call (96 workgroups of 256
-    queries would not fill the chip: the 128-query kernel) bit for bit, and both match the fp64 softmax."""
-    H, Lmax, R = 24, 1360, 12
+    attn_mfma_bf16_kernel<HOLES, QPRE, G = 2> (two 32-query groups per wave share every K / V fragment, tile and barrier); everything else runs G = 1, 128 queries
+    per workgroup.  Same arithmetic per query: rows 0:2 of an R = 12 call (24 heads x 12 rows x 2 workgroups = 576: G = 2) equal an R = 2 call (96 workgroups of
+    256 queries would not fill the chip: G = 1) bit for bit, and both match the fp64 softmax.  With holes: keys [lo, hi) of a level are invisible to its queries."""
     C = H * 64
     g = torch.Generator().manual_seed(19)
     kv = (torch.randn(R, Lmax, 2 * C, generator=g) * 0.7).to(torch.bfloat16).to(gpu_device)
@@ -925,10 +927,11 @@ def test_attention_64_queries_per_wave_kernel_equals_the_128_query_kernel_bit_fo
     qp = (q.to(torch.bfloat16).float() * (scale * 1.4426950408889634)).to(torch.bfloat16).to(gpu_device)
     out_big = torch.full((R * l, C), float('nan'), device=gpu_device, dtype=torch.bfloat16)
     lse_big = torch.empty(R, H, l, device=gpu_device)
-    ops.attention(kv, out_big, R, H, Lmax, q_off, l, scale, levels, q=qp.view(R * l, C), prescaled=True, lse=lse_big)
+    ops.attention(kv, out_big, R, H, Lmax, q_off, l, scale, levels, q=qp.view(R * l, C), prescaled=True, lse=lse_big, holes=holes)
     out_small = torch.full((2 * l, C), float('nan'), device=gpu_device, dtype=torch.bfloat16)
     lse_small = torch.empty(2, H, l, device=gpu_device)
-    ops.attention(kv[:2].contiguous(), out_small, 2, H, Lmax, q_off, l, scale, levels, q=qp[:2].reshape(2 * l, C).contiguous(), prescaled=True, lse=lse_small)
+    ops.attention(kv[:2].contiguous(), out_small, 2, H, Lmax, q_off, l, scale, levels, q=qp[:2].reshape(2 * l, C).contiguous(), prescaled=True, lse=lse_small,
+                  holes=holes)
     assert not torch.isnan(out_big.float()).any()
     assert torch.equal(out_big[:2 * l], out_small) and torch.equal(lse_big[:2], lse_small)
     # and the function itself on rows 0:2 (fp64 softmax of the same bf16 operands, log2 domain)
@@ -939,7 +942,11 @@ def test_attention_64_queries_per_wave_kernel_equals_the_128_query_kernel_bit_fo
     pos, keys = torch.arange(q_off, q_off + l), torch.arange(Lmax)
     if levels:
         ends = torch.tensor(levels)
-        vis = keys[None, :] < ends[torch.searchsorted(ends, pos, right=True)][:, None]
+        lvl = torch.searchsorted(ends, pos, right=True)
+        vis = keys[None, :] < ends[lvl][:, None]
+        if holes:
+            lo, hi = torch.tensor(holes)[lvl].unbind(1)
+            vis = vis & ~((keys[None, :] >= lo[:, None]) & (keys[None, :] < hi[:, None]))
     else:
         vis = (keys[None, :] < q_off + l).expand(l, Lmax)
     pr = torch.softmax(s2.masked_fill(~vis, float('-inf')) * math.log(2.0), dim=-1)
