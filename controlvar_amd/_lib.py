@@ -126,6 +126,10 @@ SERVE_SIGNATURES = {
     'cvar_score_rows': (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p]),
     # split-bf16 transformer mode (gemm_precision='bf16x3'): joined at version 1
     'cvar_ln_modulate_split3': (c_i, [c_p, c_p, c_p, c_l, c_i, c_p, c_i, c_i, c_f, c_p]),
+    # e4m3 linear layers (gemm_precision='fp8'): joined at version 1
+    'cvar_quant_rows_fp8': (c_i, [c_p, c_i, c_l, c_l, c_i, c_p, c_l, c_p, c_p]),
+    'cvar_ln_modulate_fp8': (c_i, [c_p, c_p, c_p, c_l, c_i, c_p, c_l, c_p, c_i, c_i, c_f, c_p]),
+    'cvar_gemm_fp8': (c_i, [c_p, c_p, c_p, c_p]),
 }
 
 _lib = None

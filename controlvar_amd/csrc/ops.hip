@@ -1,5 +1,6 @@
 // Row-wise / element-wise kernels of the transformer path (HBM-bound; 16-byte vector accesses).
 #include "cvar_common.h"
+#include "fp8_quant.h"
 
 // ------------------------------------------------------------------------------------------------
 // adaLN: out = LN(x) * (1 + scale) + shift.   One wave per row, values kept in registers.
@@ -7,12 +8,14 @@
 // NV = float4 vectors per lane (C <= NV*256); TAIL = the last vector is only partly populated (C % 256 != 0).
 // All loads of a row are issued back to back (no per-vector branches), so a wave has NV 16-byte loads in flight.
 // TO = bf16x3_t: the row leaves as the split-bf16 operand [hi(C) | lo(C) | hi(C)] of out[M][3 C] (cvar_ln_modulate_split3; split3_store below).
+// TO = fp8q_t: the row leaves as e4m3 bytes of out[M][ldq] plus one power-of-two scale per row (cvar_ln_modulate_fp8): the bf16-rounded row, quantised.
 struct bf16x3_t { bf16_t v; };
+struct fp8q_t { unsigned char v; };
 __device__ __forceinline__ void split3_store(bf16_t* __restrict__ o, const float* y, int C);
 template <typename TO, int NV, bool TAIL>
 __global__ __launch_bounds__(256) void ln_modulate_kernel(const float* __restrict__ x, const float* __restrict__ scale,
                                                          const float* __restrict__ shift, long ld_ada, int rows_per,
-                                                         TO* __restrict__ out, int M, int C, float eps) {
+                                                         TO* __restrict__ out, int M, int C, float eps, long ldq, float* __restrict__ qscale) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= M) return;
@@ -43,6 +46,35 @@ __global__ __launch_bounds__(256) void ln_modulate_kernel(const float* __restric
         for (int e = 0; e < 4; ++e) { v[i][e] = ok ? v[i][e] - mean : 0.f; q += v[i][e] * v[i][e]; }
     }
     const float rstd = rsqrtf(wave_sum(q) / (float)C + eps);
+    if constexpr (std::is_same<TO, fp8q_t>::value) {
+        // the bf16 row cvar_ln_modulate(..., CVAR_BF16) stores, kept in registers; its amax is one wave reduction (masked lanes hold zeros)
+        unsigned ab = 0u;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int c = (i * 64 + lane) * 4;
+            const bool ok = !(TAIL && i == NV - 1) || c < C;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float y = (v[i][e] * rstd) * (1.0f + a[i][e]) + b[i][e];
+                v[i][e] = ok ? bf16_to_f32(f32_to_bf16(y)) : 0.f;
+                ab = max(ab, fp8_abs_bits(v[i][e]));
+            }
+        }
+        ab = wave_max_u32(ab);
+        const bool bad = ab >= 0x7f800000u;
+        const int k = fp8_row_exp(ab);
+        const float inv = fp8_pow2(-k);
+        unsigned char* qrow = (unsigned char*)out + (long)row * ldq;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int c = (i * 64 + lane) * 4;
+            if (TAIL && i == NV - 1 && c >= C) continue;
+            *(unsigned*)(qrow + c) = bad ? 0x7f7f7f7fu : fp8_pack4(v[i][0] * inv, v[i][1] * inv, v[i][2] * inv, v[i][3] * inv);
+        }
+        for (long cp = C + lane * 4; cp < ldq; cp += 256) *(unsigned*)(qrow + cp) = 0u;      // pad bytes [C, ldq): any multiple of 128 the caller chose
+        if (lane == 0) qscale[row] = bad ? 1.0f : fp8_pow2(k);
+        return;
+    }
     TO* orow = out + (long)row * C * (std::is_same<TO, bf16x3_t>::value ? 3 : 1);
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
@@ -64,26 +96,26 @@ __global__ __launch_bounds__(256) void ln_modulate_kernel(const float* __restric
 
 template <typename TO, int NV>
 static void ln_launch(bool tail, dim3 grid, hipStream_t st, const float* x, const float* scale, const float* shift, long ld_ada,
-                      int rows_per, TO* out, int M, int C, float eps) {
-    if (tail) hipLaunchKernelGGL((ln_modulate_kernel<TO, NV, true>), grid, dim3(256), 0, st, x, scale, shift, ld_ada, rows_per, out, M, C, eps);
-    else hipLaunchKernelGGL((ln_modulate_kernel<TO, NV, false>), grid, dim3(256), 0, st, x, scale, shift, ld_ada, rows_per, out, M, C, eps);
+                      int rows_per, TO* out, int M, int C, float eps, long ldq, float* qscale) {
+    if (tail) hipLaunchKernelGGL((ln_modulate_kernel<TO, NV, true>), grid, dim3(256), 0, st, x, scale, shift, ld_ada, rows_per, out, M, C, eps, ldq, qscale);
+    else hipLaunchKernelGGL((ln_modulate_kernel<TO, NV, false>), grid, dim3(256), 0, st, x, scale, shift, ld_ada, rows_per, out, M, C, eps, ldq, qscale);
 }
 
 template <typename TO>
 static int ln_dispatch(const float* x, const float* scale, const float* shift, long ld_ada, int rows_per, TO* out, int M, int C,
-                       float eps, hipStream_t st) {
+                       float eps, hipStream_t st, long ldq = 0, float* qscale = nullptr) {
     const int nv = (C + 255) / 256;
     const bool tail = (C % 256) != 0;
     dim3 grid(cdiv(M, 4));
     switch (nv) {
-        case 1: ln_launch<TO, 1>(tail, grid, st, x, scale, shift, ld_ada, rows_per, out, M, C, eps); break;
-        case 2: ln_launch<TO, 2>(tail, grid, st, x, scale, shift, ld_ada, rows_per, out, M, C, eps); break;
-        case 3: ln_launch<TO, 3>(tail, grid, st, x, scale, shift, ld_ada, rows_per, out, M, C, eps); break;
-        case 4: ln_launch<TO, 4>(tail, grid, st, x, scale, shift, ld_ada, rows_per, out, M, C, eps); break;
-        case 5: ln_launch<TO, 5>(tail, grid, st, x, scale, shift, ld_ada, rows_per, out, M, C, eps); break;
-        case 6: ln_launch<TO, 6>(tail, grid, st, x, scale, shift, ld_ada, rows_per, out, M, C, eps); break;
-        case 7: ln_launch<TO, 7>(tail, grid, st, x, scale, shift, ld_ada, rows_per, out, M, C, eps); break;
-        case 8: ln_launch<TO, 8>(tail, grid, st, x, scale, shift, ld_ada, rows_per, out, M, C, eps); break;
+        case 1: ln_launch<TO, 1>(tail, grid, st, x, scale, shift, ld_ada, rows_per, out, M, C, eps, ldq, qscale); break;
+        case 2: ln_launch<TO, 2>(tail, grid, st, x, scale, shift, ld_ada, rows_per, out, M, C, eps, ldq, qscale); break;
+        case 3: ln_launch<TO, 3>(tail, grid, st, x, scale, shift, ld_ada, rows_per, out, M, C, eps, ldq, qscale); break;
+        case 4: ln_launch<TO, 4>(tail, grid, st, x, scale, shift, ld_ada, rows_per, out, M, C, eps, ldq, qscale); break;
+        case 5: ln_launch<TO, 5>(tail, grid, st, x, scale, shift, ld_ada, rows_per, out, M, C, eps, ldq, qscale); break;
+        case 6: ln_launch<TO, 6>(tail, grid, st, x, scale, shift, ld_ada, rows_per, out, M, C, eps, ldq, qscale); break;
+        case 7: ln_launch<TO, 7>(tail, grid, st, x, scale, shift, ld_ada, rows_per, out, M, C, eps, ldq, qscale); break;
+        case 8: ln_launch<TO, 8>(tail, grid, st, x, scale, shift, ld_ada, rows_per, out, M, C, eps, ldq, qscale); break;
         default: return CVAR_EUNSUPPORTED;
     }
     CVAR_CHECK_LAUNCH();
@@ -105,6 +137,15 @@ extern "C" int cvar_ln_modulate_split3(const float* x, const float* scale, const
     if (!x || !scale || !shift || !out || M <= 0 || rows_per <= 0) return CVAR_EINVAL;
     if (C % 4 || C > 2048 || ld_ada % 4 || (((uintptr_t)x | (uintptr_t)scale | (uintptr_t)shift) & 15) || ((uintptr_t)out & 7)) return CVAR_EUNSUPPORTED;
     return ln_dispatch<bf16x3_t>(x, scale, shift, (long)ld_ada, rows_per, (bf16x3_t*)out, M, C, eps, as_stream(stream));
+}
+
+// cvar_ln_modulate with the e4m3 store (include/cvar_serve.h): bit for bit cvar_quant_rows_fp8(cvar_ln_modulate(..., CVAR_BF16)) without the bf16 row in between
+extern "C" int cvar_ln_modulate_fp8(const float* x, const float* scale, const float* shift, int64_t ld_ada, int rows_per,
+                                    void* q, int64_t ldq, float* qscale, int M, int C, float eps, void* stream) {
+    if (!x || !scale || !shift || !q || !qscale || M <= 0 || rows_per <= 0) return CVAR_EINVAL;
+    if (C % 4 || C > 2048 || ld_ada % 4 || ldq % 128 || ldq < C ||
+        (((uintptr_t)x | (uintptr_t)scale | (uintptr_t)shift | (uintptr_t)q) & 15)) return CVAR_EUNSUPPORTED;
+    return ln_dispatch<fp8q_t>(x, scale, shift, (long)ld_ada, rows_per, (fp8q_t*)q, M, C, eps, as_stream(stream), (long)ldq, qscale);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -237,9 +237,9 @@ def attach_adapters(model, sources, alpha=32) -> List[str]:
     _check_supported(model)
     if has_lora(model):
         raise RuntimeError('the model has add_lora adapters: a bank and add_lora on one model are mutually exclusive (merge_lora first)')
-    if getattr(model, 'gemm_precision', None) == 'bf16x3':
-        from .models import _X3_NO_BANK
-        raise NotImplementedError(_X3_NO_BANK)
+    if getattr(model, 'gemm_precision', None) is not None:
+        from .models import _no_bank_message
+        raise NotImplementedError(_no_bank_message(model.gemm_precision))
     sources = list(sources)
     if not 1 <= len(sources) <= MAX_ADAPTERS:
         raise NotImplementedError(f'{len(sources)} adapters: a bank holds 1 .. {MAX_ADAPTERS}')

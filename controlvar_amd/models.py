@@ -1023,9 +1023,17 @@ class _RowDraw(NamedTuple):
     sample: bool = True
 
 
-GEMM_PRECISIONS = (None, 'bf16x3')
+GEMM_PRECISIONS = (None, 'bf16x3', 'fp8')
 _X3_NO_BANK = ("gemm_precision='bf16x3': the per-request adapter bank (attach_adapters / adapter=) is not offered - its K-augmented operands [W | B_0 ...] do not "
                "compose with the three K segments of the split product; merge one adapter with add_lora, or run the bank on gemm_precision=None")
+
+
+_FP8_NO_BANK = ("gemm_precision='fp8': the per-request adapter bank (attach_adapters / adapter=) is not offered - its K-augmented bf16 operands [W | B_0 ...] have no "
+                "e4m3 form in this mode; merge one adapter with add_lora, or run the bank on gemm_precision=None")
+
+
+def _no_bank_message(precision) -> str:
+    return _FP8_NO_BANK if precision == 'fp8' else _X3_NO_BANK
 
 
 def _split_weight_rows(w: torch.Tensor) -> torch.Tensor:
@@ -1079,6 +1087,9 @@ class ControlVAR(nn.Module):
         matrix pipe - operands carried as hi + lo in bf16, three products per multiply as three K segments of one bf16 GEMM, fp32 accumulation and fp32
         outputs (include/cvar_serve.h).  Everything else - residual stream, adaLN, K/V arena, attention, sampler, quantizer, VQVAE - is the
         fp32 mode's, through the same kernels.  Inference only: forward() and training on such a model run the fp32 path.
+        'fp8' (bf16 models only) = the bf16 model with the qkv, proj, fc1 and fc2 GEMMs of every block on OCP e4m3 operands with one power-of-two scale per
+        row, fp32 accumulation and the bf16 mode's epilogues (include/cvar_serve.h); the head, the adaLN table, the residual stream, the K/V arena,
+        attention, sampler, quantizer and VQVAE are the bf16 mode's, through the same kernels.  Inference only: forward() and training run the bf16 path.
 
         deterministic_plan (an addition of this library): every transformer GEMM runs on the unsliced tile kernels whatever its row count - no small-M weight-streaming
         kernel, no K slices - so the fp32 summation order of a row does not depend on how many rows ride beside it, and one (label, condition, g_seed) in batch row 0 gives
@@ -1185,11 +1196,14 @@ class ControlVAR(nn.Module):
     def gemm_precision(self, value: Optional[str]):
         if value not in GEMM_PRECISIONS:
             raise ValueError(f'gemm_precision must be one of {GEMM_PRECISIONS}, got {value!r}')
-        if value is not None and self.compute_dtype != torch.float32:
+        if value == 'fp8' and self.compute_dtype != torch.bfloat16:
+            raise ValueError(f"gemm_precision='fp8' needs a compute_dtype=torch.bfloat16 model: it is the bf16 model with e4m3 qkv / proj / fc1 / fc2 layers, "
+                             f"and this model computes in {self.compute_dtype} (build it with compute_dtype=torch.bfloat16)")
+        if value == 'bf16x3' and self.compute_dtype != torch.float32:
             raise ValueError(f"gemm_precision={value!r} needs a compute_dtype=torch.float32 model: it is the fp32 model with split-bf16 linear layers, "
                              f"and this model computes in {self.compute_dtype} (build it with compute_dtype=torch.float32)")
         if value is not None and getattr(self, '_adapter_bank', None) is not None:
-            raise NotImplementedError(_X3_NO_BANK)
+            raise NotImplementedError(_no_bank_message(value))
         if value != self._gemm_precision:       # the packed matrices and the arena key belong to the mode
             self._packed = None
             self._packed_base = None
@@ -1285,11 +1299,33 @@ class ControlVAR(nn.Module):
         P: Dict[str, Any] = _Pack()
         blk = lambda i, s: sd[f'blocks.{i}.{s}']
         x3 = self.gemm_precision == 'bf16x3'
+        f8 = self.gemm_precision == 'fp8'
+        F8_KEYS = ('w_qkv', 'w_proj', 'w_fc1', 'w_fc2')
+
+        def quant_stack(w):
+            """fp32 [depth][N][K] -> (e4m3 bytes [depth * N][ldq], fp32 row scales [depth * N]) through the library's row pass: torch converts nothing"""
+            w = w.float().contiguous()
+            rows, K = w.shape[0] * w.shape[1], w.shape[2]
+            ldq = ops.fp8_ldq(K)
+            q = torch.empty(rows, ldq, device=w.device, dtype=torch.uint8)
+            sc = torch.empty(rows, device=w.device, dtype=torch.float32)
+            ops.quant_rows_fp8(w, q, sc, M=rows, K=K, ldq=ldq)
+            return q, sc
 
         def matrix(key, make):
             """one stacked weight matrix, GEMM-ready: in compute dtype, or (gemm_precision='bf16x3') as split rows [w_hi | w_hi | w_lo] under key + '_x3' - the
             fp32 copy is then built only when forward() / training ask for it (both copies of every matrix are never held from the start)"""
-            if key in fresh:
+            if f8 and key in F8_KEYS:
+                # gemm_precision='fp8': e4m3 rows + one power-of-two scale per row from the fp32 parameters (a merged LoRA is folded in `sd` already);
+                # the bf16 copy is built only when forward() / training ask for it
+                if host:
+                    raise RuntimeError("gemm_precision='fp8': the e4m3 weight stacks are made by the device row pass (no host packing)")
+                P[key + '_f8'], P['s_' + key[2:]] = quant_stack(make())
+                if key in fresh:
+                    P[key] = old[key]
+                else:
+                    P.lazy[key] = lambda: make().to(T).contiguous()
+            elif key in fresh:
                 P[key] = old[key]
             elif x3:
                 P[key + '_x3'] = _split_weight_rows(make())
@@ -1435,6 +1471,10 @@ class ControlVAR(nn.Module):
             if ad is not None:
                 raise NotImplementedError(_X3_NO_BANK)
             return self._blocks_and_head_x3(P, x, ada, R, l, q_off, Lmax, arena, lvl_end, holes)
+        if self.gemm_precision == 'fp8' and x3 is None:
+            if ad is not None:
+                raise NotImplementedError(_FP8_NO_BANK)
+            return self._blocks_and_head_fp8(P, x, ada, R, l, q_off, Lmax, arena, lvl_end, holes)
         u = torch.empty(M, C, device=dev, dtype=T)
         o = torch.empty(M, C, device=dev, dtype=T)
         kx = 0 if ad is None else ad[0]['kx']
@@ -1531,6 +1571,54 @@ class ControlVAR(nn.Module):
             ops.ln_modulate_split3(x, ada, sc, sh, n_ada, l, u3, M, C, cfg.norm_eps)
         logits = torch.empty(M, cfg.head_ld, device=dev, dtype=f32)
         ops.gemm(u3, P['w_head_x3'], logits, M=M, N=cfg.head_ld, K=3 * C, bias=P['b_head'], small_m=sm, split_k=sm)
+        return logits
+
+    def _blocks_and_head_fp8(self, P, x, ada, R: int, l: int, q_off: int, Lmax: int, arena, lvl_end, holes):
+        """_blocks_and_head of gemm_precision='fp8': the bf16 pass - fp32 residual stream, bf16 arena / query scratch / attention output / GELU output, prescaled
+        queries, the MFMA attention, the bf16 head - with qkv, proj, fc1 and fc2 as cvar_gemm_fp8 on e4m3 operands (include/cvar_serve.h).  The adaLN rows leave
+        cvar_ln_modulate_fp8 quantised (no bf16 row); the attention output and the GELU output are bf16 round trips through cvar_quant_rows_fp8 (the
+        next lever).  ln_out of the GEMM makes bf16 / fp32 rows only, so adaLN is its own launch at every M; the last one (the head's) is the bf16 cvar_ln_modulate.
+        No plan slices K: deterministic_plan changes nothing in the four e4m3 GEMMs."""
+        cfg = self.cfg
+        C, H, hid, n_ada = cfg.C, cfg.H, P['hid'], P['n_ada']
+        M, dev = R * l, x.device
+        bf, f32, u8 = torch.bfloat16, torch.float32, torch.uint8
+        ldc8, ldh8 = ops.fp8_ldq(C), ops.fp8_ldq(hid)
+        u8q, u8s = torch.empty(M, ldc8, device=dev, dtype=u8), torch.empty(M, device=dev, dtype=f32)      # quantised adaLN rows: operand of qkv / fc1
+        o = torch.empty(M, C, device=dev, dtype=bf)
+        o8q, o8s = torch.empty(M, ldc8, device=dev, dtype=u8), torch.empty(M, device=dev, dtype=f32)
+        hbuf = torch.empty(M, hid, device=dev, dtype=bf)
+        h8q, h8s = torch.empty(M, ldh8, device=dev, dtype=u8), torch.empty(M, device=dev, dtype=f32)
+        qs = torch.empty(M, C, device=dev, dtype=bf)
+        u = torch.empty(M, C, device=dev, dtype=bf)                  # the head's adaLN rows
+        arena_stride = R * Lmax * 2 * C
+        LOG2E = 1.4426950408889634
+        q_alpha = 1.0 if cfg.uses_cos_attn else float(cfg.attn_scale) * LOG2E
+        sm = not self.deterministic_plan
+        ah = cfg.depth * 6 * C
+        ops.ln_modulate_fp8(x, ada, 2 * C, 4 * C, n_ada, l, u8q, u8s, M, C, cfg.norm_eps, ldq=ldc8)
+        for i in range(cfg.depth):
+            a0 = i * 6 * C
+            ops.gemm_fp8(u8q, u8s, P['w_qkv_f8'], P['s_qkv'], arena, M=M, N=3 * C, K=ldc8, lda=ldc8, ldw=ldc8, w_off=i * 3 * C * ldc8, ws_off=i * 3 * C,
+                         bias=P['b_qkv'][i], c_off=i * arena_stride, ldc=2 * C, remap=(l, Lmax, q_off), split=(qs, C, C), split_alpha=q_alpha)
+            if cfg.uses_cos_attn:
+                ops.cos_qk_norm(arena, R, H, Lmax, q_off, l, P['scale_mul'], qkv_off=i * arena_stride, sm_off=i * H, q=qs, q_mul=LOG2E)
+            ops.attention(arena, o, R, H, Lmax, q_off, l, float(cfg.attn_scale), lvl_end, qkv_off=i * arena_stride, holes=holes, q=qs, prescaled=True)
+            ops.quant_rows_fp8(o, o8q, o8s, M=M, K=C, ldq=ldc8)
+            ops.gemm_fp8(o8q, o8s, P['w_proj_f8'], P['s_proj'], x, M=M, N=C, K=ldc8, lda=ldc8, ldw=ldc8, w_off=i * C * ldc8, ws_off=i * C,
+                         bias=P['b_proj'][i], gate=ada, gate_off=a0, ldg=n_ada, gate_rows=l, residual=x)
+            ops.ln_modulate_fp8(x, ada, a0 + 3 * C, a0 + 5 * C, n_ada, l, u8q, u8s, M, C, cfg.norm_eps, ldq=ldc8)
+            ops.gemm_fp8(u8q, u8s, P['w_fc1_f8'], P['s_fc1'], hbuf, M=M, N=hid, K=ldc8, lda=ldc8, ldw=ldc8, w_off=i * hid * ldc8, ws_off=i * hid,
+                         bias=P['b_fc1'][i], act=ACT_GELU_TANH)
+            ops.quant_rows_fp8(hbuf, h8q, h8s, M=M, K=hid, ldq=ldh8)
+            ops.gemm_fp8(h8q, h8s, P['w_fc2_f8'], P['s_fc2'], x, M=M, N=C, K=ldh8, lda=ldh8, ldw=ldh8, w_off=i * C * ldh8, ws_off=i * C,
+                         bias=P['b_fc2'][i], gate=ada, gate_off=a0 + C, ldg=n_ada, gate_rows=l, residual=x)
+            if i + 1 < cfg.depth:
+                a1 = a0 + 6 * C
+                ops.ln_modulate_fp8(x, ada, a1 + 2 * C, a1 + 4 * C, n_ada, l, u8q, u8s, M, C, cfg.norm_eps, ldq=ldc8)
+        ops.ln_modulate(x, ada, ah, ah + C, n_ada, l, u, M, C, cfg.norm_eps)
+        logits = torch.empty(M, cfg.head_ld, device=dev, dtype=f32)
+        ops.gemm(u, P['w_head'], logits, M=M, N=cfg.head_ld, K=C, bias=P['b_head'], small_m=sm, split_k=sm)
         return logits
 
     def _ada(self, cond: torch.Tensor, R: int, ad=None, x3: Optional[bool] = None):
@@ -1687,8 +1775,8 @@ class ControlVAR(nn.Module):
         """``adapter=`` -> the slot of every sequence (host int32, nrep * B), or None when it is not given; refuses on the host"""
         if adapter is None:
             return None
-        if self.gemm_precision == 'bf16x3':
-            raise NotImplementedError(_X3_NO_BANK)
+        if self.gemm_precision is not None:
+            raise NotImplementedError(_no_bank_message(self.gemm_precision))
         from . import lora
         if not lora.has_adapters(self):
             raise RuntimeError('adapter=: no bank attached - call controlvar_amd.lora.attach_adapters(model, sources) first')
@@ -2069,8 +2157,8 @@ class ControlVAR(nn.Module):
             return
         if not per_request:
             raise ValueError('adapters=True needs per_request=True: the adapter slots travel with the per-request table')
-        if self.gemm_precision == 'bf16x3':
-            raise NotImplementedError(_X3_NO_BANK)
+        if self.gemm_precision is not None:
+            raise NotImplementedError(_no_bank_message(self.gemm_precision))
         if getattr(self, '_adapter_bank', None) is None:
             raise RuntimeError('adapters=True: no bank attached - call controlvar_amd.lora.attach_adapters(model, sources) first')
 

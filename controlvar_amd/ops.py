@@ -189,6 +189,80 @@ def ln_modulate_split3(x: torch.Tensor, ada: torch.Tensor, scale_off: int, shift
     return out
 
 
+def fp8_ldq(K: int) -> int:
+    """row stride in bytes of an e4m3 operand of K columns: K rounded up to the 128-byte K tile"""
+    return (K + 127) // 128 * 128
+
+
+def quant_rows_fp8(x: torch.Tensor, q: torch.Tensor, scale: torch.Tensor, *, M: int, K: int, ldx: int = 0, ldq: int = 0,
+                   x_off: int = 0, q_off: int = 0, s_off: int = 0):
+    """rows of x (bf16 / fp32) -> e4m3 bytes q[M][ldq] + one power-of-two fp32 scale per row (cvar_quant_rows_fp8, include/cvar_serve.h).
+    x_off in elements of x, q_off in bytes, s_off in scales."""
+    if q.dtype != torch.uint8 or scale.dtype != torch.float32:
+        raise TypeError('q is uint8 (e4m3 bytes), scale is float32')
+    check(_lib.load().cvar_quant_rows_fp8(_ptr(x) + x_off * x.element_size(), dt(x), ldx or K, M, K, _ptr(q) + q_off, ldq or fp8_ldq(K),
+                                          _ptr(scale) + 4 * s_off, _stream()), 'cvar_quant_rows_fp8')
+    return q, scale
+
+
+def ln_modulate_fp8(x: torch.Tensor, ada: torch.Tensor, scale_off: int, shift_off: int, ld_ada: int, rows_per: int,
+                    q: torch.Tensor, q_scale: torch.Tensor, M: int, Cdim: int, eps: float, ldq: int = 0):
+    """ln_modulate with the e4m3 store: bit for bit quant_rows_fp8(ln_modulate(bf16 out)) (cvar_ln_modulate_fp8, include/cvar_serve.h)"""
+    if q.dtype != torch.uint8 or q_scale.dtype != torch.float32:
+        raise TypeError('q is uint8 (e4m3 bytes), q_scale is float32')
+    base = _ptr(ada)
+    check(_lib.load().cvar_ln_modulate_fp8(_ptr(x), base + 4 * scale_off, base + 4 * shift_off, ld_ada, rows_per,
+                                           _ptr(q), ldq or fp8_ldq(Cdim), _ptr(q_scale), M, Cdim, eps, _stream()), 'cvar_ln_modulate_fp8')
+    return q, q_scale
+
+
+def gemm_fp8(A: torch.Tensor, a_scale: torch.Tensor, W: torch.Tensor, w_scale: torch.Tensor, out: torch.Tensor, *, M: int, N: int, K: int,
+             lda: int = 0, ldw: int = 0, ldc: int = 0, bias: Optional[torch.Tensor] = None, act: int = ACT_NONE, alpha: float = 1.0,
+             gate: Optional[torch.Tensor] = None, ldg: int = 0, gate_rows: int = 1, gate_off: int = 0,
+             residual: Optional[torch.Tensor] = None, ldr: int = 0, remap: Optional[Sequence[int]] = None,
+             a_off: int = 0, w_off: int = 0, c_off: int = 0, as_off: int = 0, ws_off: int = 0,
+             split: Optional[tuple] = None, split_alpha: float = 1.0, desc_hook=None):
+    """C = epilogue(((qA @ qW^T) * a_scale[m]) * w_scale[n]) on e4m3 operands (cvar_gemm_fp8, include/cvar_serve.h).  A [M][lda] and W [N][ldw] are
+    uint8 tensors of e4m3 bytes; lda, ldw, a_off and w_off are in bytes, as_off / ws_off in scales, c_off in elements of out.
+    desc_hook(d): last-minute edits of the descriptor (tests of the refusals)."""
+    if A.dtype != torch.uint8 or W.dtype != torch.uint8:
+        raise TypeError('A and W are uint8 tensors of e4m3 bytes')
+    d = GemmDesc()
+    d.M, d.N, d.K, d.dtype = M, N, K, CVAR_BF16
+    d.A, d.W = _ptr(A) + a_off, _ptr(W) + w_off
+    d.lda, d.ldw = lda or K, ldw or K
+    d.batch = 1
+    d.alpha, d.bias, d.act = alpha, _ptr(bias), act
+    if gate is not None:
+        d.gate = _ptr(gate) + gate_off * 4
+        d.ldg, d.gate_rows = ldg, gate_rows
+    if residual is not None:
+        d.residual, d.res_dtype, d.ldr = _ptr(residual), dt(residual), ldr or N
+    d.C = _ptr(out) + c_off * out.element_size()
+    d.out_dtype, d.ldc = dt(out), ldc or N
+    if remap is not None:
+        d.remap_l, d.remap_L, d.remap_off = remap
+    if split is not None:
+        st, d.split_n, d.ld_split = split
+        if st.dtype != out.dtype:
+            raise TypeError('split target and out must share a dtype')
+        d.C_split = _ptr(st)
+        d.split_alpha = float(split_alpha)
+    if desc_hook is not None:
+        desc_hook(d)
+    args = (C.byref(d), _ptr(a_scale) + 4 * as_off, _ptr(w_scale) + 4 * ws_off, _stream())
+    if GEMM_PROFILE is None:
+        check(_lib.load().cvar_gemm_fp8(*args), 'cvar_gemm_fp8')
+    else:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        check(_lib.load().cvar_gemm_fp8(*args), 'cvar_gemm_fp8')
+        e1.record()
+        tag = ('gemm_fp8', M, N, K, 1, 'gate' if gate is not None else ('res' if residual is not None else ('act' if act else ('remap' if remap is not None else 'plain'))), str(out.dtype)[6:])
+        GEMM_PROFILE.append((e0, e1, 2.0 * M * N * K, tag))
+    return out
+
+
 def silu_cast(x: torch.Tensor, out: torch.Tensor):
     check(_lib.load().cvar_silu_cast(_ptr(x), _ptr(out), dt(out), x.numel(), _stream()), 'cvar_silu_cast')
     return out

@@ -4,7 +4,7 @@
  * The functions live in the same libcvar_hip.so as those of cvar.h.  They are versioned on their own: cvar_serve_version() bumps on
  * any signature change in THIS header, cvar_abi_version() stays the version of cvar.h.  Adding an entry point changes no signature and
  * leaves the version alone: cvar_edit_force_table, cvar_cfg_sample_edit, cvar_lora_down_rows,
- * cvar_score_rows and cvar_ln_modulate_split3 joined at version 1.
+ * cvar_score_rows, cvar_ln_modulate_split3, cvar_quant_rows_fp8, cvar_ln_modulate_fp8 and cvar_gemm_fp8 joined at version 1.
  */
 #ifndef CVAR_SERVE_H
 #define CVAR_SERVE_H
@@ -138,6 +138,55 @@ int cvar_score_rows(const float* logits, int B, int nrep, int l, int V, const fl
  * x, scale and shift 16-byte aligned, out 8-byte aligned.  A refused call writes nothing. */
 int cvar_ln_modulate_split3(const float* x, const float* scale, const float* shift, int64_t ld_ada, int rows_per,
                             void* out_bf16 /* [M][3 C] */, int M, int C, float eps, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * e4m3 linear layers (`gemm_precision='fp8'` of a bf16 model).  Joined at version 1.
+ * The mode is the bf16 mode in everything except the qkv, proj, fc1 and fc2 GEMMs of every block: those take OCP e4m3 (e4m3fn) operands with one
+ * power-of-two scale per row and accumulate in fp32; their epilogues are cvar_gemm's.  The contract, stated once:
+ *
+ * Quantising a row x[0..K) (fp32 or bf16 values):
+ *   - amax = max |x_k|;
+ *   - k = the smallest integer with amax <= 448 * 2^k, clamped to [-60, 120], read off the exponent and mantissa fields of amax
+ *     (448 = 1.75 * 2^8: k = e - 8 for a mantissa <= 1.75, e - 7 above; no logarithm is taken);
+ *   - scale = 2^k as fp32;
+ *   - q_k = e4m3_rne(x_k * 2^-k): the product is exact (a result below the fp32 normal range rounds to zero either way), nothing exceeds 448,
+ *     so nothing saturates; the one rounding is the conversion, to nearest, ties to even;
+ *   - an all-zero row gets k = -60 and zero bytes (an entry -0.0 keeps its sign, here and in any row: its byte is 0x80, the e4m3 -0; so does a negative
+ *     value that rounds to zero - the product does not tell the two zeros apart);
+ *   - a row that holds a NaN or an Inf gets scale = 1 and every byte 0x7F (NaN): a broken activation shows instead of hiding;
+ *   - bytes [K, ldq) of a row are zero, ldq = K rounded up to 128 (or any larger multiple of 128).
+ * Product: acc[m,n] = sum_k q_a[m,k] q_w[n,k] into an fp32 accumulator, K ascending in blocks of 128 - one v_mfma_scale_f32_16x16x128_f8f6f4 per
+ * block - and no K slices in any plan: the bits of a row do not depend on M, the tile or the batch.  The hardware block scales of the MFMA are the
+ * constant 1.0 (e8m0 0x7F); MX block scales are not used.  Inside a block the sum is the instruction's, and how the instruction sums is NOT part of
+ * this contract.  What the tests hold the call to: exact results for integer-valued operands whose partial sums stay below 2^24, and the bound of
+ * tests/fp8_ref.py otherwise.  An observation, not a promise (tools/fp8_mfma_probe.py reproduces it with exact data, DESIGN.md 4i records one run on
+ * an MI355X): products far below the largest of their group of 8 consecutive k - from 2^-14 of it on - did not reach the sum, and group sums were
+ * truncated, not rounded, into the accumulator; operands inside a few binades were summed exactly.
+ * The value the epilogue sees is (acc * a_scale[m]) * w_scale[n], in that order (both factors are powers of two); bias, alpha, split_alpha,
+ * GELU, gate, residual, row remap, column split and the output cast follow as cvar_gemm does them.
+ *
+ * cvar_quant_rows_fp8: the row pass, one wave per row.  x [M][ldx] of x_dtype (CVAR_BF16 / CVAR_F32), K columns read; q [M][ldq] bytes, scale [M] fp32.
+ * ldq % 128 == 0, ldq >= K, ldx >= K, q 4-byte aligned (CVAR_EUNSUPPORTED otherwise); NULL pointers, M <= 0 or K <= 0: CVAR_EINVAL.  A refused call
+ * writes nothing.  With fp32 input it also quantises the weight stacks when a model packs them. */
+int cvar_quant_rows_fp8(const void* x, int x_dtype, int64_t ldx, int64_t M, int K, void* q, int64_t ldq, float* scale, void* stream);
+
+/* cvar_ln_modulate with the e4m3 store: y = LN(x[m]) * (1 + scale) + shift in cvar_ln_modulate's fp32 arithmetic and order, rounded to bf16, and that
+ * row quantised as above - bit for bit cvar_quant_rows_fp8(the bf16 rows of cvar_ln_modulate(..., CVAR_BF16)) in one pass (the row is in registers,
+ * its amax is one wave reduction).  Arguments and refusals as cvar_ln_modulate_split3; q [M][ldq] bytes (ldq % 128 == 0, ldq >= C - any such ldq: the
+ * bytes [C, ldq) of every row are written as zeros - 16-byte aligned),
+ * q_scale [M] fp32.  A refused call writes nothing. */
+int cvar_ln_modulate_fp8(const float* x, const float* scale, const float* shift, int64_t ld_ada, int rows_per,
+                         void* q /* [M][ldq] */, int64_t ldq, float* q_scale /* [M] */, int M, int C, float eps, void* stream);
+
+/* cvar_gemm on e4m3 operands.  d->A [M][lda] and d->W [N][ldw] are e4m3 bytes, lda / ldw in bytes; d->dtype is not read.  a_scale [M], w_scale [N] fp32.
+ * Needs K % 128 == 0, lda and ldw multiples of 16 and >= K, A and W 16-byte aligned.  Honoured: bias, alpha, act NONE / GELU_TANH, gate (+ gate_rows), residual
+ * (fp32 in place included), row remap + column split + split_alpha, bf16 or fp32 C; any M and N.
+ * Fast path of the epilogue (16-byte accesses of whole row segments; every other call takes the element-wise form: the same bits, and the d24 B = 512
+ * step 1.4x as long when the model's calls took it): N, ldc, ldr, ldg, split_n and ld_split multiples of 4; w_scale, bias, gate and an fp32 C / C_split / residual 16-byte
+ * aligned, a bf16 C / C_split / residual 8-byte aligned.  conv, batch > 1, ws, ln_out, gn_part, pre_act, aux,
+ * gate_scale and GELU_GRAD return CVAR_EUNSUPPORTED before any write; tile_cfg, stagger and group_m are not read (no plan changes a bit).
+ * One 256x256 tile (eight waves) for M >= 1024, a 128x128 tile (four waves) below; tails of any size. */
+int cvar_gemm_fp8(const cvar_gemm_desc* d, const float* a_scale, const float* w_scale, void* stream);
 
 #ifdef __cplusplus
 }
