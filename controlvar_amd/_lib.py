@@ -1,4 +1,4 @@
-"""ctypes binding of libcvar_hip.so (include/cvar.h, include/cvar_serve.h).  No torch types cross this boundary:
+"""ctypes binding of libcvar_hip.so (include/cvar.h, include/cvar_serve.h, include/cvar_accum.h).  No torch types cross this boundary:
 callers hand over raw device pointers (``tensor.data_ptr()``), sizes and the HIP stream handle.
 
 The library is mandatory on the product path: if it is missing or does not load, every op
@@ -132,6 +132,15 @@ SERVE_SIGNATURES = {
     'cvar_gemm_fp8': (c_i, [c_p, c_p, c_p, c_p]),
 }
 
+# include/cvar_accum.h: the accumulating forms of the gradient producers (gradient accumulation) - each its cvar.h namesake plus an `accumulate`
+# flag in front of the stream.  A table of its own for the same reason; no signature of the other two headers changed, so neither version moved
+ACCUM_SIGNATURES = {
+    'cvar_gemm_tn_acc': (c_i, [c_p, c_l, c_p, c_l, c_p, c_l, c_i, c_i, c_i, c_p, c_l, c_p, c_i, c_p]),
+    'cvar_lora_wgrad_acc': (c_i, [c_p, c_l, c_p, c_l, c_i, c_i, c_i, c_i, c_f, c_f, C.c_uint64, C.c_uint32, c_p, c_l, c_p, c_l, c_l, c_i, c_p]),
+    'cvar_wordembed_grad_acc': (c_i, [c_p, c_l, c_i, c_i, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_p]),
+    'cvar_add_inplace': (c_i, [c_p, c_p, c_l, c_p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -154,7 +163,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         except Exception:  # pragma: no cover
             pass
         lib = C.CDLL(path, mode=C.RTLD_GLOBAL)
-        for name, (res, args) in (*SIGNATURES.items(), *SERVE_SIGNATURES.items()):
+        for name, (res, args) in (*SIGNATURES.items(), *SERVE_SIGNATURES.items(), *ACCUM_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -49,7 +49,8 @@ def build_lib(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(OBJ, exist_ok=True)
     deps = [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(CSRC, 'cvar_common.h'), os.path.join(CSRC, 'gemm_params.h'), os.path.join(CSRC, 'fp8_quant.h'),
                                                          os.path.join(os.path.dirname(HERE), 'include', 'cvar.h'),
-                                                         os.path.join(os.path.dirname(HERE), 'include', 'cvar_serve.h')]
+                                                         os.path.join(os.path.dirname(HERE), 'include', 'cvar_serve.h'),
+                                                         os.path.join(os.path.dirname(HERE), 'include', 'cvar_accum.h')]
     stamp = os.path.join(OBJ, 'digest.txt')
     dig = _digest(deps)
     if not force and os.path.exists(LIB) and os.path.exists(stamp) and open(stamp).read() == dig:

@@ -10,7 +10,10 @@
 //   Calls with few tiles (the square proj gradient) take a 256 x 256 tile on eight waves instead (same 64 x 128 wave tiles, ring of four 32 KB stages, one
 //   workgroup per CU): a third less L2 -> LDS traffic per flop; the large calls stay on the 128-row tile, whose two independent workgroups per CU cover
 //   each other's barriers (measured both ways, profiles/r04_train_gemm_tn.txt).
+//   Accumulating form (cvar_gemm_tn_acc, gradient accumulation): C = fp32(C_old + plain), one add per element, performed last.  One slice: the epilogue
+//   loads the row segments it is about to overwrite; token split: the slices never read C, the fixed-order reduction adds C_old after the last slice.
 #include "cvar_common.h"
+#include "../../include/cvar_accum.h"
 
 typedef __attribute__((address_space(3))) void* lptr_t;
 
@@ -48,7 +51,8 @@ __device__ __forceinline__ bf16x8_t tn_pack(const v2i_t lo, const v2i_t hi) {
 }
 
 // BM = 128: 4 waves, two workgroups per CU;  BM = 256: 8 waves (4 x 2), one workgroup per CU.  The wave tile is 64 x 128 in both.
-template <int TN_BM, int NST>
+// ACC (single-slice launches only): add what C / colsum held before; ACC = false is the plain kernel, instruction for instruction.
+template <int TN_BM, int NST, bool ACC>
 __global__ __launch_bounds__(TN_BM * 2, TN_BM == 128 ? 2 : 1) void gemm_tn_bf16_kernel(const GemmTnParams p) {
     constexpr int NW = TN_BM / 32;                       // waves
     constexpr int TN_A_BYTES = TN_BK * TN_BM * 2;        // [32 t][BM x 2 B]
@@ -197,30 +201,47 @@ __global__ __launch_bounds__(TN_BM * 2, TN_BM == 128 ? 2 : 1) void gemm_tn_bf16_
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
+        for (int j = 0; j < 4; ++j) {
+            float old[ACC ? 16 : 1];
+            if constexpr (ACC) {                    // the 16 row segments of this block, loaded with the addressing of the stores below, then one add each
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int n = n0 + 64 * wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * hi;
+                    const int k = k0 + 128 * wn + 32 * j + lrow;
+                    old[r] = cbase[(long)n * p.ldc + k];
+                }
+            }
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int n = n0 + 64 * wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * hi;
                 const int k = k0 + 128 * wn + 32 * j + lrow;
-                cbase[(long)n * p.ldc + k] = acc[i][j][r];
+                if constexpr (ACC) cbase[(long)n * p.ldc + k] = old[r] + acc[i][j][r];
+                else cbase[(long)n * p.ldc + k] = acc[i][j][r];
             }
+        }
     if (do_cs && lrow == 0) {                       // column 0 of the block: lanes 0 (hi = 0) and 32 (hi = 1) hold the 32 row sums between them
         float* cs = p.colsum + (long)blockIdx.z * p.cs_stride;
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) cs[n0 + 64 * wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * hi] = accb[i][r];
+            for (int r = 0; r < 16; ++r) {
+                float* o = cs + n0 + 64 * wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * hi;
+                if constexpr (ACC) *o = *o + accb[i][r];
+                else *o = accb[i][r];
+            }
     }
 }
 
 // out[i] = sum_s part[s][i] in slice order (fixed -> bit-reproducible); row-major [Nn][Kk] partials -> C with leading dimension ldc
+// ACC: the old C / cs_out is added after the last slice - fp32(old + plain)
+template <bool ACC>
 __global__ __launch_bounds__(256) void gemm_tn_reduce_kernel(const float* __restrict__ part, float* __restrict__ C, long ldc, int Nn, int Kk, int nsplit,
                                                              const float* __restrict__ cs_part, float* __restrict__ cs_out) {
     if (cs_out) {                                   // the slices' column sums, same fixed order; spread over the grid (one block doing all of it was the launch's straggler)
         for (long n = (long)blockIdx.x * 256 + threadIdx.x; n < Nn; n += (long)gridDim.x * 256) {
             float v = cs_part[n];
             for (int s = 1; s < nsplit; ++s) v += cs_part[(long)s * Nn + n];
-            cs_out[n] = v;
+            cs_out[n] = ACC ? cs_out[n] + v : v;
         }
     }
     const long nvec = (long)Nn * (Kk / 4);
@@ -239,6 +260,11 @@ __global__ __launch_bounds__(256) void gemm_tn_reduce_kernel(const float* __rest
                     for (int e = 0; e < 4; ++e) v[e] += w[u][e];
                 }
         }
+        if constexpr (ACC) {
+            const f32x4_t old = *(const f32x4_t*)(C + (long)n * ldc + k);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = old[e] + v[e];
+        }
         *(f32x4_t*)(C + (long)n * ldc + k) = v;
     }
 }
@@ -246,8 +272,8 @@ __global__ __launch_bounds__(256) void gemm_tn_reduce_kernel(const float* __rest
 /* C[Nn][Kk] (fp32, leading dimension ldc) = A^T B with A = [T][lda] (Nn columns used), B = [T][ldb] (Kk columns used), both bf16.
  * Nn % 128 == 0, Kk % 128 == 0 (column tiles are 256 wide; a half-filled last one stores its first 128 columns); lda, ldb multiples of 8 (any T: the last K step is zero-filled); ws: caller workspace for the token-split partials (may be NULL: one slice).
  * colsum_a (optional, ABI 14): colsum_a[n] = sum_t A[t][n], the bias gradient of the same layer, from the A fragments the kernel holds anyway. */
-extern "C" int cvar_gemm_tn(const void* A, int64_t lda, const void* B, int64_t ldb, float* C, int64_t ldc, int T, int Nn, int Kk,
-                            float* ws, int64_t ws_bytes, float* colsum_a, void* stream) {
+static int gemm_tn_run(const void* A, int64_t lda, const void* B, int64_t ldb, float* C, int64_t ldc, int T, int Nn, int Kk,
+                       float* ws, int64_t ws_bytes, float* colsum_a, bool accumulate, void* stream) {
     if (!A || !B || !C || T <= 0 || Nn <= 0 || Kk <= 0) return CVAR_EINVAL;
     if (Nn % 128 || Kk % (TN_BN / 2) || lda % 8 || ldb % 8 || ldc % 4 || lda < Nn || ldb < Kk || ldc < Kk) return CVAR_EUNSUPPORTED;
     if ((((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15) || (long)T * lda * 2 >= 0x7fffffffL || (long)T * ldb * 2 >= 0x7fffffffL) return CVAR_EUNSUPPORTED;
@@ -274,19 +300,34 @@ extern "C" int cvar_gemm_tn(const void* A, int64_t lda, const void* B, int64_t l
     const int nsplit = (p.nsteps + p.steps_per_split - 1) / p.steps_per_split;
     hipStream_t st = as_stream(stream);
     auto launch = [&](int nz) {
-        if (big) hipLaunchKernelGGL((gemm_tn_bf16_kernel<256, CVAR_TN_STAGES256>), dim3(tiles, 1, nz), dim3(512), 0, st, p);
-        else hipLaunchKernelGGL((gemm_tn_bf16_kernel<128, 3>), dim3(tiles, 1, nz), dim3(256), 0, st, p);
+        if (big) hipLaunchKernelGGL((gemm_tn_bf16_kernel<256, CVAR_TN_STAGES256, false>), dim3(tiles, 1, nz), dim3(512), 0, st, p);
+        else hipLaunchKernelGGL((gemm_tn_bf16_kernel<128, 3, false>), dim3(tiles, 1, nz), dim3(256), 0, st, p);
     };
     if (nsplit == 1) {
         p.C = C; p.split_stride = 0; p.colsum = colsum_a; p.cs_stride = 0;
-        launch(1);
+        if (!accumulate) launch(1);
+        else if (big) hipLaunchKernelGGL((gemm_tn_bf16_kernel<256, CVAR_TN_STAGES256, true>), dim3(tiles, 1, 1), dim3(512), 0, st, p);
+        else hipLaunchKernelGGL((gemm_tn_bf16_kernel<128, 3, true>), dim3(tiles, 1, 1), dim3(256), 0, st, p);
     } else {
         float* cs_part = colsum_a ? ws + (size_t)nsplit * Nn * Kk : nullptr;          // behind the partial tiles
         p.C = ws; p.ldc = Kk; p.split_stride = (long)Nn * Kk; p.colsum = cs_part; p.cs_stride = Nn;
         launch(nsplit);
         const long nvec = (long)Nn * (Kk / 4);
-        hipLaunchKernelGGL(gemm_tn_reduce_kernel, dim3((unsigned)min((long)2048, (nvec + 255) / 256)), dim3(256), 0, st, ws, C, (long)ldc, Nn, Kk, nsplit, cs_part, colsum_a);
+        const dim3 rgrid((unsigned)min((long)2048, (nvec + 255) / 256));
+        if (accumulate) hipLaunchKernelGGL(gemm_tn_reduce_kernel<true>, rgrid, dim3(256), 0, st, ws, C, (long)ldc, Nn, Kk, nsplit, cs_part, colsum_a);
+        else hipLaunchKernelGGL(gemm_tn_reduce_kernel<false>, rgrid, dim3(256), 0, st, ws, C, (long)ldc, Nn, Kk, nsplit, cs_part, colsum_a);
     }
     CVAR_CHECK_LAUNCH();
     return CVAR_OK;
+}
+
+extern "C" int cvar_gemm_tn(const void* A, int64_t lda, const void* B, int64_t ldb, float* C, int64_t ldc, int T, int Nn, int Kk,
+                            float* ws, int64_t ws_bytes, float* colsum_a, void* stream) {
+    return gemm_tn_run(A, lda, B, ldb, C, ldc, T, Nn, Kk, ws, ws_bytes, colsum_a, false, stream);
+}
+
+/* cvar_gemm_tn with C (and colsum_a) = fp32(old + plain) where accumulate != 0: same operands, same slice plan, same sums - one more add per element, last. */
+extern "C" int cvar_gemm_tn_acc(const void* A, int64_t lda, const void* B, int64_t ldb, float* C, int64_t ldc, int T, int Nn, int Kk,
+                                float* ws, int64_t ws_bytes, float* colsum_a, int accumulate, void* stream) {
+    return gemm_tn_run(A, lda, B, ldb, C, ldc, T, Nn, Kk, ws, ws_bytes, colsum_a, accumulate != 0, stream);
 }

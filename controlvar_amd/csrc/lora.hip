@@ -11,6 +11,7 @@
 //                    adapter of a bank, no dropout; the other slots' columns of the K-augmented operand are written as zeros
 // The dropout keep mask of (seed, tag, row, column) is a counter-based hash: forward and backward regenerate it, nothing is stored.
 #include "cvar_common.h"
+#include "../../include/cvar_accum.h"
 #include "../../include/cvar_serve.h"
 
 #define LORA_R 16           // rank held in registers; r < 16 leaves the upper accumulators unused
@@ -340,6 +341,8 @@ __global__ __launch_bounds__(256) void lora_wgrad_kernel(const T* __restrict__ Y
 }
 
 // block = 64 outputs x 4 split groups: group g sums the splits g, g + 4, ... in order, the four group sums are added in a fixed order
+// ACC (cvar_lora_wgrad_acc, gradient accumulation): the old output is added last - fp32(old + plain)
+template <bool ACC>
 __global__ __launch_bounds__(256) void lora_wgrad_finish_kernel(const float* __restrict__ ws, int nsplit, int N, int r, float scale, float* __restrict__ out,
                                                                 long os_n, long os_j) {
     __shared__ float part[4][64];
@@ -355,7 +358,8 @@ __global__ __launch_bounds__(256) void lora_wgrad_finish_kernel(const float* __r
     const int n = (int)(i / LORA_R), j = (int)(i % LORA_R);
     if (j >= r) return;
     const int t = threadIdx.x;
-    out[n * os_n + j * os_j] = scale * (((part[0][t] + part[1][t]) + part[2][t]) + part[3][t]);
+    const float v = scale * (((part[0][t] + part[1][t]) + part[2][t]) + part[3][t]);
+    out[n * os_n + j * os_j] = ACC ? out[n * os_n + j * os_j] + v : v;
 }
 
 __global__ __launch_bounds__(256) void lora_mask_kernel(float* __restrict__ out, int M, int K, LoraMask mk) {
@@ -447,8 +451,8 @@ extern "C" int cvar_lora_dx(void* dx, int64_t lddx, int dx_dtype, const void* du
     return CVAR_OK;
 }
 
-extern "C" int cvar_lora_wgrad(const void* Y, int64_t ldy, const void* Z, int64_t ldz, int M, int N, int r, int dtype, float scale, float p, uint64_t seed,
-                               uint32_t tag, float* ws, int64_t ws_floats, float* out, int64_t os_n, int64_t os_j, void* stream) {
+static int lora_wgrad_run(const void* Y, int64_t ldy, const void* Z, int64_t ldz, int M, int N, int r, int dtype, float scale, float p, uint64_t seed,
+                          uint32_t tag, float* ws, int64_t ws_floats, float* out, int64_t os_n, int64_t os_j, bool accumulate, void* stream) {
     if (!Y || !Z || !ws || !out || M <= 0 || N <= 0 || r <= 0) return CVAR_EINVAL;
     if (r > LORA_R || ldy < N || ldz < r || N % WG_COLS || ldy % WG_COLS || ((uintptr_t)Y & (WG_COLS * (dtype == CVAR_BF16 ? 2 : 4) - 1)))
         return CVAR_EUNSUPPORTED;
@@ -465,9 +469,21 @@ extern "C" int cvar_lora_wgrad(const void* Y, int64_t ldy, const void* Z, int64_
         hipLaunchKernelGGL((lora_wgrad_kernel<float>), grid, block, 0, st, (const float*)Y, (long)ldy, (const float*)Z, (long)ldz, M, N, r, rps, mk, ws);
     else return CVAR_EUNSUPPORTED;
     CVAR_CHECK_LAUNCH();
-    hipLaunchKernelGGL(lora_wgrad_finish_kernel, dim3(cdiv((int64_t)N * LORA_R, 64)), block, 0, st, ws, ns, N, r, scale, out, (long)os_n, (long)os_j);
+    const dim3 fgrid(cdiv((int64_t)N * LORA_R, 64));
+    if (accumulate) hipLaunchKernelGGL(lora_wgrad_finish_kernel<true>, fgrid, block, 0, st, ws, ns, N, r, scale, out, (long)os_n, (long)os_j);
+    else hipLaunchKernelGGL(lora_wgrad_finish_kernel<false>, fgrid, block, 0, st, ws, ns, N, r, scale, out, (long)os_n, (long)os_j);
     CVAR_CHECK_LAUNCH();
     return CVAR_OK;
+}
+
+extern "C" int cvar_lora_wgrad(const void* Y, int64_t ldy, const void* Z, int64_t ldz, int M, int N, int r, int dtype, float scale, float p, uint64_t seed,
+                               uint32_t tag, float* ws, int64_t ws_floats, float* out, int64_t os_n, int64_t os_j, void* stream) {
+    return lora_wgrad_run(Y, ldy, Z, ldz, M, N, r, dtype, scale, p, seed, tag, ws, ws_floats, out, os_n, os_j, false, stream);
+}
+
+extern "C" int cvar_lora_wgrad_acc(const void* Y, int64_t ldy, const void* Z, int64_t ldz, int M, int N, int r, int dtype, float scale, float p, uint64_t seed,
+                                   uint32_t tag, float* ws, int64_t ws_floats, float* out, int64_t os_n, int64_t os_j, int accumulate, void* stream) {
+    return lora_wgrad_run(Y, ldy, Z, ldz, M, N, r, dtype, scale, p, seed, tag, ws, ws_floats, out, os_n, os_j, accumulate != 0, stream);
 }
 
 extern "C" int cvar_lora_dropout_mask(float* out, int M, int K, float p, uint64_t seed, uint32_t tag, void* stream) {

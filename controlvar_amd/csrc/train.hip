@@ -3,6 +3,7 @@
 // cross-entropy forward+backward, embedding scatter, SiLU backward, fused AdamW and the gradient-norm reduction.
 // All reductions are two-level with a fixed order (no atomics): results are bit-reproducible.
 #include "cvar_common.h"
+#include "../../include/cvar_accum.h"
 
 constexpr int RED_S = 8;      // row segments of the per-sequence column reductions (scalar fallbacks)
 // The vector kernels split every sequence into red_segments(R, l) row segments so that R * segments blocks fill the chip
@@ -569,21 +570,24 @@ __global__ __launch_bounds__(256) void wordembed_grad_kernel(const float* __rest
         if (j == 0) o[e * 33 + 32] = accb[e];
     }
 }
+// ACC (cvar_wordembed_grad_acc, gradient accumulation): the old dW / db is added after the last slice - fp32(old + plain)
+template <bool ACC>
 __global__ __launch_bounds__(256) void wordembed_grad_reduce_kernel(const float* __restrict__ part, int nslice, int C, float* __restrict__ dW, float* __restrict__ db) {
     const long total = (long)C * 33;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
         float v = part[i];
         for (int s2 = 1; s2 < nslice; ++s2) v += part[(long)s2 * total + i];
         const int c = (int)(i / 33), jj = (int)(i % 33);
-        if (jj < 32) dW[(long)c * 32 + jj] = v; else db[c] = v;
+        float* o = jj < 32 ? dW + (long)c * 32 + jj : db + c;
+        *o = ACC ? *o + v : v;
     }
 }
 extern "C" int64_t cvar_wordembed_grad_ws_bytes(int64_t ntok, int C) {
     const int64_t nslice = ntok >= 32768 ? 32 : (ntok >= 4096 ? 16 : (ntok >= 256 ? 4 : 1));
     return nslice * (int64_t)C * 33 * (int64_t)sizeof(float);
 }
-extern "C" int cvar_wordembed_grad(const float* dx, int64_t ldx, int rows_per_sample, int skip, const float* tok, int n_per_sample, int B, int C, int Cvae,
-                                   float* dW, float* db, float* ws, void* stream) {
+static int wordembed_grad_run(const float* dx, int64_t ldx, int rows_per_sample, int skip, const float* tok, int n_per_sample, int B, int C, int Cvae,
+                              float* dW, float* db, float* ws, bool accumulate, void* stream) {
     if (!dx || !tok || !dW || !db || !ws || B <= 0 || n_per_sample <= 0 || C <= 0 || rows_per_sample < skip + n_per_sample) return CVAR_EINVAL;
     if (Cvae != 32 || C % WEG_CT || (ldx & 3) || (((uintptr_t)dx | (uintptr_t)ws) & 15)) return CVAR_EUNSUPPORTED;
     const long ntok = (long)B * n_per_sample;
@@ -591,7 +595,45 @@ extern "C" int cvar_wordembed_grad(const float* dx, int64_t ldx, int rows_per_sa
     const int per = (int)((ntok + nslice - 1) / nslice);
     hipStream_t st = as_stream(stream);
     hipLaunchKernelGGL(wordembed_grad_kernel, dim3(C / WEG_CT, nslice), dim3(256), 0, st, dx, (long)ldx, rows_per_sample, skip, tok, n_per_sample, ntok, C, per, ws);
-    hipLaunchKernelGGL(wordembed_grad_reduce_kernel, dim3((unsigned)min((long)256, ((long)C * 33 + 255) / 256)), dim3(256), 0, st, (const float*)ws, nslice, C, dW, db);
+    const dim3 rgrid((unsigned)min((long)256, ((long)C * 33 + 255) / 256));
+    if (accumulate) hipLaunchKernelGGL(wordembed_grad_reduce_kernel<true>, rgrid, dim3(256), 0, st, (const float*)ws, nslice, C, dW, db);
+    else hipLaunchKernelGGL(wordembed_grad_reduce_kernel<false>, rgrid, dim3(256), 0, st, (const float*)ws, nslice, C, dW, db);
+    CVAR_CHECK_LAUNCH();
+    return CVAR_OK;
+}
+extern "C" int cvar_wordembed_grad(const float* dx, int64_t ldx, int rows_per_sample, int skip, const float* tok, int n_per_sample, int B, int C, int Cvae,
+                                   float* dW, float* db, float* ws, void* stream) {
+    return wordembed_grad_run(dx, ldx, rows_per_sample, skip, tok, n_per_sample, B, C, Cvae, dW, db, ws, false, stream);
+}
+extern "C" int cvar_wordembed_grad_acc(const float* dx, int64_t ldx, int rows_per_sample, int skip, const float* tok, int n_per_sample, int B, int C, int Cvae,
+                                       float* dW, float* db, float* ws, int accumulate, void* stream) {
+    return wordembed_grad_run(dx, ldx, rows_per_sample, skip, tok, n_per_sample, B, C, Cvae, dW, db, ws, accumulate != 0, stream);
+}
+
+// ---- y += x (fp32): the staging buffers of an accumulating backward - the derived embedding gradients and the cvar_gemm fallbacks run on a staging
+// copy exactly as in a plain step - are added into the window's accumulators with one IEEE add per element
+__global__ __launch_bounds__(256) void add_inplace_kernel(float* __restrict__ y, const float* __restrict__ x, long n, int vec) {
+    const long stride = (long)gridDim.x * 256;
+    if (vec) {
+        const long nv = n / 4;
+        for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nv; i += stride) {
+            const f32x4_t a = ((const f32x4_t*)y)[i], b = ((const f32x4_t*)x)[i];
+            f32x4_t r;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) r[e] = a[e] + b[e];
+            ((f32x4_t*)y)[i] = r;
+        }
+        for (long i = nv * 4 + (long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) y[i] = y[i] + x[i];
+    } else {
+        for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) y[i] = y[i] + x[i];
+    }
+}
+extern "C" int cvar_add_inplace(float* y, const float* x, int64_t n, void* stream) {
+    if (!y || !x || n <= 0) return CVAR_EINVAL;
+    if ((((uintptr_t)y | (uintptr_t)x) & 3)) return CVAR_EUNSUPPORTED;
+    const int vec = (((uintptr_t)y | (uintptr_t)x) & 15) == 0;
+    const long work = vec ? (n + 3) / 4 : n;
+    hipLaunchKernelGGL(add_inplace_kernel, dim3((unsigned)min((long)4096, (work + 255) / 256)), dim3(256), 0, as_stream(stream), y, x, (long)n, vec);
     CVAR_CHECK_LAUNCH();
     return CVAR_OK;
 }

@@ -159,14 +159,20 @@ def gemm(A: torch.Tensor, W: torch.Tensor, out: torch.Tensor, *, M: int, N: int,
 
 
 def gemm_tn(A: torch.Tensor, B: torch.Tensor, out: torch.Tensor, *, T: int, Nn: int, Kk: int, lda: int = 0, ldb: int = 0, ldc: int = 0, c_off: int = 0,
-            colsum: Optional[torch.Tensor] = None, colsum_off: int = 0):
+            colsum: Optional[torch.Tensor] = None, colsum_off: int = 0, accumulate: bool = False, use_ws: bool = True):
     """out[n, k] (fp32) = sum_t A[t, n] * B[t, k] - the weight gradient dW = dY^T X on token-major bf16 operands (cvar_gemm_tn).
-    colsum (fp32, optional): colsum[colsum_off + n] = sum_t A[t, n] - the bias gradient - from the same pass"""
+    colsum (fp32, optional): colsum[colsum_off + n] = sum_t A[t, n] - the bias gradient - from the same pass.
+    accumulate: out and colsum become fp32(old + plain) (cvar_gemm_tn_acc, include/cvar_accum.h); use_ws=False: no workspace, hence one token slice"""
     ws = _SPLITK_WS.get((A.device.index, _stream()))
     if ws is None:
         ws = ensure_splitk_workspace(A.device)
     cs = (_ptr(colsum) + 4 * colsum_off) if colsum is not None else None
-    check(_lib.load().cvar_gemm_tn(_ptr(A), lda or Nn, _ptr(B), ldb or Kk, _ptr(out) + 4 * c_off, ldc or Kk, T, Nn, Kk, ws.data_ptr(), ws.numel(), cs, _stream()),
+    wp, wn = (ws.data_ptr(), ws.numel()) if use_ws else (None, 0)
+    if accumulate:
+        check(_lib.load().cvar_gemm_tn_acc(_ptr(A), lda or Nn, _ptr(B), ldb or Kk, _ptr(out) + 4 * c_off, ldc or Kk, T, Nn, Kk, wp, wn, cs, 1, _stream()),
+              'cvar_gemm_tn_acc')
+        return out
+    check(_lib.load().cvar_gemm_tn(_ptr(A), lda or Nn, _ptr(B), ldb or Kk, _ptr(out) + 4 * c_off, ldc or Kk, T, Nn, Kk, wp, wn, cs, _stream()),
           'cvar_gemm_tn')
     return out
 
@@ -564,13 +570,27 @@ def colsum(A, lda, out, M, N, ws, accumulate=False, a_off: int = 0, out_off: int
 
 
 def wordembed_grad(dx, ldx: int, rows_per_sample: int, skip: int, tok, n_per_sample: int, B: int, Cdim: int, Cvae: int, out, w_off: int, b_off: int,
-                   dx_off: int = 0):
-    """dW (Cdim x Cvae at out[w_off:]) and db (out[b_off:]) of word_embed from the token-major fp32 tensors (cvar_wordembed_grad)"""
+                   dx_off: int = 0, accumulate: bool = False):
+    """dW (Cdim x Cvae at out[w_off:]) and db (out[b_off:]) of word_embed from the token-major fp32 tensors (cvar_wordembed_grad);
+    accumulate: both become fp32(old + plain) (cvar_wordembed_grad_acc)"""
     lib = _lib.load()
     nb = lib.cvar_wordembed_grad_ws_bytes(B * n_per_sample, Cdim)
     ws = torch.empty(nb, device=dx.device, dtype=torch.uint8)
+    if accumulate:
+        check(lib.cvar_wordembed_grad_acc(_ptr(dx) + 4 * dx_off, ldx, rows_per_sample, skip, _ptr(tok), n_per_sample, B, Cdim, Cvae,
+                                          _ptr(out) + 4 * w_off, _ptr(out) + 4 * b_off, _ptr(ws), 1, _stream()), 'cvar_wordembed_grad_acc')
+        return
     check(lib.cvar_wordembed_grad(_ptr(dx) + 4 * dx_off, ldx, rows_per_sample, skip, _ptr(tok), n_per_sample, B, Cdim, Cvae,
                                   _ptr(out) + 4 * w_off, _ptr(out) + 4 * b_off, _ptr(ws), _stream()), 'cvar_wordembed_grad')
+
+
+def add_inplace(y, x, n: int, y_off: int = 0, x_off: int = 0):
+    """y[y_off + i] = fp32(y[y_off + i] + x[x_off + i]), i < n, both fp32 and not overlapping (cvar_add_inplace): a staging buffer into an accumulator"""
+    if y.dtype != torch.float32 or x.dtype != torch.float32:
+        raise TypeError('add_inplace: y and x are fp32')
+    if n <= 0 or y_off < 0 or x_off < 0 or y_off + n > y.numel() or x_off + n > x.numel():
+        raise ValueError(f'add_inplace: range of {n} at {y_off} / {x_off} outside tensors of {y.numel()} / {x.numel()} elements')
+    check(_lib.load().cvar_add_inplace(_ptr(y) + 4 * y_off, _ptr(x) + 4 * x_off, n, _stream()), 'cvar_add_inplace')
 
 
 def rowsum(A, lda, out, nrows, ncols, accumulate=False, out_off: int = 0):
@@ -701,13 +721,19 @@ def lora_wgrad_ws_floats(M: int, N: int) -> int:
 
 
 def lora_wgrad(Y, Z, out, ws, *, M: int, N: int, r: int, scale: float = 1.0, p: float = 0.0, seed: int = 0, tag: int = 0, ldy: int = 0,
-               ldz: int = 0, y_off: int = 0, z_off: int = 0, out_off: int = 0, os_n: int = 0, os_j: int = 1):
-    """fp32 out[n * os_n + j * os_j] = scale * sum_m drop(Y)[m, n] Z[m, j] (cvar_lora_wgrad; os_n defaults to r: an [N][r] matrix)"""
+               ldz: int = 0, y_off: int = 0, z_off: int = 0, out_off: int = 0, os_n: int = 0, os_j: int = 1, accumulate: bool = False):
+    """fp32 out[n * os_n + j * os_j] = scale * sum_m drop(Y)[m, n] Z[m, j] (cvar_lora_wgrad; os_n defaults to r: an [N][r] matrix);
+    accumulate: out becomes fp32(old + plain) (cvar_lora_wgrad_acc)"""
     if Y.dtype != Z.dtype:
         raise TypeError('lora_wgrad: Y and Z must share a dtype')
     if out.dtype != torch.float32 or ws.dtype != torch.float32:
         raise TypeError('lora_wgrad: out and ws are fp32')
     es = Y.element_size()
+    if accumulate:
+        check(_lib.load().cvar_lora_wgrad_acc(_ptr(Y) + y_off * es, ldy or N, _ptr(Z) + z_off * es, ldz or r, M, N, r, dt(Y), float(scale), float(p),
+                                              int(seed) & (2 ** 64 - 1), int(tag) & 0xffffffff, _ptr(ws), ws.numel(), _ptr(out) + 4 * out_off,
+                                              os_n or r, os_j, 1, _stream()), 'cvar_lora_wgrad_acc')
+        return out
     check(_lib.load().cvar_lora_wgrad(_ptr(Y) + y_off * es, ldy or N, _ptr(Z) + z_off * es, ldz or r, M, N, r, dt(Y), float(scale), float(p),
                                       int(seed) & (2 ** 64 - 1), int(tag) & 0xffffffff, _ptr(ws), ws.numel(), _ptr(out) + 4 * out_off,
                                       os_n or r, os_j, _stream()), 'cvar_lora_wgrad')

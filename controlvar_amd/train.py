@@ -91,6 +91,40 @@ def filter_params(model, nowd_keys: Iterable[str] = NOWD_KEYS, trainable_only: b
     return names, paras, list(groups.values())
 
 
+class AccumWindow:
+    """Bookkeeping of gradient accumulation, accelerate's semantics (`accelerator.accumulate`, train.py:105 / train_var.py:112 /
+    train_control_var.py:130 of the reference): a window is n consecutive micro-batches, each with its own loss; the optimizer sees
+    (1 / n) * sum_k grad(loss_k) - micro-batches are NOT sample-weighted - and steps once, in the call that closes the window.
+    Plain Python (no device work): Trainer.step asks `begin()` what this call is and reports back with `end()`."""
+
+    def __init__(self, n: int = 1):
+        if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+            raise ValueError(f'grad_accum must be an integer >= 1 (micro-batches per optimizer step), got {n!r}')
+        self.n = n
+        self.micro = 0              # index of the next micro-batch inside its window
+        self.it = 0                 # optimizer steps taken = closed windows (what the lr / wd schedule counts, as accelerator.sync_gradients does)
+
+    def begin(self) -> Tuple[int, bool, bool]:
+        """-> (micro, accumulate, sync) of the call that starts now: the first micro-batch of a window overwrites the gradient
+        buffers, the later ones add to them; the last one reduces, steps the optimizer and closes the window"""
+        return self.micro, self.micro > 0, self.micro == self.n - 1
+
+    def end(self) -> bool:
+        """the call is done; -> whether it closed a window (it then counted one optimizer step)"""
+        if self.micro == self.n - 1:
+            self.micro = 0
+            self.it += 1
+            return True
+        self.micro += 1
+        return False
+
+    @staticmethod
+    def grad_scale(world: int, n: int) -> float:
+        """the gradient buffers hold the SUM over the window's micro-batches and, after the all-reduce, over the ranks: the mean over both
+        is folded into the optimizer's gradient scale (clip coefficient and AdamW alike)"""
+        return 1.0 / (world * n)
+
+
 # =====================================================================================
 # Training engine (GPU): forward with saved activations, hand-written backward, fused optimizer
 # =====================================================================================
@@ -111,6 +145,11 @@ class TrainEngine:
     MFMA GEMM as the forward on transposed operands (activations are transposed into zero-padded [N][Mpad] buffers),
     accumulated in fp32 into per-layer contiguous slabs so that each layer's slab can be all-reduced as soon as its
     backward is done (bucket = layer, overlapped with the rest of the backward on a side stream).
+
+    Gradient accumulation: ``forward_backward(..., accumulate=True)`` adds this micro-batch's gradient to what
+    ``grads()`` holds - every element becomes fp32(old + plain), `plain` being the bits the non-accumulating call produces - so a
+    window of micro-batches leaves their sum in micro-batch order.  The gradient buffers are allocated once per engine and do not
+    depend on the batch size: the micro-batches of a window may differ in size.
     """
 
     def __init__(self, var, drop_path: bool = True, reducer=None):
@@ -121,6 +160,8 @@ class TrainEngine:
         self._B = None
         self._wt_gen = -1
         self._lora = None
+        self._grads_key = None          # what the gradient buffers were allocated for: 'full' or ('lora', id of the LoRA state)
+        self._staging = {}              # accumulating backward: fp32 staging buffers by name (_stage)
 
     # ---------------------------------------------------------------- buffers
     def _setup(self, B: int):
@@ -169,6 +210,20 @@ class TrainEngine:
         self.dada = torch.zeros(B, n_ada, **f32)
         self.ws = torch.empty(max(ops.train_ws_floats(M, B, C), 64 * max(hid, 3 * C, V, n_ada), L * C, B * cfg.H * L,
                                   6 * C * C if cfg.shared_aln else 0) + 16, **f32)
+        self._setup_grads()
+        self._B = B
+        self._transposed_weights()
+
+    def _setup_grads(self):
+        """gradient buffers of the full model: once per engine, whatever the batch size (a window of micro-batches accumulates into them)"""
+        if self._grads_key == 'full':
+            return
+        cfg = self.cfg
+        C, depth, V = cfg.C, cfg.depth, cfg.head_ld
+        L = cfg.pyramid.L
+        hid = round(C * cfg.mlp_ratio)
+        n_ada = depth * 6 * C + 2 * C
+        f32 = dict(device=self.var.device, dtype=torch.float32)
         # gradient slabs: [layer][w_qkv | w_proj | w_fc1 | w_fc2 | b_qkv | b_proj | b_fc1 | b_fc2]
         self.slab_off = {}
         o = 0
@@ -194,8 +249,16 @@ class TrainEngine:
             o += n
         self.G_misc = torch.zeros(o, **f32)
         self.buckets = [self.G_layers[i] for i in range(depth)] + [self.G_ada, self.G_misc]
-        self._B = B
-        self._transposed_weights()
+        self._staging = {}
+        self._grads_key = 'full'
+
+    def _stage(self, name: str, n: int) -> torch.Tensor:
+        """fp32 staging buffer of an accumulating backward (allocated on first use, kept): what cannot take the accumulate flag at its producer
+        is computed here exactly as in a plain step and then added into the accumulator by ops.add_inplace"""
+        t = self._staging.get(name)
+        if t is None or t.numel() < n:
+            t = self._staging[name] = torch.zeros(n, device=self.var.device, dtype=torch.float32)
+        return t
 
     def _transposed_weights(self):
         """W^T copies for the data-gradient GEMMs (refreshed after every optimizer step).  LoRA: of the frozen base weights."""
@@ -280,8 +343,11 @@ class TrainEngine:
     # ---------------------------------------------------------------- forward + backward
     @torch.no_grad()
     def forward_backward(self, label_B: torch.Tensor, x_wo_first: torch.Tensor, cond_type: Optional[torch.Tensor], targets: torch.Tensor,
-                         ignore_mask: Optional[torch.Tensor] = None, drop_seed: Optional[int] = None, mask_first: bool = True):
-        """-> (loss scalar tensor, per-token loss (B*L,)); gradients land in self.grads() (overwritten, not accumulated)."""
+                         ignore_mask: Optional[torch.Tensor] = None, drop_seed: Optional[int] = None, mask_first: bool = True,
+                         accumulate: bool = False):
+        """-> (loss scalar tensor, per-token loss (B*L,)); gradients land in self.grads(): overwritten, or with accumulate=True added to what
+        it holds - fp32(old + this micro-batch's plain gradient) per element, whatever the batch size of the earlier calls.  The loss and its
+        1 / M scale are this micro-batch's own; the 1 / N of a window of N belongs to the optimizer's gradient scale (FusedAdamW.step)."""
         self.forward_train(label_B, x_wo_first, cond_type, drop_seed, mask_first)
         dev = self.var.device
         M, V = self.M, self.cfg.head_ld
@@ -293,7 +359,7 @@ class TrainEngine:
             w, gscale = None, 1.0 / M
         ops.ce_fwd_bwd(self.logits, tg, w, gscale, self.loss_tok, self.dlogits, M, V)
         loss = (self.loss_tok * w).mean() / (w.mean() + 1e-6) if w is not None else self.loss_tok.mean()
-        self.backward()
+        self.backward(accumulate=accumulate)
         return loss, self.loss_tok
 
     @torch.no_grad()
@@ -388,27 +454,38 @@ class TrainEngine:
         return self.logits
 
     @torch.no_grad()
-    def _wgrad(self, dY, n_out: int, X, k_in: int, G, w_off: int, b_off=None):
+    def _wgrad(self, dY, n_out: int, X, k_in: int, G, w_off: int, b_off=None, acc: bool = False):
         """dW[n_out, k_in] = dY^T X into the fp32 gradient slab (+ the bias gradient = column sums of dY).  bf16 mode: `cvar_gemm_tn` reads both
         token-major operands in place (LDS transpose-read) - no transposed copies; shapes it does not take (a dimension that is not a
-        multiple of its tile, the fp32 parity mode) go through two HBM transposes + `cvar_gemm` as in round 1."""
+        multiple of its tile, the fp32 parity mode) go through two HBM transposes + `cvar_gemm` as in round 1.  acc: add to what G holds -
+        `cvar_gemm_tn_acc`; the fallback computes into a staging buffer and adds it (cvar_gemm's kernels have no accumulating form)."""
         M, Mp = self.M, self.Mp
         if (dY.dtype == torch.bfloat16 and X.dtype == torch.bfloat16 and n_out % 128 == 0 and k_in % 128 == 0
                 and 2 * M * max(n_out, k_in) < 2 ** 31 - 1):
             # the bias gradient (column sums of dY) rides on the same pass: ones-operand MFMAs on the dY fragments (round 3; a separate colsum pass before)
-            ops.gemm_tn(dY, X, G, T=M, Nn=n_out, Kk=k_in, c_off=w_off, colsum=G if b_off is not None else None, colsum_off=b_off or 0)
+            ops.gemm_tn(dY, X, G, T=M, Nn=n_out, Kk=k_in, c_off=w_off, colsum=G if b_off is not None else None, colsum_off=b_off or 0, accumulate=acc)
             return
         ops.transpose(dY, self.TA, 1, M, n_out, n_out, ld_out=Mp)
         ops.transpose(X, self.TB, 1, M, k_in, k_in, ld_out=Mp)
-        ops.gemm(self.TA, self.TB, G, M=n_out, N=k_in, K=Mp, c_off=w_off)
+        if acc:
+            S = self._stage('wgrad', n_out * k_in)
+            ops.gemm(self.TA, self.TB, S, M=n_out, N=k_in, K=Mp)
+            ops.add_inplace(G, S, n_out * k_in, y_off=w_off)
+        else:
+            ops.gemm(self.TA, self.TB, G, M=n_out, N=k_in, K=Mp, c_off=w_off)
         if b_off is not None:
-            ops.rowsum(self.TA, Mp, G, n_out, M, out_off=b_off)
+            ops.rowsum(self.TA, Mp, G, n_out, M, accumulate=acc, out_off=b_off)
 
-    def backward(self):
-        """backward from self.dlogits (compute dtype, (B*L, V)) through head, blocks, adaLN generator and embeddings"""
+    def backward(self, accumulate: bool = False):
+        """backward from self.dlogits (compute dtype, (B*L, V)) through head, blocks, adaLN generator and embeddings.  accumulate: every
+        gradient element becomes fp32(old + plain).  The weight-gradient GEMMs, bias sums and the word-embedding gradient add at their
+        producer; the adaLN generator's gradient and the small embedding gradients - several of which are DERIVED from other entries of
+        the gradient buffer (lvl / type from pos, pos_start a copy, w_shared / b_shared sums over G_ada, class_emb / cond_embed zeroed
+        and scattered into) - are computed on staging copies exactly as in a plain step and then added."""
         cfg, var = self.cfg, self.var
+        acc = bool(accumulate)
         if self._lora is not None:
-            return self._backward_lora()
+            return self._backward_lora(acc)
         P = var._pack()
         py, C, depth, V, H = cfg.pyramid, cfg.C, cfg.depth, cfg.head_ld, cfg.H
         L, fl = py.L, py.first_l
@@ -429,7 +506,7 @@ class TrainEngine:
         mo = self.misc_off
         self.dada.zero_()
         ops.gemm(self.dlogits, self.WT['head'], self.DU, M=M, N=C, K=V)
-        self._wgrad(self.dlogits, V, self.UH, C, self.G_misc, mo['w_head'][0], mo['b_head'][0])
+        self._wgrad(self.dlogits, V, self.UH, C, self.G_misc, mo['w_head'][0], mo['b_head'][0], acc)
         ops.ln_modulate_bwd(self.Xs[depth], self.DU, ada, ah, n_ada, L, None, self.dX, self.dada, ah, ah + C, n_ada, M, C, eps, ws)
         # ---- backward: blocks
         for i in reversed(range(depth)):
@@ -439,20 +516,20 @@ class TrainEngine:
             # FFN branch
             ops.gated_grad(self.dX, self.F2[i], ada, a0 + C, n_ada, dp2[i].contiguous() if dp2 is not None else None, self.DF, self.dada, a0 + C, n_ada, B, L, C, ws)
             ops.gemm(self.DF, self.WT['fc2'], self.DH, M=M, N=hid, K=C, w_off=i * hid * C, act=ACT_GELU_GRAD, aux=self.A[i])   # dH = (dF W2) * gelu'(A)
-            self._wgrad(self.DF, C, self.Hh[i], hid, G, go + so['w_fc2'], go + so['b_fc2'])
+            self._wgrad(self.DF, C, self.Hh[i], hid, G, go + so['w_fc2'], go + so['b_fc2'], acc)
             ops.gemm(self.DH, self.WT['fc1'], self.DU, M=M, N=C, K=hid, w_off=i * C * hid)
-            self._wgrad(self.DH, hid, self.U2[i], C, G, go + so['w_fc1'], go + so['b_fc1'])
+            self._wgrad(self.DH, hid, self.U2[i], C, G, go + so['w_fc1'], go + so['b_fc1'], acc)
             ops.ln_modulate_bwd(self.X1s[i], self.DU, ada, a0 + 3 * C, n_ada, L, self.dX, self.dX, self.dada, a0 + 3 * C, a0 + 5 * C, n_ada, M, C, eps, ws)
             # attention branch
             ops.gated_grad(self.dX, self.F1[i], ada, a0, n_ada, dp1[i].contiguous() if dp1 is not None else None, self.DF, self.dada, a0, n_ada, B, L, C, ws)
             ops.gemm(self.DF, self.WT['proj'], self.DU, M=M, N=C, K=C, w_off=i * C * C)
-            self._wgrad(self.DF, C, self.O[i], C, G, go + so['w_proj'], go + so['b_proj'])
+            self._wgrad(self.DF, C, self.O[i], C, G, go + so['w_proj'], go + so['b_proj'], acc)
             ops.attention_bwd(self.arena[i], self.O[i], self.DU, self.LSE[i], self.DQKV, ws, B, H, L, L, scale, lvl_end, holes=holes)
             if cfg.uses_cos_attn:           # normalisation + learned temperature of basic_var.py:99-104
                 ops.cos_qk_norm_bwd(self.arena[i], self.DQKV, B, H, L, L, P['scale_mul'], self.NORMS[i], self.DSM, sm_off=i * H)
-                ops.colsum(self.DSM, H, G, M, H, ws, out_off=go + so['scale_mul'])
+                ops.colsum(self.DSM, H, G, M, H, ws, accumulate=acc, out_off=go + so['scale_mul'])
             ops.gemm(self.DQKV, self.WT['qkv'], self.DU, M=M, N=C, K=3 * C, w_off=i * C * 3 * C)
-            self._wgrad(self.DQKV, 3 * C, self.U[i], C, G, go + so['w_qkv'], go + so['b_qkv'])      # the k-bias third is unused (zero_k_bias is a buffer)
+            self._wgrad(self.DQKV, 3 * C, self.U[i], C, G, go + so['w_qkv'], go + so['b_qkv'], acc)      # the k-bias third is unused (zero_k_bias is a buffer)
             ops.ln_modulate_bwd(self.Xs[i], self.DU, ada, a0 + 2 * C, n_ada, L, self.dX, self.dX, self.dada, a0 + 2 * C, a0 + 4 * C, n_ada, M, C, eps, ws)
             if self.reducer is not None:
                 self.reducer.ready(i)
@@ -465,17 +542,21 @@ class TrainEngine:
         tB = torch.zeros(C, Bp, device=dev, dtype=T)
         ops.transpose(dada_T, tA, 1, B, n_ada, n_ada, ld_out=Bp)
         ops.transpose(cs, tB, 1, B, C, C, ld_out=Bp)
-        ops.gemm(tA, tB, self.G_ada, M=n_ada, N=C, K=Bp)
-        ops.colsum(self.dada, n_ada, self.G_ada, B, n_ada, ws, out_off=n_ada * C)
+        # accumulating: this micro-batch's values go to staging copies (Ga, Gm) - what is derived below must be derived from them, not from the window's sum
+        Ga = self._stage('ada', self.G_ada.numel()) if acc else self.G_ada
+        Gm = self._stage('misc', self.G_misc.numel()) if acc else self.G_misc
+        ops.gemm(tA, tB, Ga, M=n_ada, N=C, K=Bp)
+        ops.colsum(self.dada, n_ada, Ga, B, n_ada, ws, out_off=n_ada * C)
         if cfg.shared_aln:          # rows = blocks: column sums over the depth axis of the folded per-block gradients
-            ops.colsum(self.G_ada, 6 * C * C, self.G_misc, depth, 6 * C * C, ws, out_off=mo['w_shared'][0])
-            ops.colsum(self.G_ada, 6 * C, self.G_misc, depth, 6 * C, ws, a_off=n_ada * C, out_off=mo['b_shared'][0])
+            ops.colsum(Ga, 6 * C * C, Gm, depth, 6 * C * C, ws, out_off=mo['w_shared'][0])
+            ops.colsum(Ga, 6 * C, Gm, depth, 6 * C, ws, a_off=n_ada * C, out_off=mo['b_shared'][0])
+        if acc:
+            ops.add_inplace(self.G_ada, Ga, self.G_ada.numel())
         dcond = torch.empty(B, C, device=dev, dtype=torch.float32)
         ops.silu_bwd(cond, dsilu, dcond)
         if self.reducer is not None:
             self.reducer.ready(depth)
         # ---- backward: embeddings (dX now holds d loss / d x0)
-        Gm = self.G_misc
         ops.colsum(self.dX, L * C, Gm, B, L * C, ws, out_off=mo['pos'][0])
         for k, (b0, e0) in enumerate(zip(py.begin, py.end)):
             ops.colsum(Gm, C, Gm, e0 - b0, C, ws, a_off=mo['pos'][0] + b0 * C, out_off=mo['lvl'][0] + k * C)
@@ -490,12 +571,12 @@ class TrainEngine:
         if cfg.separator:           # code rows are interleaved with the separator rows: gather them; the separators' gradient is the batch sum of their rows
             code = torch.from_numpy(py.code_positions()[fl:]).to(dev)
             dXw = self.dX.view(B, L, C)[:, code].contiguous()               # (B, ncode, C)
-            self._word_embed_grads(tok, B, self.ncode + fl, fl, C, Mt, Mtp, src=dXw, src_has_first=False)
+            we_staged = self._word_embed_grads(tok, B, self.ncode + fl, fl, C, Mt, Mtp, Gm, acc, src=dXw, src_has_first=False)
             mapping = cfg.special_mapping(self._mask_first)
             for j, pos in enumerate(int(q) for q in py.special_positions()):
                 ops.colsum(self.dX, L * C, Gm, B, C, ws, a_off=pos * C, out_off=mo['special'][0] + mapping[j] * C)
         else:
-            self._word_embed_grads(tok, B, L, fl, C, Mt, Mtp)
+            we_staged = self._word_embed_grads(tok, B, L, fl, C, Mt, Mtp, Gm, acc)
         cls_o, cnd_o = mo['class_emb'][0], mo['cond_embed'][0]
         Gm[cls_o:cls_o + mo['class_emb'][1]].zero_()
         Gm[cnd_o:cnd_o + mo['cond_embed'][1]].zero_()
@@ -505,6 +586,9 @@ class TrainEngine:
         ops.scatter_add_rows(dcond, C, labels, g_class, B, C)
         if cfg.mask_factor == 2:
             ops.scatter_add_rows(self.dX, L * C, types, Gm[cnd_o:cnd_o + mo['cond_embed'][1]], B, C, src_off=(1 - sos_row) * C)
+        if acc:         # misc layout: [w_head | b_head | w_we | b_we | pos ... ]: the head added at its GEMM, word_embed at its kernel unless it took the slow path
+            o0 = mo['w_we'][0] if we_staged else mo['pos'][0]
+            ops.add_inplace(self.G_misc, Gm, self.G_misc.numel() - o0, y_off=o0, x_off=o0)
         if self.reducer is not None:
             self.reducer.ready(depth + 1)
 
@@ -580,9 +664,11 @@ class TrainEngine:
                 o += shape[0] * shape[1]
         if set(self.lora_off) != {n for n, p in var.named_parameters() if p.requires_grad}:
             raise RuntimeError('LoRA: the trainable parameters are not exactly the adapters of add_lora')
-        self.G_lora = torch.zeros(o, **f32)
-        starts = [0] + bounds
-        self.buckets = [self.G_lora[starts[i]:starts[i + 1]] for i in range(depth)] + [self.G_lora[bounds[-1]:]]
+        if self._grads_key != ('lora', id(lora)):                  # once per adapter state, whatever the batch size (a window accumulates into it)
+            self.G_lora = torch.zeros(o, **f32)
+            starts = [0] + bounds
+            self.buckets = [self.G_lora[starts[i]:starts[i + 1]] for i in range(depth)] + [self.G_lora[bounds[-1]:]]
+            self._grads_key = ('lora', id(lora))
         self._aug = None
         self._B = key
         self._transposed_weights()
@@ -664,7 +750,7 @@ class TrainEngine:
         ops.gemm(self.Hha[i], self.Wa['fc2'], self.Xs[i + 1], M=M, N=C, K=kh, lda=kh, ldw=kh, w_off=i * C * kh, bias=P['b_fc2'][i], gate=ada, ldg=n_ada,
                  gate_rows=L, gate_off=a0 + C, gate_scale=dp2[i].contiguous() if dp2 is not None else None, residual=self.X1s[i], pre_act=self.F2[i])
 
-    def _lora_grads_of(self, i, kind, name, dY, n_out, x, k_in, ldx, x_off_u, aux=None, ldaux=0):
+    def _lora_grads_of(self, i, kind, name, dY, n_out, x, k_in, ldx, x_off_u, aux=None, ldaux=0, acc=False):
         """du = dY B; dx (self.DU / self.DH, in place) += branch share (* gelu'(aux)); dB = dY^T u; dA = s du^T drop(x).  x: the augmented
         saved input [x | u] with row stride ldx, u at column x_off_u"""
         lo, M, r = self._lora, self.M, self.r
@@ -675,12 +761,13 @@ class TrainEngine:
         ops.lora_down(dY, self.LBT[kind][i], self.DUr, M=M, K=n_out, r=r, scale=1.0, ldu=16)
         dx = self.DH if kind == 'fc2' else self.DU
         ops.lora_dx(dx, self.DUr, self.LA[kind][i], M=M, K=k_in, r=r, scale=s, p=p, seed=seed, tag=tag, lddu=16, aux=aux, ldaux=ldaux)
-        ops.lora_wgrad(dY, x, G, self.lws, M=M, N=n_out, r=r, ldz=ldx, z_off=x_off_u, out_off=oB)
-        ops.lora_wgrad(x, self.DUr, G, self.lws, M=M, N=k_in, r=r, scale=s, p=p, seed=seed, tag=tag, ldy=ldx, ldz=16, out_off=oA, os_n=1, os_j=k_in)
+        ops.lora_wgrad(dY, x, G, self.lws, M=M, N=n_out, r=r, ldz=ldx, z_off=x_off_u, out_off=oB, accumulate=acc)
+        ops.lora_wgrad(x, self.DUr, G, self.lws, M=M, N=k_in, r=r, scale=s, p=p, seed=seed, tag=tag, ldy=ldx, ldz=16, out_off=oA, os_n=1, os_j=k_in,
+                       accumulate=acc)
 
-    def _backward_lora(self):
+    def _backward_lora(self, acc: bool = False):
         """backward of a LoRA model: data gradients through the frozen base (no weight-gradient GEMMs, no embedding gradients) plus
-        the adapter gradients into self.G_lora"""
+        the adapter gradients into self.G_lora (acc: added to it by cvar_lora_wgrad_acc)"""
         cfg, var = self.cfg, self.var
         P = var._pack(base=True)
         py, C, depth, V, H = cfg.pyramid, cfg.C, cfg.depth, cfg.head_ld, cfg.H
@@ -707,14 +794,14 @@ class TrainEngine:
             # FFN branch: fc2's data-gradient GEMM runs without its GELU' - cvar_lora_dx applies it after adding the branch's share
             ops.gated_grad(self.dX, self.F2[i], ada, a0 + C, n_ada, dp2[i].contiguous() if dp2 is not None else None, self.DF, self.dada, a0 + C, n_ada, B, L, C, ws)
             ops.gemm(self.DF, self.WT['fc2'], self.DH, M=M, N=hid, K=C, w_off=i * hid * C)
-            self._lora_grads_of(i, 'fc2', p_ + 'ffn.fc2', self.DF, C, self.Hha[i], hid, kh, hid, aux=self.Aa[i], ldaux=kh)
+            self._lora_grads_of(i, 'fc2', p_ + 'ffn.fc2', self.DF, C, self.Hha[i], hid, kh, hid, aux=self.Aa[i], ldaux=kh, acc=acc)
             ops.gemm(self.DH, self.WT['fc1'], self.DU, M=M, N=C, K=hid, w_off=i * C * hid)
-            self._lora_grads_of(i, 'fc1', p_ + 'ffn.fc1', self.DH, hid, self.U2a[i], C, kc, C)
+            self._lora_grads_of(i, 'fc1', p_ + 'ffn.fc1', self.DH, hid, self.U2a[i], C, kc, C, acc=acc)
             ops.ln_modulate_bwd(self.X1s[i], self.DU, ada, a0 + 3 * C, n_ada, L, self.dX, self.dX, self.dada, a0 + 3 * C, a0 + 5 * C, n_ada, M, C, eps, ws)
             # attention branch
             ops.gated_grad(self.dX, self.F1[i], ada, a0, n_ada, dp1[i].contiguous() if dp1 is not None else None, self.DF, self.dada, a0, n_ada, B, L, C, ws)
             ops.gemm(self.DF, self.WT['proj'], self.DU, M=M, N=C, K=C, w_off=i * C * C)
-            self._lora_grads_of(i, 'proj', p_ + 'attn.proj', self.DF, C, self.Oa[i], C, kc, C)
+            self._lora_grads_of(i, 'proj', p_ + 'attn.proj', self.DF, C, self.Oa[i], C, kc, C, acc=acc)
             ops.attention_bwd(self.arena[i], self.O[i], self.DU, self.LSE[i], self.DQKV, ws, B, H, L, L, scale, lvl_end, holes=holes)
             if cfg.uses_cos_attn:
                 ops.cos_qk_norm_bwd(self.arena[i], self.DQKV, B, H, L, L, P['scale_mul'], self.NORMS[i], self.DSM, sm_off=i * H)
@@ -733,32 +820,34 @@ class TrainEngine:
             oA = self.lora_off[f'{name}.lora_A.default.weight'][0]
             oB = self.lora_off[f'{name}.lora_B.default.weight'][0]
             ops.lora_down(dada_T, self.LBT['ada'][t], self.DUa, M=B, K=n_out, r=r, scale=1.0, ldx=n_ada, x_off=t * 6 * C, lda=6 * C, ldu=16)
-            ops.lora_wgrad(dada_T, self.csa, self.G_lora, self.lws, M=B, N=n_out, r=r, ldy=n_ada, y_off=t * 6 * C, ldz=ld, z_off=C + 16 * t, out_off=oB)
+            ops.lora_wgrad(dada_T, self.csa, self.G_lora, self.lws, M=B, N=n_out, r=r, ldy=n_ada, y_off=t * 6 * C, ldz=ld, z_off=C + 16 * t, out_off=oB,
+                           accumulate=acc)
             ops.lora_wgrad(self.csa, self.DUa, self.G_lora, self.lws, M=B, N=C, r=r, scale=s, p=p, seed=seed, tag=self._tag(t, 'ada'), ldy=ld, ldz=16,
-                           out_off=oA, os_n=1, os_j=C)
+                           out_off=oA, os_n=1, os_j=C, accumulate=acc)
         if self.reducer is not None:
             self.reducer.ready(depth)
 
 
-    def _word_embed_grads(self, tok, B, L, fl, C, Mt, Mtp, src=None, src_has_first=True):
+    def _word_embed_grads(self, tok, B, L, fl, C, Mt, Mtp, Gm, acc=False, src=None, src_has_first=True):
         """src: gradient rows of the word-embedded tokens - self.dX with L rows per sample of which the first fl are skipped, or a compact
-        (B, L - fl, C) gather of them (separator models)"""
+        (B, L - fl, C) gather of them (separator models).  Gm: where the plain values go (self.G_misc, or its staging copy when acc); the
+        one-pass kernel adds into self.G_misc itself when acc.  -> True if the values were left in the staging copy for the caller to add"""
         cfg = self.cfg
         mo = self.misc_off
-        Gm = self.G_misc
         src = self.dX if src is None else src
         rows = L if src_has_first else L - fl
         skip = fl if src_has_first else 0
         if cfg.cvae == 32 and C % 64 == 0 and tok.dtype == torch.float32 and src.dtype == torch.float32:
             # one pass over the token-major tensors (round 3): dW and db together, no transposes, no per-sample launches
-            ops.wordembed_grad(src, C, rows, skip, tok, L - fl, B, C, cfg.cvae, Gm, mo['w_we'][0], mo['b_we'][0])
-            return
+            ops.wordembed_grad(src, C, rows, skip, tok, L - fl, B, C, cfg.cvae, self.G_misc if acc else Gm, mo['w_we'][0], mo['b_we'][0], accumulate=acc)
+            return False
         for b in range(B):      # gradient rows of sample b -> columns [b*(L-fl), (b+1)*(L-fl)) of TA32 ([C][Mtp])
             ops.transpose(src, self.TA32[b * (L - fl):], 1, L - fl, C, C, in_off=(b * rows + skip) * C, ld_out=Mtp)
         ops.transpose(tok, self.TB32, 1, Mt, cfg.cvae, cfg.cvae, ld_out=Mtp)
         ops.gemm(self.TA32, self.TB32, Gm, M=C, N=cfg.cvae, K=Mtp, c_off=mo['w_we'][0])
         for b in range(B):
             ops.colsum(src, C, Gm, L - fl, C, self.ws, accumulate=(b > 0), a_off=(b * rows + skip) * C, out_off=mo['b_we'][0])
+        return acc
 
 
 class BucketReducer:
@@ -832,8 +921,9 @@ class FusedAdamW:
         self.fuse_copies = True                                  # False: rebuild every packed copy from the fp32 parameters after a step
 
     @torch.no_grad()
-    def step(self, grads: Dict[str, torch.Tensor], max_norm: float = 0.0, world: int = 1) -> torch.Tensor:
-        """returns a device tensor [grad_norm (of the world-averaged gradient), clip coefficient]"""
+    def step(self, grads: Dict[str, torch.Tensor], max_norm: float = 0.0, world: int = 1, accum: int = 1) -> torch.Tensor:
+        """returns a device tensor [grad_norm (of the averaged gradient), clip coefficient].  `grads` holds the sum over `world` ranks and over
+        the `accum` micro-batches of a window: the gradient scale is 1 / (world * accum)"""
         dev = self.named[0][1].device
         n = len(self.named)
         if self._partial is None:
@@ -855,11 +945,12 @@ class FusedAdamW:
             self._table = ops.adam_table(entries, dev)
             self._table_sig = sig
         ops.sumsq_multi(self._table, n, self._partial)
-        ops.clip_coef(self._partial, n * 256, 1.0 / world, float(max_norm), self._out2)
+        gscale = AccumWindow.grad_scale(world, accum)
+        ops.clip_coef(self._partial, n * 256, gscale, float(max_norm), self._out2)
         self.steps += 1
         coef = self._out2[1:]
         ops.adamw_multi(self._table, n, [float(g['lr']) for g in self.param_groups], [float(g['weight_decay']) for g in self.param_groups],
-                        self.betas[0], self.betas[1], self.eps, self.steps, coef, 1.0 / world)
+                        self.betas[0], self.betas[1], self.eps, self.steps, coef, gscale)
         if fresh:
             self.var._pack(fresh=fresh)                          # the matrices are current; biases / tables are rebuilt from the parameters
         else:
@@ -909,14 +1000,24 @@ class FusedAdamW:
 
 
 class Trainer:
-    """One process per GPU; the step of train_control_var_hpu.py:130-255 (minus its logging / gradient-accumulation quirks)."""
+    """One process per GPU; the step of train_control_var_hpu.py:130-255 (minus its logging and its own accumulation quirk: it steps the
+    optimizer every batch and zeroes the gradients every N-th).
+
+    grad_accum=N accumulates gradients over windows of N calls of step() with the semantics of `accelerator.accumulate` (train.py:105,
+    train_var.py:112, train_control_var.py:130): step() is called once per micro-batch, as the reference's loop body is; calls 1 .. N-1 of a
+    window run tokenizer, forward and backward only, call N also all-reduces, clips, steps AdamW with the mean of the N micro-batch gradients
+    (micro-batches weigh the same whatever their size) and advances `it`.  The lr / wd schedule counts optimizer steps.  N = 1 is the plain
+    step.  See AccumWindow and DESIGN.md 8c."""
 
     def __init__(self, var, vae, peak_lr: float, weight_decay: float, weight_decay_end: Optional[float] = None, sche: str = 'lin0',
                  warmup_it: float = 0, max_it: int = 1000, clip: float = 2.0, wp0: float = 0.005, wpe: float = 0.01, drop_path: bool = True,
-                 train_mode: Optional[bool] = None, force_reducer: bool = False):
+                 train_mode: Optional[bool] = None, force_reducer: bool = False, grad_accum: int = 1):
         """train_mode: True puts the model in train() (DropPath active, as the reference's loop runs it, train_control_var_hpu.py:136),
         False in eval(); None leaves the mode as the caller set it."""
         import torch.distributed as dist
+        self.window = AccumWindow(grad_accum)           # refuses N < 1 before anything is built
+        self.grad_accum = grad_accum
+        self._loss_sum = None
         self.var, self.vae = var, vae
         if train_mode is not None:
             var.train(train_mode)
@@ -925,12 +1026,20 @@ class Trainer:
         self.sched = dict(sche=sche, peak_lr=peak_lr, wd=weight_decay, wd_end=weight_decay if weight_decay_end is None else weight_decay_end,
                           wp_it=warmup_it, max_it=max_it, wp0=wp0, wpe=wpe)
         self.clip = clip
-        self.it = 0
         self.world = dist.get_world_size() if dist.is_initialized() else 1
         self.force_reducer = force_reducer
         self.comm = True                        # False: skip the gradient exchange (bench.py measures the exposed communication time with it)
         self.comm_group = None                  # process group of the gradient exchange (None = default); see set_comm_group
         self._reducer_for = None
+
+    @property
+    def it(self) -> int:
+        """optimizer steps taken (the iteration the lr / wd schedule is evaluated at)"""
+        return self.window.it
+
+    @it.setter
+    def it(self, value: int):
+        self.window.it = int(value)
 
     def set_comm_group(self, group):
         """run the gradient all-reduce in `group` from the next step on (launcher.channel_groups: one group per RCCL channel cap)"""
@@ -967,7 +1076,13 @@ class Trainer:
     @torch.no_grad()
     def step(self, images, masks, cls, types, ignore_mask=None, drop_seed=None, mask_first: Optional[bool] = None) -> Dict[str, object]:
         """mask_first=None draws the order as the reference does (image first with probability 1/2 when the model is bidirectional,
-        python `random`, train_control_var_hpu.py:192-199); pass the matching ``ignore_mask`` / ``ignore_mask_`` (:234)."""
+        python `random`, train_control_var_hpu.py:192-199); pass the matching ``ignore_mask`` / ``ignore_mask_`` (:234).  It is drawn per
+        call, as the reference draws it per batch; ``drop_seed`` is per call too.
+
+        One call = one micro-batch.  The returned dict carries ``micro`` (index inside the window) and ``synced`` (this call closed the window
+        and stepped the optimizer).  A call that does not sync returns its micro-batch loss and ``grad_norm`` / ``clip_coef`` None; the one
+        that does returns the last micro-batch's ``loss`` next to ``window_loss``, the mean of the window's micro-batch losses."""
+        micro, accumulate, sync = self.window.begin()
         if mask_first is None:
             import random
             mask_first = not (getattr(self.var, 'bidirectional', False) and random.random() < 0.5)
@@ -975,21 +1090,29 @@ class Trainer:
         _, max_lr, _, max_wd = lr_wd_annealing(s['sche'], self.opt, s['peak_lr'], s['wd'], s['wd_end'], self.it, s['wp_it'], s['max_it'], wp0=s['wp0'], wpe=s['wpe'])
         x, labels = self.tokenize(images, masks, mask_first)
         self.engine._setup(x.shape[0])
-        if (self.world > 1 or self.force_reducer) and self.comm:
+        if (self.world > 1 or self.force_reducer) and self.comm and sync:         # the all-reduce rides on the backward that closes the window
             if self._reducer_for is not self.engine.buckets:
                 self._reducer = BucketReducer(self.engine.buckets, group=self.comm_group, force=self.force_reducer)
                 self._reducer_for = self.engine.buckets
             self.engine.reducer = self._reducer
         else:
             self.engine.reducer = None
-        loss, _ = self.engine.forward_backward(cls, x, types, labels, ignore_mask, drop_seed, mask_first)
+        loss, _ = self.engine.forward_backward(cls, x, types, labels, ignore_mask, drop_seed, mask_first, accumulate=accumulate)
+        n = self.window.n
+        if n > 1:
+            self._loss_sum = loss if micro == 0 else self._loss_sum + loss
+        if not sync:
+            self.window.end()
+            return dict(loss=loss, grad_norm=None, clip_coef=None, lr=max_lr, wd=max_wd, mask_first=mask_first, synced=False, micro=micro)
         if self.engine.reducer is not None:
             self.engine.reducer.wait()
-        norm_coef = self.opt.step(self.engine.grads(), self.clip, self.world)
+        norm_coef = self.opt.step(self.engine.grads(), self.clip, self.world, n)
         if self.engine._lora is None:                # LoRA: the base weights (and their W^T copies) do not move
             self.engine._transposed_weights()
-        self.it += 1
-        return dict(loss=loss, grad_norm=norm_coef[0], clip_coef=norm_coef[1], lr=max_lr, wd=max_wd, mask_first=mask_first)
+        self.window.end()
+        window_loss = self._loss_sum / n if n > 1 else loss
+        return dict(loss=loss, window_loss=window_loss, grad_norm=norm_coef[0], clip_coef=norm_coef[1], lr=max_lr, wd=max_wd, mask_first=mask_first,
+                    synced=True, micro=micro)
 
 
 class _TeacherForcedFn(torch.autograd.Function):
