@@ -1,4 +1,4 @@
-"""ctypes binding of libcvar_hip.so (include/cvar.h, include/cvar_serve.h, include/cvar_accum.h).  No torch types cross this boundary:
+"""ctypes binding of libcvar_hip.so (include/cvar.h, include/cvar_serve.h, include/cvar_accum.h, include/cvar_kvcache.h).  No torch types cross this boundary:
 callers hand over raw device pointers (``tensor.data_ptr()``), sizes and the HIP stream handle.
 
 The library is mandatory on the product path: if it is missing or does not load, every op
@@ -141,6 +141,13 @@ ACCUM_SIGNATURES = {
     'cvar_add_inplace': (c_i, [c_p, c_p, c_l, c_p]),
 }
 
+# include/cvar_kvcache.h: the e4m3 K/V cache of generation (kv_precision='fp8') - the append pass and the attention over the quantised arena.  A table
+# of its own for the same reason; no signature of the other three headers changed, so neither version moved
+KVCACHE_SIGNATURES = {
+    'cvar_kv_append_fp8': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
+    'cvar_attention_kv8': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, C.POINTER(c_i), c_i, C.POINTER(c_i), c_p, c_p, c_p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -163,7 +170,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         except Exception:  # pragma: no cover
             pass
         lib = C.CDLL(path, mode=C.RTLD_GLOBAL)
-        for name, (res, args) in (*SIGNATURES.items(), *SERVE_SIGNATURES.items(), *ACCUM_SIGNATURES.items()):
+        for name, (res, args) in (*SIGNATURES.items(), *SERVE_SIGNATURES.items(), *ACCUM_SIGNATURES.items(), *KVCACHE_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -6,6 +6,8 @@
 // query row (q, o in registers), K/V tiles of 64 keys are staged in LDS as fp32 and read as wave-wide
 // broadcasts; block-wise online softmax (one rescale per 64-key tile).
 #include "cvar_common.h"
+#include "fp8_quant.h"
+#include "../../include/cvar_kvcache.h"
 #include <type_traits>
 
 constexpr int CVAR_ATTN_MAX_LVL = 32;
@@ -22,6 +24,9 @@ struct AttnParams {
     int hole_lo[CVAR_ATTN_MAX_LVL], hole_hi[CVAR_ATTN_MAX_LVL];     // per level: keys [lo, hi) are invisible to its queries (empty: lo = hi = INT_MAX)
     float* lse;          // optional [R][H][l] log-sum-exp of the scaled scores (saved for the backward pass)
 };
+// kv_precision='fp8' (include/cvar_kvcache.h): qkv holds e4m3 BYTES [R][Lmax][ldkv], kv_scale one power-of-two fp32 scale per (row, key, k|v head): [R][Lmax][2H].
+// A type of its own: the kernel arguments of the bf16 instantiations stay what they were.
+struct AttnParamsKV8 : AttnParams { const float* kv_scale; };
 
 // Visibility of one query: keys [0, kvlen) minus the hole [hlo, hhi).  The prefix is the block-causal level mask of training
 // (control_var.py:158-168) or, with half-scale levels, of separate_decoding (:170-180); the hole is the `indep` variant, where the image
@@ -193,7 +198,7 @@ __global__ __launch_bounds__(256) void attn_rowwise_kernel(const AttnParams p) {
 }
 
 // (a template takes its launch bounds from the FIRST declaration: without them here the kernels are compiled for 1024-thread groups, 128 VGPRs)
-template <bool HOLES, bool QPRE, int G> __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(G == 1 ? 3 : 2, G == 1 ? 3 : 2))) void attn_mfma_bf16_kernel(const AttnParams p);
+template <bool HOLES, bool QPRE, int G, bool KV8 = false> __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(G == 1 ? 3 : 2, G == 1 ? 3 : 2))) void attn_mfma_bf16_kernel(const std::conditional_t<KV8, AttnParamsKV8, AttnParams> p);
 template <bool HOLES> __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void attn_mfma_bf16_v1_kernel(const AttnParams p);
 #ifndef CVAR_ATTN_Q64
 #define CVAR_ATTN_Q64 1
@@ -226,20 +231,33 @@ static int fill_levels(P& p, const int* lvl_end_host, int n_lvl, const int* hole
     return CVAR_OK;
 }
 
+// G = 2 or G = 1 (one rule for the bf16 and the e4m3 arena):
+static bool attn_two_groups(const AttnParams& p, bool qpre) {
+    // prescaled queries, long scales: 64 queries per wave (K / V fragments, tiles and barriers shared by two query groups)
+    // (only where the last 256-query workgroup is nearly full: l = 512 runs 1.371 -> 1.285 ms per call at B = 128, l = 338 - 82 queries in its second workgroup -
+    //  0.685 -> 0.82 ms and stays on 32 queries per wave; profiles/r04_attn_ablation.txt)
+    // and only where the halved workgroup count still fills the chip twice over (a B = 1 generation has 48 (row, head) pairs)
+    return CVAR_ATTN_Q64 && qpre && p.l >= CVAR_ATTN_Q64_MINL && cdiv(p.l, 256) * 256 - p.l < 64 && (long)cdiv(p.l, 256) * p.H * p.R >= 512;
+}
+
 // launch of the bf16 MFMA forward: picks QPRE and G (the v1 kernel has neither)
 template <bool HOLES>
 static void launch_attn_mfma(const AttnParams& p, bool qpre, bool v1, hipStream_t st) {
     const dim3 block(256);
     if (v1) { hipLaunchKernelGGL(attn_mfma_bf16_v1_kernel<HOLES>, dim3(cdiv(p.l, 128), p.H, p.R), block, 0, st, p); return; }
-    // prescaled queries, long scales: 64 queries per wave (K / V fragments, tiles and barriers shared by two query groups)
-    // (only where the last 256-query workgroup is nearly full: l = 512 runs 1.371 -> 1.285 ms per call at B = 128, l = 338 - 82 queries in its second workgroup -
-    //  0.685 -> 0.82 ms and stays on 32 queries per wave; profiles/r04_attn_ablation.txt)
-    // and only where the halved workgroup count still fills the chip twice over (a B = 1 generation has 48 (row, head) pairs)
-    const bool g2 = CVAR_ATTN_Q64 && qpre && p.l >= CVAR_ATTN_Q64_MINL && cdiv(p.l, 256) * 256 - p.l < 64 && (long)cdiv(p.l, 256) * p.H * p.R >= 512;
+    const bool g2 = attn_two_groups(p, qpre);
     const dim3 grid((unsigned)((long)cdiv(p.l, g2 ? 256 : 128) * p.H * p.R));
     if (g2) hipLaunchKernelGGL((attn_mfma_bf16_kernel<HOLES, true, 2>), grid, block, 0, st, p);
     else if (qpre) hipLaunchKernelGGL((attn_mfma_bf16_kernel<HOLES, true, 1>), grid, block, 0, st, p);
     else hipLaunchKernelGGL((attn_mfma_bf16_kernel<HOLES, false, 1>), grid, block, 0, st, p);
+}
+// launch of the e4m3-arena forward (prescaled queries only): the same G rule, the same grid
+template <bool HOLES>
+static void launch_attn_kv8(const AttnParamsKV8& p, hipStream_t st) {
+    const bool g2 = attn_two_groups(p, true);
+    const dim3 grid((unsigned)((long)cdiv(p.l, g2 ? 256 : 128) * p.H * p.R)), block(256);
+    if (g2) hipLaunchKernelGGL((attn_mfma_bf16_kernel<HOLES, true, 2, true>), grid, block, 0, st, p);
+    else hipLaunchKernelGGL((attn_mfma_bf16_kernel<HOLES, true, 1, true>), grid, block, 0, st, p);
 }
 
 static int cvar_attention_impl(const void* qkv, const void* q, int dtype, int R, int H, int Lmax, int q_off, int l, float scale,
@@ -478,9 +496,11 @@ __device__ __forceinline__ s16x4_t lds_tr16_b64(const char* lds_ptr) {
     return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)lds_ptr);
 }
 
-template <bool HOLES, bool QPRE, int G>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(G == 1 ? 3 : 2, G == 1 ? 3 : 2))) void attn_mfma_bf16_kernel(const AttnParams p) {
+template <bool HOLES, bool QPRE, int G, bool KV8>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(G == 1 ? 3 : 2, G == 1 ? 3 : 2))) void attn_mfma_bf16_kernel(const std::conditional_t<KV8, AttnParamsKV8, AttnParams> p) {
     static_assert(G == 1 || (G == 2 && QPRE), "two query groups per wave: prescaled queries only");
+    static_assert(!KV8 || QPRE, "e4m3 K/V arena: prescaled queries only");
+    typedef std::conditional_t<KV8, unsigned char, bf16_t> kv_t;       // one cached element
     constexpr int D = 64, KT = 64, QB = 128 * G;         // QB: queries per workgroup
     // one K and one V tile, two barriers per tile.  (Two buffers and one barrier per tile: 7 % SLOWER - profiles/r03_attn_ab3_lds_double_buffer_rejected.txt.)
     constexpr int TILE_B = KT * 128;
@@ -500,9 +520,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(G == 1 ? 3 
     const int h = pair % p.H;
     const long r = pair / p.H;
     const int C3 = p.ldkv;
-    const bf16_t* base = (const bf16_t*)p.qkv + r * (long)p.Lmax * C3;
-    const bf16_t* kbase = base + p.k_col + h * D;
-    const bf16_t* vbase = base + p.v_col + h * D;
+    const kv_t* base = (const kv_t*)p.qkv + r * (long)p.Lmax * C3;
+    const kv_t* kbase = base + p.k_col + h * D;
+    const kv_t* vbase = base + p.v_col + h * D;
 
     const int q0 = qb * QB + w * 32 * G;
     const bool active = q0 < p.l;                     // a wave without a single query of the scale only helps staging the tiles
@@ -519,20 +539,39 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(G == 1 ? 3 
     const int kv_end = kv_len_of(p, p.q_off + min(p.l, (qb + 1) * QB) - 1);
 
     // staging map (K and V alike): thread -> keys k_key and k_key + 32, 16-byte chunk k_chunk of the 128-byte head row
-    const int k_key = tid >> 3, k_chunk = tid & 7;
+    // KV8: a head row is 64 bytes - thread -> ONE key, 16-byte chunk k_chunk of it (the bf16 chunks 2 k_chunk and 2 k_chunk + 1), and the key's two scales
+    const int k_key = KV8 ? tid >> 2 : tid >> 3, k_chunk = KV8 ? tid & 3 : tid & 7;
     bf16x8_t kreg[2], vreg[2];
     // buffer loads: the resource covers rows [0, kv_end) of this (row, head)'s K (V) columns, a lane's offset inside a tile never changes
     // and the tile's base is a scalar - no vector address arithmetic, no predication (rows past kv_end come back as zeros)
-    const int row_bytes = C3 * 2;
-    const int rec = (kv_end - 1) * row_bytes + 128;
+    const int row_bytes = C3 * (int)sizeof(kv_t);
+    const int rec = (kv_end - 1) * row_bytes + D * (int)sizeof(kv_t);
     const __amdgpu_buffer_rsrc_t k_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)kbase, 0, rec, 0x00020000);
     const __amdgpu_buffer_rsrc_t v_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)vbase, 0, rec, 0x00020000);
     int ld_off[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) ld_off[i] = (k_key + 32 * i) * row_bytes + k_chunk * 16;
     typedef int v4i_t __attribute__((ext_vector_type(4)));
+    // KV8: the scale table [R][Lmax][2H] through two more resources over rows [0, kv_end) (a row past kv_end: zero bytes times a zero scale)
+    [[maybe_unused]] v4i_t k8, v8;
+    [[maybe_unused]] float k8s, v8s;
+    [[maybe_unused]] int sc_row = 0;
+    [[maybe_unused]] __amdgpu_buffer_rsrc_t ks_rsrc, vs_rsrc;
+    if constexpr (KV8) {
+        sc_row = 2 * p.H * 4;
+        const float* sbase = p.kv_scale + r * (long)p.Lmax * (2 * p.H) + h;
+        ks_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)sbase, 0, (kv_end - 1) * sc_row + 4, 0x00020000);
+        vs_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(sbase + p.H), 0, (kv_end - 1) * sc_row + 4, 0x00020000);
+    }
     auto load_tile = [&](int kt0) {
         const int so = kt0 * row_bytes;
+        if constexpr (KV8) {
+            k8 = (v4i_t)__builtin_amdgcn_raw_buffer_load_b128(k_rsrc, ld_off[0], so, 0);
+            v8 = (v4i_t)__builtin_amdgcn_raw_buffer_load_b128(v_rsrc, ld_off[0], so, 0);
+            k8s = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ks_rsrc, k_key * sc_row, kt0 * sc_row, 0));
+            v8s = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(vs_rsrc, k_key * sc_row, kt0 * sc_row, 0));
+            return;
+        }
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             kreg[i] = __builtin_bit_cast(bf16x8_t, (v4i_t)__builtin_amdgcn_raw_buffer_load_b128(k_rsrc, ld_off[i], so, 0));
@@ -540,6 +579,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(G == 1 ? 3 
         }
     };
     auto store_tile = [&]() {
+        if constexpr (KV8) {            // dequantise (exact) into the SAME layout: bf16 chunk c = 2 k_chunk + i of key k_key
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const int c = 2 * k_chunk + i;
+                *(bf16x8_t*)(Ks + k_key * 128 + ((c ^ ((k_key >> 1) & 7)) << 4)) = fp8x8_to_bf16(k8[2 * i], k8[2 * i + 1], k8s);
+                *(bf16x8_t*)(Vs + k_key * 128 + ((((c >> 1) ^ (k_key & 3)) << 5) | ((c & 1) << 4))) = fp8x8_to_bf16(v8[2 * i], v8[2 * i + 1], v8s);
+            }
+            return;
+        }
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int key = k_key + 32 * i;
@@ -723,6 +771,24 @@ extern "C" int cvar_attention(const void* qkv, const void* q, int dtype, int R, 
 extern "C" int cvar_attention_prescaled(const void* kv, const void* q, int dtype, int R, int H, int Lmax, int q_off, int l,
                                         const int* lvl_end_host, int n_lvl, const int* hole_host, void* out, float* lse, void* stream) {
     return cvar_attention_impl(kv, q, dtype, R, H, Lmax, q_off, l, 1.0f, lvl_end_host, n_lvl, hole_host, out, lse, stream, 4);
+}
+// include/cvar_kvcache.h: cvar_attention_prescaled over the e4m3 arena - its checks, its refusals, its launch rule
+extern "C" int cvar_attention_kv8(const void* kv8, const float* kv_scale, const void* q, int R, int H, int Lmax, int q_off, int l,
+                                  const int* lvl_end_host, int n_lvl, const int* hole_host, void* out, float* lse, void* stream) {
+    if (!kv8 || !kv_scale || !q || !out || R <= 0 || H <= 0 || l <= 0 || q_off < 0 || q_off + l > Lmax) return CVAR_EINVAL;
+    if (((uintptr_t)kv8 & 15) || ((uintptr_t)kv_scale & 3)) return CVAR_EINVAL;
+    AttnParamsKV8 p;
+    const int C = H * 64;
+    p.q = q; p.ldq = C; p.q_rows = l; p.q_pos0 = q_off; p.ldkv = 2 * C; p.k_col = 0; p.v_col = C;
+    p.qkv = kv8; p.kv_scale = kv_scale; p.out = out; p.R = R; p.H = H; p.Lmax = Lmax; p.q_off = q_off; p.l = l; p.scale = 1.0f; p.lse = lse;
+    { const int rc = fill_levels(p, lvl_end_host, n_lvl, hole_host); if (rc != CVAR_OK) return rc; }
+    for (int i = 0; i < p.n_lvl; ++i)                       // no first-tile maximum for such a level (see cvar_attention_impl)
+        if (p.hole_lo[i] <= 0 && p.hole_hi[i] >= 64) return CVAR_EUNSUPPORTED;
+    if ((long)cdiv(l, 128) * H * R > 0x7fffffffL) return CVAR_EUNSUPPORTED;        // 1-D grid
+    if (has_holes(p)) launch_attn_kv8<true>(p, as_stream(stream));
+    else launch_attn_kv8<false>(p, as_stream(stream));
+    CVAR_CHECK_LAUNCH();
+    return CVAR_OK;
 }
 extern "C" int cvar_attention_v1(const void* qkv, const void* q, int dtype, int R, int H, int Lmax, int q_off, int l, float scale,
                                  const int* lvl_end_host, int n_lvl, const int* hole_host, void* out, float* lse, void* stream) {

@@ -29,3 +29,23 @@ __device__ __forceinline__ unsigned fp8_pack4(float a, float b, float c, float d
     w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
     return (unsigned)w;
 }
+
+// The way back (kv_precision='fp8', include/cvar_kvcache.h): eight e4m3 bytes (w0 = elements 0..3, w1 = 4..7) times a power-of-two scale, as
+// eight bf16 values.  An e4m3 value has 3 mantissa bits and bf16 has 7, so value * 2^k IS a bf16 value: the fp32 product is exact and its upper
+// 16 bits are the result - no rounding anywhere (v_perm_b32 picks the two upper halves).  0x7F / 0xFF (NaN) stay NaN.
+__device__ __forceinline__ bf16x8_t fp8x8_to_bf16(int w0, int w1, float scale) {
+    const f32x2_t f[4] = {__builtin_amdgcn_cvt_pk_f32_fp8(w0, false), __builtin_amdgcn_cvt_pk_f32_fp8(w0, true),
+                          __builtin_amdgcn_cvt_pk_f32_fp8(w1, false), __builtin_amdgcn_cvt_pk_f32_fp8(w1, true)};
+    // The pair times (scale, scale) as ONE vector multiply.  Written as two scalar multiplies, the compiler paired the K and the V scale of a thread in one
+    // register pair and built each product pair from two v_pk_mul_f32 with crossed op_sel; the G = 2 attention instantiations then gave wrong upper halves
+    // (odd elements of V) on the MI355X, differently from run to run.  This form compiles to one broadcast v_pk_mul_f32 per pair.
+    const f32x2_t s2 = {scale, scale};
+    unsigned u[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const f32x2_t p = f[i] * s2;                    // one packed multiply per pair
+        u[i] = __builtin_amdgcn_perm(__float_as_uint(p[1]), __float_as_uint(p[0]), 0x07060302u);
+    }
+    const u32x4_t v = {u[0], u[1], u[2], u[3]};
+    return __builtin_bit_cast(bf16x8_t, v);
+}

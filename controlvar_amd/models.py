@@ -1024,10 +1024,13 @@ class _RowDraw(NamedTuple):
 
 
 GEMM_PRECISIONS = (None, 'bf16x3', 'fp8')
+KV_PRECISIONS = (None, 'fp8')
 _X3_NO_BANK = ("gemm_precision='bf16x3': the per-request adapter bank (attach_adapters / adapter=) is not offered - its K-augmented operands [W | B_0 ...] do not "
                "compose with the three K segments of the split product; merge one adapter with add_lora, or run the bank on gemm_precision=None")
 
 
+_KV8_NO_X3 = ("kv_precision='fp8' is not offered under gemm_precision='bf16x3': the split-bf16 mode exists for exactness (fp32 arena, exact row-wise attention) "
+              "and an e4m3 K/V cache would undo it; run it on a compute_dtype=torch.bfloat16 model with gemm_precision None or 'fp8'")
 _FP8_NO_BANK = ("gemm_precision='fp8': the per-request adapter bank (attach_adapters / adapter=) is not offered - its K-augmented bf16 operands [W | B_0 ...] have no "
                 "e4m3 form in this mode; merge one adapter with add_lora, or run the bank on gemm_precision=None")
 
@@ -1043,6 +1046,22 @@ def _split_weight_rows(w: torch.Tensor) -> torch.Tensor:
     hi = w.to(torch.bfloat16)
     lo = (w - hi.float()).to(torch.bfloat16)
     return torch.cat((hi, hi, lo), dim=-1).contiguous()
+
+
+def kv8_arena_shapes(depth: int, R: int, Lmax: int, H: int):
+    """kv_precision='fp8' (include/cvar_kvcache.h): shapes of the e4m3 byte arena [depth][R][Lmax][2C] and of its fp32 scale table [depth][R][Lmax][2H] -
+    2C + 8H = 136 H bytes per token and layer against the 256 H of the bf16 arena: 17/32"""
+    return (depth, R, Lmax, 2 * H * 64), (depth, R, Lmax, 2 * H)
+
+
+class KV8Arena(NamedTuple):
+    """the e4m3 K/V arena of one stream: q = the bytes (uint8), scale = one power-of-two fp32 per (layer, sequence, token, k or v head)"""
+    q: torch.Tensor
+    scale: torch.Tensor
+
+    @property
+    def nbytes(self) -> int:
+        return self.q.numel() + 4 * self.scale.numel()
 
 
 class _Pack(dict):
@@ -1081,7 +1100,8 @@ class ControlVAR(nn.Module):
                  drop_path_rate=0., layer_scale=-1., tau=4, cos_attn=False, patch_nums=DEFAULT_PATCH_NUMS,
                  flash_if_available=True, fused_if_available=True, mask_factor=2, bidirectional=False, separate_decoding=False,
                  separator=False, type_pos=False, indep=True, multi_cond=False,
-                 compute_dtype=None, init_seed: int = 0, deterministic_plan: bool = False, sampler: str = 'counter', gemm_precision: Optional[str] = None):
+                 compute_dtype=None, init_seed: int = 0, deterministic_plan: bool = False, sampler: str = 'counter', gemm_precision: Optional[str] = None,
+                 kv_precision: Optional[str] = None):
         """gemm_precision (an addition of this library; fp32 models only; also settable: ``model.gemm_precision = 'bf16x3'``): None = the linear layers run
         in compute_dtype; 'bf16x3' = the fp32 model with its six GEMM families (ada, qkv, proj, fc1, fc2, head) taken as split-bf16 products on the bf16
         matrix pipe - operands carried as hi + lo in bf16, three products per multiply as three K segments of one bf16 GEMM, fp32 accumulation and fp32
@@ -1090,6 +1110,12 @@ class ControlVAR(nn.Module):
         'fp8' (bf16 models only) = the bf16 model with the qkv, proj, fc1 and fc2 GEMMs of every block on OCP e4m3 operands with one power-of-two scale per
         row, fp32 accumulation and the bf16 mode's epilogues (include/cvar_serve.h); the head, the adaLN table, the residual stream, the K/V arena,
         attention, sampler, quantizer and VQVAE are the bf16 mode's, through the same kernels.  Inference only: forward() and training run the bf16 path.
+
+        kv_precision (an addition of this library; bf16 models with gemm_precision None or 'fp8'; also settable: ``model.kv_precision = 'fp8'``): None = the
+        K/V arena of generation holds compute_dtype values; 'fp8' = it holds OCP e4m3 bytes with one power-of-two fp32 scale per (token, k or v head) - 17/32
+        of the bf16 arena (include/cvar_kvcache.h).  The qkv GEMM then writes the k|v rows of a pass to a scratch, cvar_kv_append_fp8 quantises
+        them into the arena and the attention kernel dequantises (exactly) while it stages its tiles; everything else is the mode's own.  Generation only:
+        forward() and training keep the bf16 arena.
 
         deterministic_plan (an addition of this library): every transformer GEMM runs on the unsliced tile kernels whatever its row count - no small-M weight-streaming
         kernel, no K slices - so the fp32 summation order of a row does not depend on how many rows ride beside it, and one (label, condition, g_seed) in batch row 0 gives
@@ -1156,7 +1182,9 @@ class ControlVAR(nn.Module):
         self._packed = None
         self._arena = None
         self._gemm_precision = None
+        self._kv_precision = None
         self.gemm_precision = gemm_precision
+        self.kv_precision = kv_precision
         self.last_trace: Optional[dict] = None
 
     # ---- plumbing
@@ -1204,11 +1232,30 @@ class ControlVAR(nn.Module):
                              f"and this model computes in {self.compute_dtype} (build it with compute_dtype=torch.float32)")
         if value is not None and getattr(self, '_adapter_bank', None) is not None:
             raise NotImplementedError(_no_bank_message(value))
+        if value == 'bf16x3' and getattr(self, '_kv_precision', None) is not None:
+            raise ValueError(_KV8_NO_X3)
         if value != self._gemm_precision:       # the packed matrices and the arena key belong to the mode
             self._packed = None
             self._packed_base = None
             self._arena = None
         self._gemm_precision = value
+
+    @property
+    def kv_precision(self) -> Optional[str]:
+        return self._kv_precision
+
+    @kv_precision.setter
+    def kv_precision(self, value: Optional[str]):
+        if value not in KV_PRECISIONS:
+            raise ValueError(f'kv_precision must be one of {KV_PRECISIONS}, got {value!r}')
+        if value is not None and self._gemm_precision == 'bf16x3':
+            raise ValueError(_KV8_NO_X3)
+        if value is not None and self.compute_dtype != torch.bfloat16:
+            raise ValueError(f"kv_precision={value!r} needs a compute_dtype=torch.bfloat16 model: the e4m3 K/V cache trades precision for memory, and this model "
+                             f"computes in {self.compute_dtype}, a mode that exists for exactness (build it with compute_dtype=torch.bfloat16)")
+        if value != self._kv_precision:         # the arena belongs to the mode; the packed matrices do not
+            self._arena = None
+        self._kv_precision = value
 
     @property
     def rng(self) -> torch.Generator:
@@ -1441,17 +1488,23 @@ class ControlVAR(nn.Module):
         pos = [int(p) for p in py.special_positions()]
         xv[:, pos] = self._special_rows(table, pos, [mapping[i] for i in range(len(pos))])
 
-    def _get_arena(self, R: int, Lmax: int):
+    def _get_arena(self, R: int, Lmax: int, kv_precision: Optional[str] = None):
         """KV arena [depth][R][Lmax][2C] (k | v halves; the queries of a scale are dead after its attention and live in a per-call scratch,
         like the reference's cache of k and v only, basic_var.py:108-111) of the calling stream (generations running concurrently on
-        different streams must not share it)"""
+        different streams must not share it).  kv_precision='fp8' (generation passes the model's; forward() does not): a KV8Arena - the e4m3
+        bytes and their scale table (include/cvar_kvcache.h)"""
         sid = torch.cuda.current_stream(self.device).cuda_stream
-        key = (R, Lmax, self.compute_dtype, self.gemm_precision)
+        key = (R, Lmax, self.compute_dtype, self.gemm_precision, kv_precision)
         if self._arena is None:
             self._arena = {}
         ent = self._arena.get(sid)
         if ent is None or ent[0] != key:
-            ent = self._arena[sid] = (key, torch.empty(self.cfg.depth, R, Lmax, 2 * self.cfg.C, device=self.device, dtype=self.compute_dtype))
+            if kv_precision == 'fp8':
+                sq, ss = kv8_arena_shapes(self.cfg.depth, R, Lmax, self.cfg.H)
+                buf = KV8Arena(torch.empty(sq, device=self.device, dtype=torch.uint8), torch.empty(ss, device=self.device, dtype=torch.float32))
+            else:
+                buf = torch.empty(self.cfg.depth, R, Lmax, 2 * self.cfg.C, device=self.device, dtype=self.compute_dtype)
+            ent = self._arena[sid] = (key, buf)
         return ent[1]
 
     # ---- one pass of all blocks + head over l new tokens per sequence
@@ -1489,6 +1542,8 @@ class ControlVAR(nn.Module):
         hbuf = torch.empty(M, kh, device=dev, dtype=T)                # adapters: [gelu | u_fc2], fc1 writes it through ldc
         qs = torch.empty(M, C, device=dev, dtype=T)                 # queries of this pass: (R, l, C)
         arena_stride = R * Lmax * 2 * C
+        kv8 = isinstance(arena, KV8Arena)                           # kv_precision='fp8': k | v rows go to a scratch of the pass and from there, quantised, into the arena
+        kvs = torch.empty(M, 2 * C, device=dev, dtype=T) if kv8 else None
         # bf16 mode: the queries carry softmax scale * log2(e) from the producing epilogue (one rounding of q * c; the attention kernel then
         # spends no multiply per score - cvar_attention_prescaled).  fp32 parity mode: the exact row-wise kernel, unscaled queries.
         LOG2E = 1.4426950408889634
@@ -1504,11 +1559,17 @@ class ControlVAR(nn.Module):
         for i in range(cfg.depth):
             a0 = i * 6 * C
             # one GEMM for q | k | v: the q columns land in the scratch, k | v rows straight in their KV-arena slots (row remap)
-            ops.gemm(u, P['w_qkv'], arena, M=M, N=3 * C, K=C, w_off=i * 3 * C * C, bias=P['b_qkv'][i], c_off=i * arena_stride,
-                     ldc=2 * C, remap=(l, Lmax, q_off), split=(qs, C, C), split_alpha=q_alpha, small_m=sm, split_k=sm)
-            if cfg.uses_cos_attn:
-                ops.cos_qk_norm(arena, R, H, Lmax, q_off, l, P['scale_mul'], qkv_off=i * arena_stride, sm_off=i * H, q=qs, q_mul=LOG2E if pre else 1.0)
-            ops.attention(arena, o, R, H, Lmax, q_off, l, float(cfg.attn_scale), lvl_end, qkv_off=i * arena_stride, holes=holes, q=qs, prescaled=pre)
+            if kv8:
+                # (the q split of cvar_gemm rides on its row-remap epilogue: the scratch is addressed as an arena of its own, Lmax = l, q_off = 0 - the identity)
+                ops.gemm(u, P['w_qkv'], kvs, M=M, N=3 * C, K=C, w_off=i * 3 * C * C, bias=P['b_qkv'][i], ldc=2 * C, remap=(l, l, 0), split=(qs, C, C),
+                         split_alpha=q_alpha, small_m=sm, split_k=sm)
+                self._kv8_append_and_attend(i, arena, kvs, qs, o, R, l, q_off, Lmax, lvl_end, holes)
+            else:
+                ops.gemm(u, P['w_qkv'], arena, M=M, N=3 * C, K=C, w_off=i * 3 * C * C, bias=P['b_qkv'][i], c_off=i * arena_stride,
+                         ldc=2 * C, remap=(l, Lmax, q_off), split=(qs, C, C), split_alpha=q_alpha, small_m=sm, split_k=sm)
+                if cfg.uses_cos_attn:
+                    ops.cos_qk_norm(arena, R, H, Lmax, q_off, l, P['scale_mul'], qkv_off=i * arena_stride, sm_off=i * H, q=qs, q_mul=LOG2E if pre else 1.0)
+                ops.attention(arena, o, R, H, Lmax, q_off, l, float(cfg.attn_scale), lvl_end, qkv_off=i * arena_stride, holes=holes, q=qs, prescaled=pre)
             ln2 = (u, ada, a0 + 3 * C, a0 + 5 * C, n_ada, l, cfg.norm_eps)
             if ad is not None:
                 ops.lora_down_rows(o, BK['A']['proj'][i], BK['scale'], slot, oa, R=R, l=l, K=C, kpad=kx, ldxa=kc, x_copy=oa, ld_copy=kc)
@@ -1531,6 +1592,18 @@ class ControlVAR(nn.Module):
         logits = torch.empty(M, cfg.head_ld, device=dev, dtype=torch.float32)
         ops.gemm(u, P['w_head'], logits, M=M, N=cfg.head_ld, K=C, bias=P['b_head'], small_m=sm, split_k=sm)
         return logits
+
+    def _kv8_append_and_attend(self, i: int, arena: 'KV8Arena', kvs, qs, o, R: int, l: int, q_off: int, Lmax: int, lvl_end, holes):
+        """kv_precision='fp8', layer i, behind the qkv GEMM that wrote this pass's k | v rows to the scratch kvs [R*l][2C] and its prescaled queries to qs:
+        cos-norm on the scratch (a [R][l][2C] arena of its own: Lmax = l, q_off = 0), cvar_kv_append_fp8 into the arena rows (r, q_off + t), attention over the
+        e4m3 arena (include/cvar_kvcache.h)"""
+        cfg = self.cfg
+        H = cfg.H
+        a_off, s_off = i * R * Lmax * 2 * cfg.C, i * R * Lmax * 2 * H
+        if cfg.uses_cos_attn:
+            ops.cos_qk_norm(kvs, R, H, l, 0, l, self._pack()['scale_mul'], sm_off=i * H, q=qs, q_mul=1.4426950408889634)
+        ops.kv_append_fp8(kvs, arena.q, arena.scale, R, H, Lmax, q_off, l, kv8_off=a_off, scale_off=s_off)
+        ops.attention_kv8(arena.q, arena.scale, qs, o, R, H, Lmax, q_off, l, lvl_end, holes=holes, kv8_off=a_off, scale_off=s_off)
 
     def _blocks_and_head_x3(self, P, x, ada, R: int, l: int, q_off: int, Lmax: int, arena, lvl_end, holes):
         """_blocks_and_head of gemm_precision='bf16x3': the fp32 pass - fp32 residual stream, arena and query scratch, unscaled queries, the exact row-wise
@@ -1592,6 +1665,8 @@ class ControlVAR(nn.Module):
         qs = torch.empty(M, C, device=dev, dtype=bf)
         u = torch.empty(M, C, device=dev, dtype=bf)                  # the head's adaLN rows
         arena_stride = R * Lmax * 2 * C
+        kv8 = isinstance(arena, KV8Arena)                           # kv_precision='fp8': as in _blocks_and_head
+        kvs = torch.empty(M, 2 * C, device=dev, dtype=bf) if kv8 else None
         LOG2E = 1.4426950408889634
         q_alpha = 1.0 if cfg.uses_cos_attn else float(cfg.attn_scale) * LOG2E
         sm = not self.deterministic_plan
@@ -1599,11 +1674,16 @@ class ControlVAR(nn.Module):
         ops.ln_modulate_fp8(x, ada, 2 * C, 4 * C, n_ada, l, u8q, u8s, M, C, cfg.norm_eps, ldq=ldc8)
         for i in range(cfg.depth):
             a0 = i * 6 * C
-            ops.gemm_fp8(u8q, u8s, P['w_qkv_f8'], P['s_qkv'], arena, M=M, N=3 * C, K=ldc8, lda=ldc8, ldw=ldc8, w_off=i * 3 * C * ldc8, ws_off=i * 3 * C,
-                         bias=P['b_qkv'][i], c_off=i * arena_stride, ldc=2 * C, remap=(l, Lmax, q_off), split=(qs, C, C), split_alpha=q_alpha)
-            if cfg.uses_cos_attn:
-                ops.cos_qk_norm(arena, R, H, Lmax, q_off, l, P['scale_mul'], qkv_off=i * arena_stride, sm_off=i * H, q=qs, q_mul=LOG2E)
-            ops.attention(arena, o, R, H, Lmax, q_off, l, float(cfg.attn_scale), lvl_end, qkv_off=i * arena_stride, holes=holes, q=qs, prescaled=True)
+            if kv8:
+                ops.gemm_fp8(u8q, u8s, P['w_qkv_f8'], P['s_qkv'], kvs, M=M, N=3 * C, K=ldc8, lda=ldc8, ldw=ldc8, w_off=i * 3 * C * ldc8, ws_off=i * 3 * C,
+                             bias=P['b_qkv'][i], ldc=2 * C, remap=(l, l, 0), split=(qs, C, C), split_alpha=q_alpha)
+                self._kv8_append_and_attend(i, arena, kvs, qs, o, R, l, q_off, Lmax, lvl_end, holes)
+            else:
+                ops.gemm_fp8(u8q, u8s, P['w_qkv_f8'], P['s_qkv'], arena, M=M, N=3 * C, K=ldc8, lda=ldc8, ldw=ldc8, w_off=i * 3 * C * ldc8, ws_off=i * 3 * C,
+                             bias=P['b_qkv'][i], c_off=i * arena_stride, ldc=2 * C, remap=(l, Lmax, q_off), split=(qs, C, C), split_alpha=q_alpha)
+                if cfg.uses_cos_attn:
+                    ops.cos_qk_norm(arena, R, H, Lmax, q_off, l, P['scale_mul'], qkv_off=i * arena_stride, sm_off=i * H, q=qs, q_mul=LOG2E)
+                ops.attention(arena, o, R, H, Lmax, q_off, l, float(cfg.attn_scale), lvl_end, qkv_off=i * arena_stride, holes=holes, q=qs, prescaled=True)
             ops.quant_rows_fp8(o, o8q, o8s, M=M, K=C, ldq=ldc8)
             ops.gemm_fp8(o8q, o8s, P['w_proj_f8'], P['s_proj'], x, M=M, N=C, K=ldc8, lda=ldc8, ldw=ldc8, w_off=i * C * ldc8, ws_off=i * C,
                          bias=P['b_proj'][i], gate=ada, gate_off=a0, ldg=n_ada, gate_rows=l, residual=x)
@@ -1932,7 +2012,7 @@ class ControlVAR(nn.Module):
         self._first_tokens(P, labels_all, types_all, x, cond, R, py.first_l, P['lvl_pos'], mask_first)
         gen_table = P['lvl_pos'] if four_way else (P['lvl_pos_gen'] if mask_first else P['lvl_pos_gen_'])
         ada = self._ada(cond, R, ad)
-        arena = self._get_arena(R, py.L)
+        arena = self._get_arena(R, py.L, self.kv_precision)
         S = py.patch_nums[-1]
         f_hat = torch.zeros(nb, mf, cfg.cvae, S, S, device=dev, dtype=torch.float32)
         tr = {'idx': [], 'margin': [], 'logits': []} if trace else None
@@ -1998,7 +2078,7 @@ class ControlVAR(nn.Module):
         cond = torch.empty(R, C, device=dev, dtype=torch.float32)
         self._first_tokens(P, labels_all, types_all, xf, cond, R, 2, P['lvl_pos'], mask_first)
         ada = self._ada(cond, R)
-        arena = self._get_arena(R, py.L)
+        arena = self._get_arena(R, py.L, self.kv_precision)
         S = pns[-1]
         f = [torch.zeros(B, 1, cfg.cvae, S, S, device=dev, dtype=torch.float32) for _ in range(2)]
         x = torch.empty(R * S * S, C, device=dev, dtype=torch.float32)
@@ -2529,14 +2609,14 @@ class VAR(ControlVAR):
                  cond_drop_rate=0.1, depth=16, embed_dim=1024, num_heads=16, mlp_ratio=4., drop_rate=0., attn_drop_rate=0.,
                  drop_path_rate=0., layer_scale=-1., tau=4, cos_attn=False, patch_nums=DEFAULT_PATCH_NUMS,
                  flash_if_available=True, fused_if_available=True, compute_dtype=None, init_seed: int = 0, deterministic_plan: bool = False,
-                 sampler: str = 'counter', gemm_precision: Optional[str] = None):
+                 sampler: str = 'counter', gemm_precision: Optional[str] = None, kv_precision: Optional[str] = None):
         super().__init__(vae_local, num_classes=num_classes, norm_eps=norm_eps, aln=aln, aln_gamma_init=aln_gamma_init,
                          shared_aln=shared_aln, cond_drop_rate=cond_drop_rate, depth=depth, embed_dim=embed_dim, num_heads=num_heads,
                          mlp_ratio=mlp_ratio, drop_rate=drop_rate, attn_drop_rate=attn_drop_rate, drop_path_rate=drop_path_rate,
                          layer_scale=layer_scale, tau=tau, cos_attn=cos_attn, patch_nums=patch_nums,
                          flash_if_available=flash_if_available, fused_if_available=fused_if_available, mask_factor=1,
                          multi_cond=False, compute_dtype=compute_dtype, init_seed=init_seed, deterministic_plan=deterministic_plan,
-                         sampler=sampler, gemm_precision=gemm_precision)
+                         sampler=sampler, gemm_precision=gemm_precision, kv_precision=kv_precision)
 
     @torch.no_grad()
     def autoregressive_infer_cfg(self, B: int, label_B, g_seed: Optional[int] = None, cfg=1.5, top_k=0, top_p=0.0,

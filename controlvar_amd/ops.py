@@ -306,6 +306,37 @@ def attention(qkv: torch.Tensor, out: torch.Tensor, R: int, H: int, Lmax: int, q
     return out
 
 
+def _check_kv8(name: str, kv8: torch.Tensor, kv_scale: torch.Tensor, R: int, H: int, Lmax: int, kv8_off: int, scale_off: int):
+    if kv8.dtype != torch.uint8 or kv_scale.dtype != torch.float32 or not kv8.is_contiguous() or not kv_scale.is_contiguous():
+        raise ValueError(f'{name}: the arena is contiguous uint8 [.., R, Lmax, 2*H*64] with a contiguous float32 scale table [.., R, Lmax, 2*H]')
+    if kv8_off < 0 or scale_off < 0 or kv8.numel() - kv8_off < R * Lmax * 2 * H * 64 or kv_scale.numel() - scale_off < R * Lmax * 2 * H:
+        raise ValueError(f'{name}: the arena / scale table is smaller than R x Lmax x 2H head vectors behind the offset')
+
+
+def kv_append_fp8(kv: torch.Tensor, kv8: torch.Tensor, kv_scale: torch.Tensor, R: int, H: int, Lmax: int, q_off: int, l: int,
+                  kv8_off: int = 0, scale_off: int = 0):
+    """cvar_kv_append_fp8 (include/cvar_kvcache.h): the bf16 k|v rows [R*l][2*H*64] of one pass -> e4m3 bytes and power-of-two scales of the
+    arena rows (r, q_off + t) of one layer (kv8_off / scale_off: that layer's offset, in elements)."""
+    if kv.dtype != torch.bfloat16 or not kv.is_contiguous() or kv.numel() < R * l * 2 * H * 64:
+        raise ValueError('kv_append_fp8: kv must be contiguous bfloat16 with R*l rows of 2*H*64 elements')
+    _check_kv8('kv_append_fp8', kv8, kv_scale, R, H, Lmax, kv8_off, scale_off)
+    check(_lib.load().cvar_kv_append_fp8(_ptr(kv), _ptr(kv8) + kv8_off, _ptr(kv_scale) + 4 * scale_off, R, H, Lmax, q_off, l, _stream()),
+          'cvar_kv_append_fp8')
+
+
+def attention_kv8(kv8: torch.Tensor, kv_scale: torch.Tensor, q: torch.Tensor, out: torch.Tensor, R: int, H: int, Lmax: int, q_off: int, l: int,
+                  lvl_end: Optional[Sequence[int]] = None, holes: Optional[Sequence[Sequence[int]]] = None, lse: Optional[torch.Tensor] = None,
+                  kv8_off: int = 0, scale_off: int = 0):
+    """cvar_attention_kv8 (include/cvar_kvcache.h): attention(..., prescaled=True) over the e4m3 arena of one layer"""
+    n, arr, harr = _level_arrays(lvl_end, holes)
+    if q.dtype != torch.bfloat16 or out.dtype != torch.bfloat16 or q.numel() < R * l * H * 64 or out.numel() < R * l * H * 64:
+        raise ValueError('attention_kv8: q and out must hold R*l bfloat16 rows of H*64 elements')
+    _check_kv8('attention_kv8', kv8, kv_scale, R, H, Lmax, kv8_off, scale_off)
+    check(_lib.load().cvar_attention_kv8(_ptr(kv8) + kv8_off, _ptr(kv_scale) + 4 * scale_off, _ptr(q), R, H, Lmax, q_off, l, arr, n, harr,
+                                         _ptr(out), _ptr(lse), _stream()), 'cvar_attention_kv8')
+    return out
+
+
 def attention_bwd(qkv, o, dout, lse, dqkv, ws, R, H, Lmax, l, scale, lvl_end=None, qkv_off: int = 0, rowwise: bool = False, holes=None):
     n, arr, harr = _level_arrays(lvl_end, holes)
     fn = _lib.load().cvar_attention_bwd_rowwise if rowwise else _lib.load().cvar_attention_bwd

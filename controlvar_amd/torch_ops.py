@@ -371,6 +371,37 @@ _define('attention_kv_prescaled', '(Tensor kv, Tensor q, int H, int q_off, int[]
         lambda kv, q, H, q_off, lvl_end, holes=(): q.new_empty(q.shape[0] * q.shape[1], H * 64))
 
 
+def _kv_append_fp8_(kv, kv8, kv_scale, H, q_off):
+    """cvar_kv_append_fp8 (include/cvar_kvcache.h): kv (R, l, 2*H*64) bf16 k|v rows of one pass -> the rows [q_off, q_off + l) of one layer's e4m3
+    arena kv8 (R, Lmax, 2*H*64) uint8 and of its scale table kv_scale (R, Lmax, 2*H) float32, in place"""
+    if kv.dtype != torch.bfloat16 or kv.dim() != 3 or kv.shape[2] != 2 * H * 64 or not kv.is_contiguous():
+        raise ValueError(f'kv_append_fp8_: kv must be contiguous bfloat16 (R, l, 2*H*64); got {tuple(kv.shape)} {kv.dtype}')
+    if kv8.dim() != 3 or kv8.shape[0] != kv.shape[0] or kv8.shape[2] != 2 * H * 64 or tuple(kv_scale.shape) != (kv8.shape[0], kv8.shape[1], 2 * H):
+        raise ValueError(f'kv_append_fp8_: arena (R, Lmax, 2*H*64) uint8 and scales (R, Lmax, 2*H) float32; got {tuple(kv8.shape)}, {tuple(kv_scale.shape)}')
+    K.kv_append_fp8(kv, kv8, kv_scale, kv8.shape[0], H, kv8.shape[1], q_off, kv.shape[1])
+
+
+_define('kv_append_fp8_', '(Tensor kv, Tensor(a!) kv8, Tensor(b!) kv_scale, int H, int q_off) -> ()', _kv_append_fp8_, lambda kv, kv8, kv_scale, H, q_off: None)
+
+
+def _attention_kv8(kv8, kv_scale, q, H, q_off, lvl_end, holes=()):
+    """cvar_attention_kv8 (include/cvar_kvcache.h): attention_kv_prescaled over one layer's e4m3 arena (R, Lmax, 2*H*64) uint8 + scales (R, Lmax, 2*H)
+    float32 - bit for bit attention_kv_prescaled over the bf16 arena byte * scale"""
+    if kv8.dim() != 3 or kv8.shape[2] != 2 * H * 64 or tuple(kv_scale.shape) != (kv8.shape[0], kv8.shape[1], 2 * H):
+        raise ValueError(f'attention_kv8: arena (R, Lmax, 2*H*64) uint8 and scales (R, Lmax, 2*H) float32; got {tuple(kv8.shape)}, {tuple(kv_scale.shape)}')
+    R, Lmax, _ = kv8.shape
+    if q.dim() != 3 or q.shape[0] != R or q.shape[2] != H * 64 or not q.is_contiguous() or q.dtype != torch.bfloat16:
+        raise ValueError(f'attention_kv8: q must be contiguous bfloat16 (R, l, H*64); got {tuple(q.shape)} {q.dtype}')
+    l = q.shape[1]
+    out = torch.empty(R * l, H * 64, device=q.device, dtype=torch.bfloat16)
+    K.attention_kv8(kv8, kv_scale, q, out, R, H, Lmax, q_off, l, list(lvl_end) or None, holes=_holes(list(holes)))
+    return out
+
+
+_define('attention_kv8', '(Tensor kv8, Tensor kv_scale, Tensor q, int H, int q_off, int[] lvl_end, int[] holes=[]) -> Tensor', _attention_kv8,
+        lambda kv8, kv_scale, q, H, q_off, lvl_end, holes=(): q.new_empty(q.shape[0] * q.shape[1], H * 64))
+
+
 def _cos_qk_norm_(qkv, H, q_off, l, scale_mul):
     R, Lmax, _ = qkv.shape
     K.cos_qk_norm(qkv, R, H, Lmax, q_off, l, scale_mul.float().contiguous())
