@@ -210,24 +210,41 @@ class VQVAE(nn.Module):
     # tensor object (``_gn_part``): whoever consumes the tensor without a GroupNorm simply ignores them.  Class-level switch for A/B runs and tests.
     GN_FROM_CONV = True
 
+    # The encoder of a bf16 model in its higher precisions (encoder_precision 'fp32' / 'bf16x3') is the same layer walk over other conv and GroupNorm leaves: fp32 NHWC
+    # activations throughout; 'fp32' = the parity mode's exact-f32 MFMA, 'bf16x3' = every conv input split into [hi | lo | hi] bf16 rows (by the GroupNorm that feeds it,
+    # or by cvar_split3) and contracted with [w_hi | w_hi | w_lo] rows on the bf16 tiles.  The 16 x 16 attention blocks (0.1 % of the encoder's flops) then run q k^T and
+    # p v on the exact-f32 MFMA, as every fp32 tensor does.  _conv and _gn pick the leaf by the layer's name; everything outside 'encoder.' is native.
+    def _encoder_leaf(self, name: str) -> Optional[str]:
+        """'fp32' / 'bf16x3' when layer `name` runs in the encoder's own precision, None for the native leaf (compute dtype)"""
+        if name.startswith('encoder.') and self.compute_dtype == torch.bfloat16 and self.encoder_precision != 'bf16':
+            return self.encoder_precision
+        return None
+
     def _conv(self, x, name, B, Hin, Win, *, stride=1, up=0, residual=None, out_dtype=None):
-        c = self._pack()['conv'][name]
-        T = c['w'].dtype
+        leaf = self._encoder_leaf(name)
+        c = self._pack()['conv' if leaf is None else 'enc'][name]
+        T, cin = c['w'].dtype, c['cin']
+        if leaf == 'bf16x3':
+            cin = c['cin3']
+            if x.dtype != torch.bfloat16:           # not split by the GroupNorm in front (split rows are the only bf16 tensors of this stream)
+                xs = torch.empty(B * Hin * Win, cin, device=x.device, dtype=torch.bfloat16)
+                x = ops.split3(x, xs, B * Hin * Win, c['cin'], cin)
+        out_dtype = out_dtype or (T if leaf is None else torch.float32)
         if c['ks'] == 1:
             M = B * Hin * Win
-            out = torch.empty(M, c['cout'], device=x.device, dtype=out_dtype or T)
+            out = torch.empty(M, c['cout'], device=x.device, dtype=out_dtype)
             # never split along K: with the tile kernels alone a row's sum order does not depend on M, so an image decodes / encodes to the same bits in any batch
-            ops.gemm(x, c['w'], out, M=M, N=c['cout'], K=c['cin'], bias=c['b'], residual=residual, split_k=False)
+            ops.gemm(x, c['w'], out, M=M, N=c['cout'], K=cin, bias=c['b'], residual=residual, split_k=False)
             return out, Hin, Win
         Hout = Hin * 2 if up else (Hin // 2 if stride == 2 else Hin)
         Wout = Win * 2 if up else (Win // 2 if stride == 2 else Win)
         M = B * Hout * Wout
-        out = torch.empty(M, c['cout'], device=x.device, dtype=out_dtype or T)
-        geo = ops.conv_gn_partials(T, stride, c['cin'], c['cout'], Hin, Win, Hout, Wout) if (self.GN_FROM_CONV and out.dtype == T) else None
+        out = torch.empty(M, c['cout'], device=x.device, dtype=out_dtype)
+        geo = ops.conv_gn_partials(T, stride, cin, c['cout'], Hin, Win, Hout, Wout) if (leaf is None and self.GN_FROM_CONV and out.dtype == T) else None
         part = torch.empty(B, geo[0], c['cout'], 3, device=x.device, dtype=torch.float32) if geo else None
-        cv = dict(Hin=Hin, Win=Win, Cin=c['cin'], Hout=Hout, Wout=Wout, stride=stride, up=up)
+        cv = dict(Hin=Hin, Win=Win, Cin=cin, Hout=Hout, Wout=Wout, stride=stride, up=up)
         try:
-            ops.gemm(x, c['w'], out, M=M, N=c['cout'], K=9 * c['cin'], bias=c['b'], residual=residual, conv=cv, gn_part=part)
+            ops.gemm(x, c['w'], out, M=M, N=c['cout'], K=9 * cin, bias=c['b'], residual=residual, conv=cv, gn_part=part)
         except CvarError as e:
             # conv_gn_partials() decides by shape alone; the kernel that emits the partials also needs 16-byte aligned bias / output / residual and dense
             # strides (a state dict assigned from a flat buffer can hand over a 4-byte aligned bias).  Such a call is unsupported WITH partials, not
@@ -235,14 +252,23 @@ class VQVAE(nn.Module):
             if part is None or 'unsupported' not in str(e).lower():
                 raise
             geo, part = None, None
-            ops.gemm(x, c['w'], out, M=M, N=c['cout'], K=9 * c['cin'], bias=c['b'], residual=residual, conv=cv)
+            ops.gemm(x, c['w'], out, M=M, N=c['cout'], K=9 * cin, bias=c['b'], residual=residual, conv=cv)
         if geo:
             out._gn_part = (part, geo[0], geo[1])
         return out, Hout, Wout
 
+    def _hp_conv(self, x, name, B, Hin, Win, **kw):
+        """one encoder conv in the encoder's own precision: the name under which tests/test_gpu_encoder_precision.py calls that leaf of _conv"""
+        if self._encoder_leaf(name) is None:
+            raise ValueError(f'{name}: not a layer that runs in an encoder precision of its own')
+        return self._conv(x, name, B, Hin, Win, **kw)
+
     def _gn(self, x, name, B, HW, C, silu=True):
         w, b = self._pack()['norm'][name]
         ws = torch.empty(ops.groupnorm_ws_bytes(B, HW, C), device=x.device, dtype=torch.uint8)
+        if self._encoder_leaf(name) == 'bf16x3':        # GroupNorm(+SiLU) of the fp32 stream -> split rows, the next conv's operand
+            out = torch.empty(B * HW, 3 * C, device=x.device, dtype=torch.bfloat16)
+            return ops.groupnorm_silu_split3(x, w, b, out, B, HW, C, self.cfg.gn_groups, self.cfg.gn_eps, silu, ws)
         out = torch.empty_like(x)
         gp = getattr(x, '_gn_part', None)
         if gp is not None and gp[0].shape[0] == B and gp[0].shape[2] == C and gp[1] * gp[2] == HW:
@@ -284,17 +310,14 @@ class VQVAE(nn.Module):
     def _encode_f(self, img: torch.Tensor) -> torch.Tensor:
         """quant_conv(encoder(img)) -> f (B, Cvae, S, S) fp32, S = H / 16 (16 for 256 x 256 images, 32 for 512 x 512) (vqvae.py:74; vae_modules.py:144-160)."""
         P = self._pack()
-        if self.encoder_precision != ('bf16' if self.compute_dtype == torch.bfloat16 else 'fp32'):
-            return self._encode_f_hiprec(img)
         B, _, H, W = img.shape
-        T = self.compute_dtype
         cfg = self.cfg
-        cin_p = P['conv']['encoder.conv_in']['cin']
-        x = torch.empty(B * H * W, cin_p, device=img.device, dtype=T)
+        leaf = self._encoder_leaf('encoder.conv_in')
+        cin_p = P['conv' if leaf is None else 'enc']['encoder.conv_in']['cin']
+        x = torch.empty(B * H * W, cin_p, device=img.device, dtype=self.compute_dtype if leaf is None else torch.float32)
         ops.nchw_to_nhwc(img.contiguous().float(), x, B, 3, H * W, cin_p)
         h, H, W = self._conv(x, 'encoder.conv_in', B, H, W)
         nlev = len(cfg.ch_mult)
-        in_mult = (1,) + tuple(cfg.ch_mult)
         cur = cfg.ch
         for lv in range(nlev):
             cout = cfg.ch * cfg.ch_mult[lv]
@@ -310,96 +333,6 @@ class VQVAE(nn.Module):
         h = self._resblock(h, 'encoder.mid.block_2', B, H, W, cur, cur)
         h = self._gn(h, 'encoder.norm_out', B, H * W, cur)
         z, _, _ = self._conv(h, 'encoder.conv_out', B, H, W, out_dtype=torch.float32)      # (B*HW, Cvae) fp32 NHWC
-        f, _, _ = self._conv(z, 'quant_conv', B, H, W)                                      # fp32 weights
-        out = torch.empty(B, self.Cvae, H, W, device=img.device, dtype=torch.float32)
-        ops.nhwc_to_nchw(f, self.Cvae, out, B, self.Cvae, H * W)
-        return out
-
-    # ---- the encoder in its higher precisions (bf16 model, encoder_precision 'bf16x3' / 'fp32'): fp32 NHWC activations throughout; x3: every conv input is split into
-    # [hi | lo | hi] bf16 rows (by the GroupNorm that feeds it, or by cvar_split3) and contracted with [w_hi | w_hi | w_lo] rows on the bf16 tiles.  The 16 x 16 attention
-    # blocks (0.1 % of the encoder's flops) run q k^T and p v on the exact-f32 MFMA.  Same layer walk as _encode_f (vae_modules.py:144-160).
-    def _hp_conv(self, x, name, B, Hin, Win, *, stride=1, residual=None, pre_split=False):
-        c = self._pack()['enc'][name]
-        x3mode = self.encoder_precision == 'bf16x3'
-        ks = c['ks']
-        Hout, Wout = (Hin // 2, Win // 2) if stride == 2 else (Hin, Win)
-        M = B * Hout * Wout
-        if x3mode and not pre_split:
-            xs = torch.empty(B * Hin * Win, c['cin3'], device=x.device, dtype=torch.bfloat16)
-            ops.split3(x, xs, B * Hin * Win, c['cin'], c['cin3'])
-            x = xs
-        cin = c['cin3'] if x3mode else c['cin']
-        out = torch.empty(M, c['cout'], device=x.device, dtype=torch.float32)
-        if ks == 1:
-            ops.gemm(x, c['w'], out, M=M, N=c['cout'], K=cin, bias=c['b'], residual=residual, split_k=False)
-        else:
-            ops.gemm(x, c['w'], out, M=M, N=c['cout'], K=9 * cin, bias=c['b'], residual=residual,
-                     conv=dict(Hin=Hin, Win=Win, Cin=cin, Hout=Hout, Wout=Wout, stride=stride, up=0))
-        return out, Hout, Wout
-
-    def _hp_gn(self, x, name, B, HW, C, silu=True):
-        """GroupNorm(+SiLU) of the fp32 stream -> the next conv's input: split rows (x3) or fp32"""
-        w, b = self._pack()['norm'][name]
-        ws = torch.empty(ops.groupnorm_ws_bytes(B, HW, C), device=x.device, dtype=torch.uint8)
-        if self.encoder_precision == 'bf16x3':
-            out = torch.empty(B * HW, 3 * C, device=x.device, dtype=torch.bfloat16)
-            return ops.groupnorm_silu_split3(x, w, b, out, B, HW, C, self.cfg.gn_groups, self.cfg.gn_eps, silu, ws)
-        return ops.groupnorm_silu(x, w, b, torch.empty_like(x), B, HW, C, self.cfg.gn_groups, self.cfg.gn_eps, silu, ws)
-
-    def _hp_resblock(self, x, name, B, H, W, cin, cout):
-        h = self._hp_gn(x, name + '.norm1', B, H * W, cin)
-        h, _, _ = self._hp_conv(h, name + '.conv1', B, H, W, pre_split=True)
-        h = self._hp_gn(h, name + '.norm2', B, H * W, cout)
-        if cin != cout:
-            x, _, _ = self._hp_conv(x, name + '.nin_shortcut', B, H, W)
-        h, _, _ = self._hp_conv(h, name + '.conv2', B, H, W, residual=x, pre_split=True)
-        return h
-
-    def _hp_attnblock(self, x, name, B, HW, C):
-        F32 = torch.float32
-        n = self._hp_gn(x, name + '.norm', B, HW, C, silu=False)
-        qkv, _, _ = self._hp_conv(n, name + '.qkv', B, HW, 1, pre_split=True)             # (B*HW, 3C) fp32: q | k | v
-        HWp = -(-HW // 4) * 4
-        vT = torch.empty(B, C, HW, device=x.device, dtype=F32) if HWp == HW else torch.zeros(B, C, HWp, device=x.device, dtype=F32)
-        ops.transpose(qkv, vT, B, HW, C, 3 * C, in_off=2 * C, ld_out=HWp)
-        s = torch.empty(B, HW, HW, device=x.device, dtype=F32)
-        ops.gemm(qkv, qkv, s, M=HW, N=HW, K=C, lda=3 * C, ldw=3 * C, w_off=C, alpha=float(int(C) ** -0.5), batch=B,
-                 strideA=HW * 3 * C, strideW=HW * 3 * C, strideC=HW * HW)
-        p = torch.empty(B, HW, HW, device=x.device, dtype=F32)
-        ops.softmax_rows(s, p, B * HW, HW)
-        if HWp != HW:
-            pp = torch.zeros(B, HW, HWp, device=x.device, dtype=F32)
-            pp[:, :, :HW] = p
-            p = pp
-        o = torch.empty(B * HW, C, device=x.device, dtype=F32)
-        ops.gemm(p, vT, o, M=HW, N=C, K=HWp, batch=B, strideA=HW * HWp, strideW=C * HWp, strideC=HW * C)
-        y, _, _ = self._hp_conv(o, name + '.proj_out', B, HW, 1, residual=x)
-        return y
-
-    def _encode_f_hiprec(self, img: torch.Tensor) -> torch.Tensor:
-        P = self._pack()
-        B, _, H, W = img.shape
-        cfg = self.cfg
-        cin_p = P['enc']['encoder.conv_in']['cin']
-        x = torch.empty(B * H * W, cin_p, device=img.device, dtype=torch.float32)
-        ops.nchw_to_nhwc(img.contiguous().float(), x, B, 3, H * W, cin_p)
-        h, H, W = self._hp_conv(x, 'encoder.conv_in', B, H, W)
-        nlev = len(cfg.ch_mult)
-        cur = cfg.ch
-        for lv in range(nlev):
-            cout = cfg.ch * cfg.ch_mult[lv]
-            for b in range(cfg.num_res_blocks):
-                h = self._hp_resblock(h, f'encoder.down.{lv}.block.{b}', B, H, W, cur, cout)
-                cur = cout
-                if lv == nlev - 1:
-                    h = self._hp_attnblock(h, f'encoder.down.{lv}.attn.{b}', B, H * W, cur)
-            if lv != nlev - 1:
-                h, H, W = self._hp_conv(h, f'encoder.down.{lv}.downsample.conv', B, H, W, stride=2)
-        h = self._hp_resblock(h, 'encoder.mid.block_1', B, H, W, cur, cur)
-        h = self._hp_attnblock(h, 'encoder.mid.attn_1', B, H * W, cur)
-        h = self._hp_resblock(h, 'encoder.mid.block_2', B, H, W, cur, cur)
-        h = self._hp_gn(h, 'encoder.norm_out', B, H * W, cur)
-        z, _, _ = self._hp_conv(h, 'encoder.conv_out', B, H, W, pre_split=True)             # (B*HW, Cvae) fp32 NHWC
         f, _, _ = self._conv(z, 'quant_conv', B, H, W)                                      # fp32 weights
         out = torch.empty(B, self.Cvae, H, W, device=img.device, dtype=torch.float32)
         ops.nhwc_to_nchw(f, self.Cvae, out, B, self.Cvae, H * W)
@@ -1508,90 +1441,211 @@ class ControlVAR(nn.Module):
         return ent[1]
 
     # ---- one pass of all blocks + head over l new tokens per sequence
+    def _pass_mode(self, ad, x3: Optional[bool]) -> Optional[str]:
+        """the operand form of a pass's linear layers: None (compute dtype), 'bf16x3' or 'fp8'.  x3: None = the model's gemm_precision decides; False = the
+        compute-dtype form whatever the mode (forward(): the fp32 / bf16 matrices are then built on first use).  The adapter bank exists in the compute-dtype
+        form only: refused here, before anything is allocated or launched."""
+        mode = self.gemm_precision if x3 is None else ('bf16x3' if x3 else None)
+        if mode is not None and ad is not None:
+            raise NotImplementedError(_no_bank_message(mode))
+        return mode
+
     def _blocks_and_head(self, x, ada, R: int, l: int, q_off: int, Lmax: int, arena, lvl_end=None, holes=None, ad=None, x3: Optional[bool] = None):
-        """x: (R*l, C) fp32 residual stream (updated in place).  Returns logits (R*l, V) fp32.
-        ad (per-request adapters): (lora.bank_pack, slot (R,) int32 on the device).  proj / fc1 / fc2 then run over the K-augmented weights
-        [W | B_0 .. B_{n-1} | 0] with an operand that ops.lora_down_rows widened by each row's own s x A^T; without it the launches are
-        exactly the adapter-free ones.
-        x3: None = the model's gemm_precision decides; False = the compute-dtype path whatever the mode (forward(): the fp32 matrices are then built on first use)."""
+        """x: (R*l, C) fp32 residual stream (updated in place).  Returns logits (R*l, V) fp32.  x3: see _pass_mode.
+        ONE walk for every mode.  The walk owns the offsets into the ada row, the qkv launch (q | k | v in one GEMM: the q columns land in a scratch, the k | v rows
+        straight in their arena slots through the row remap), the arena / e4m3-arena branch with cos-norm and attention, the gate + residual epilogues of proj and
+        fc2, and the head.  A mode is three leaves over its own scratch, chosen once per pass:
+          norm(sc, sh, head)       writes the adaLN rows that qkv / fc1 / the head read and returns them as a GEMM operand
+          feed(name, i, a)         turns the attention output (proj), the adaLN rows (fc1, adapter bank only) or the GELU output (fc2) into that layer's operand;
+                                   called for the layers the mode names in `fed`, the others read `a` as it is
+          linear(layer, i, a, out) one of qkv / proj / fc1 / fc2 / head of block i, epilogue keywords passed through; `layer` is the mode's entry of `layers`
+                                   (weight, N, K as the call takes them), resolved before the loop
+        compute dtype: cvar_ln_modulate, cvar_gemm on w_*; below FUSE_LN_BELOW rows proj / fc2 also write the adaLN rows of the op that follows (ln=).  With ad
+            (per-request adapters: (lora.bank_pack, slot (R,) int32 on the device)) proj / fc1 / fc2 run over the K-augmented weights [W | B_0 .. B_{n-1} | 0] and
+            feed is ops.lora_down_rows: it widens the operand by each row's own s x A^T.  Without it the launches are exactly the adapter-free ones.
+        'bf16x3': every GEMM is ONE bf16 cvar_gemm over K' = 3 K, activation rows [hi | lo | hi] against weight rows [w_hi | w_hi | w_lo], fp32 output.  The adaLN rows
+            leave cvar_ln_modulate_split3 split; the attention and GELU outputs are fp32 round trips through cvar_split3 (the next lever).
+        'fp8': qkv / proj / fc1 / fc2 are cvar_gemm_fp8 on e4m3 operands (include/cvar_serve.h).  The adaLN rows leave cvar_ln_modulate_fp8 quantised; the attention and
+            GELU outputs are bf16 round trips through cvar_quant_rows_fp8.  The head is the bf16 mode's: cvar_ln_modulate and cvar_gemm.  No plan
+            slices K: deterministic_plan changes nothing in the four e4m3 GEMMs.
+        ln_out of the GEMM makes bf16 / fp32 rows only, so under 'bf16x3' and 'fp8' adaLN is its own launch at every M.  The arena, the query scratch and the attention
+        and GELU outputs hold compute_dtype in every mode ('bf16x3' is an fp32 model, 'fp8' a bf16 one)."""
+        mode = self._pass_mode(ad, x3)
         P, cfg = self._pack(), self.cfg
-        C, H, T = cfg.C, cfg.H, self.compute_dtype
-        M = R * l
-        hid = P['hid']
-        n_ada = P['n_ada']
-        dev = x.device
-        if (self.gemm_precision == 'bf16x3') if x3 is None else x3:
+        C, H, T, hid, n_ada, eps = cfg.C, cfg.H, self.compute_dtype, P['hid'], P['n_ada'], cfg.norm_eps
+        M, dev = R * l, x.device
+        bf = torch.bfloat16
+        buf = lambda cols, dtype: torch.empty(M, cols, device=dev, dtype=dtype)
+        sm = not self.deterministic_plan      # small-M plans (weight-streaming kernel, K slices): the summation order then depends on M; off = tile kernels only, unsliced
+        NK = dict(qkv=(3 * C, C), proj=(C, C), fc1=(hid, C), fc2=(C, hid), head=(cfg.head_ld, C))          # (N, K) of every linear layer
+        kx = 0 if ad is None else ad[0]['kx']                         # the bank's columns: proj / fc1 / fc2 operands and weights are wider by them
+        # Every mode allocates its scratch first: o = attention output, hbuf = GELU output, qs = queries of this pass (R, l, C), all in T; the rest are the mode's
+        # operands.  (The order of these allocations is part of the pass: the caching allocator reuses freed blocks by it, and torch.cuda.max_memory_allocated()
+        # counts whole blocks - the peak that tests/test_gpu_block_pass_launches.py holds a fresh process to follows from it.)
+        fc1_out, fuse_ln, fed = {}, False, ()           # fed: the layers whose operand feed() has to make
+        if mode is None:
+            u = buf(C, T)                                             # adaLN rows: operand of qkv / fc1 / head
+            o = buf(C, T)
+            wide = {}
             if ad is not None:
-                raise NotImplementedError(_X3_NO_BANK)
-            return self._blocks_and_head_x3(P, x, ada, R, l, q_off, Lmax, arena, lvl_end, holes)
-        if self.gemm_precision == 'fp8' and x3 is None:
+                wide['proj'] = buf(C + kx, T)                         # [o | u_proj of the row's slot, zeros elsewhere]
+                wide['fc1'] = buf(C + kx, T)                          # [adaLN output | u_fc1]
+            hbuf = buf(hid + kx, T)                                   # adapters: [gelu | u_fc2], fc1 writes it through ldc
+            qs = buf(C, T)
+            W = {n: P['w_' + n] for n in NK}
+            ld = dict(qkv=C, proj=C + kx, fc1=C + kx, fc2=hid + kx, head=C)          # K = lda = ldw of every call
+            fc1_out = dict(ldc=hid + kx)
+            # Small passes (early scales, small batches): proj / fc2 also produce the adaLN input of the op that follows (cvar_gemm_desc.ln_out) - their split-K
+            # reduction finishes rows, so LayerNorm + modulation ride in that launch instead of a cvar_ln_modulate of their own (same bits).  Large passes keep the
+            # separate launch: their GEMMs finish tiles, not rows.
+            fuse_ln = M < FUSE_LN_BELOW
+
+            def norm(sc, sh, head=False):
+                ops.ln_modulate(x, ada, sc, sh, n_ada, l, u, M, C, eps)
+                return u
+
+            def linear(layer, i, a, out, **epi):
+                w, N, K = layer
+                ops.gemm(a, w, out, M=M, N=N, K=K, w_off=i * N * K, small_m=sm, split_k=sm, **epi)
+
             if ad is not None:
-                raise NotImplementedError(_FP8_NO_BANK)
-            return self._blocks_and_head_fp8(P, x, ada, R, l, q_off, Lmax, arena, lvl_end, holes)
-        u = torch.empty(M, C, device=dev, dtype=T)
-        o = torch.empty(M, C, device=dev, dtype=T)
-        kx = 0 if ad is None else ad[0]['kx']
-        kc, kh = C + kx, hid + kx                                     # K = lda = ldw of proj / fc1 and of fc2: wider by the bank's columns
-        if ad is None:
-            oa, ua, w_proj, w_fc1, w_fc2 = o, u, P['w_proj'], P['w_fc1'], P['w_fc2']
+                BK, slot = ad
+                fed = ('proj', 'fc1', 'fc2')
+                W.update((n, BK['W'][n]) for n in ('proj', 'fc1', 'fc2'))
+
+                def feed(name, i, a):
+                    K, kw = NK[name][1], ld[name]
+                    if name == 'fc2':                                     # fc1 wrote the wide buffer itself: no copy
+                        ops.lora_down_rows(a, BK['A'][name][i], BK['scale'], slot, a, R=R, l=l, K=K, kpad=kx, ldx=kw, ldxa=kw)
+                        return a
+                    xa = wide[name]
+                    ops.lora_down_rows(a, BK['A'][name][i], BK['scale'], slot, xa, R=R, l=l, K=K, kpad=kx, ldxa=kw, x_copy=xa, ld_copy=kw)
+                    return xa
+            layers = {n: (W[n], NK[n][0], ld[n]) for n in NK}
+        elif mode == 'bf16x3':
+            u3 = buf(3 * C, bf)                                       # split adaLN rows: operand of qkv / fc1 / head
+            o = buf(C, T)
+            wide = dict(proj=buf(3 * C, bf))
+            hbuf = buf(hid, T)
+            wide['fc2'] = buf(3 * hid, bf)
+            qs = buf(C, T)
+
+            def norm(sc, sh, head=False):
+                ops.ln_modulate_split3(x, ada, sc, sh, n_ada, l, u3, M, C, eps)
+                return u3
+
+            fed = ('proj', 'fc2')
+            layers = {n: (P['w_' + n + '_x3'], NK[n][0], 3 * NK[n][1]) for n in NK}
+
+            def feed(name, i, a):
+                return ops.split3(a, wide[name], M, NK[name][1])
+
+            def linear(layer, i, a, out, **epi):
+                w, N, K = layer
+                ops.gemm(a, w, out, M=M, N=N, K=K, w_off=i * N * K, small_m=sm, split_k=sm, **epi)
         else:
-            BK, slot = ad
-            oa = torch.empty(M, kc, device=dev, dtype=T)              # [o | u_proj of the row's slot, zeros elsewhere]
-            ua = torch.empty(M, kc, device=dev, dtype=T)              # [adaLN output | u_fc1]
-            w_proj, w_fc1, w_fc2 = BK['W']['proj'], BK['W']['fc1'], BK['W']['fc2']
-        hbuf = torch.empty(M, kh, device=dev, dtype=T)                # adapters: [gelu | u_fc2], fc1 writes it through ldc
-        qs = torch.empty(M, C, device=dev, dtype=T)                 # queries of this pass: (R, l, C)
+            ldq = {C: ops.fp8_ldq(C), hid: ops.fp8_ldq(hid)}              # row bytes of an e4m3 operand of C / hid columns
+            rows8 = lambda K: (buf(ldq[K], torch.uint8), torch.empty(M, device=dev, dtype=torch.float32))          # e4m3 bytes + one scale per row
+            u8 = rows8(C)                                             # quantised adaLN rows: operand of qkv / fc1
+            o = buf(C, T)
+            wide = dict(proj=rows8(C))
+            hbuf = buf(hid, T)
+            wide['fc2'] = rows8(hid)
+            qs = buf(C, T)
+            ub = buf(C, T)                                            # the head's adaLN rows
+            fed = ('proj', 'fc2')
+            layers = {n: (P['w_' + n + '_f8'], P['s_' + n], NK[n][0], ldq[NK[n][1]]) for n in ('qkv', 'proj', 'fc1', 'fc2')}
+            layers['head'] = (P['w_head'], None, *NK['head'])                 # no e4m3 form: the bf16 GEMM
+
+            def norm(sc, sh, head=False):
+                if head:
+                    ops.ln_modulate(x, ada, sc, sh, n_ada, l, ub, M, C, eps)
+                    return ub
+                ops.ln_modulate_fp8(x, ada, sc, sh, n_ada, l, *u8, M, C, eps, ldq=ldq[C])
+                return u8
+
+            def feed(name, i, a):
+                K = NK[name][1]
+                ops.quant_rows_fp8(a, *wide[name], M=M, K=K, ldq=ldq[K])
+                return wide[name]
+
+            def linear(layer, i, a, out, ln=None, **epi):
+                assert ln is None                                     # cvar_gemm_fp8 has no ln_out: fuse_ln stays off in this mode
+                w, ws, N, K = layer
+                if ws is None:
+                    ops.gemm(a, w, out, M=M, N=N, K=K, small_m=sm, split_k=sm, **epi)
+                    return
+                ops.gemm_fp8(*a, w, ws, out, M=M, N=N, K=K, lda=K, ldw=K, w_off=i * N * K, ws_off=i * N, **epi)
+
         arena_stride = R * Lmax * 2 * C
         kv8 = isinstance(arena, KV8Arena)                           # kv_precision='fp8': k | v rows go to a scratch of the pass and from there, quantised, into the arena
-        kvs = torch.empty(M, 2 * C, device=dev, dtype=T) if kv8 else None
-        # bf16 mode: the queries carry softmax scale * log2(e) from the producing epilogue (one rounding of q * c; the attention kernel then
-        # spends no multiply per score - cvar_attention_prescaled).  fp32 parity mode: the exact row-wise kernel, unscaled queries.
+        kvs = buf(2 * C, T) if kv8 else None
+        # bf16 arena: the queries carry softmax scale * log2(e) from the producing epilogue (one rounding of q * c; the attention kernel then
+        # spends no multiply per score - cvar_attention_prescaled).  fp32 arena: the exact row-wise kernel, unscaled queries.
         LOG2E = 1.4426950408889634
-        pre = T == torch.bfloat16
+        pre = T == bf
         q_alpha = (float(cfg.attn_scale) * LOG2E) if (pre and not cfg.uses_cos_attn) else 1.0
-        # Small passes (early scales, small batches): proj / fc2 also produce the adaLN input of the op that follows (cvar_gemm_desc.ln_out) - their split-K
-        # reduction finishes rows, so LayerNorm + modulation ride in that launch instead of a cvar_ln_modulate of their own (same bits).  Large passes keep the
-        # separate launch: their GEMMs finish tiles, not rows.
-        sm = not self.deterministic_plan      # small-M plans (weight-streaming kernel, K slices): the summation order then depends on M; off = tile kernels only, unsliced
-        fuse_ln = M < FUSE_LN_BELOW   # calls up to here can be sliced along K (small-M split-K, the long-K rule of the 256x256 tiles); an unsliced call launches cvar_ln_modulate itself
+        qkv_epi = dict(ldc=2 * C, split=(qs, C, C), split_alpha=q_alpha)
         ah = cfg.depth * 6 * C
-        ops.ln_modulate(x, ada, 2 * C, 4 * C, n_ada, l, u, M, C, cfg.norm_eps)
+        qkv, proj, fc1, fc2 = layers['qkv'], layers['proj'], layers['fc1'], layers['fc2']
+        feed_proj, feed_fc1, feed_fc2 = 'proj' in fed, 'fc1' in fed, 'fc2' in fed
+        u = norm(2 * C, 4 * C)
         for i in range(cfg.depth):
             a0 = i * 6 * C
-            # one GEMM for q | k | v: the q columns land in the scratch, k | v rows straight in their KV-arena slots (row remap)
             if kv8:
                 # (the q split of cvar_gemm rides on its row-remap epilogue: the scratch is addressed as an arena of its own, Lmax = l, q_off = 0 - the identity)
-                ops.gemm(u, P['w_qkv'], kvs, M=M, N=3 * C, K=C, w_off=i * 3 * C * C, bias=P['b_qkv'][i], ldc=2 * C, remap=(l, l, 0), split=(qs, C, C),
-                         split_alpha=q_alpha, small_m=sm, split_k=sm)
+                linear(qkv, i, u, kvs, bias=P['b_qkv'][i], remap=(l, l, 0), **qkv_epi)
                 self._kv8_append_and_attend(i, arena, kvs, qs, o, R, l, q_off, Lmax, lvl_end, holes)
             else:
-                ops.gemm(u, P['w_qkv'], arena, M=M, N=3 * C, K=C, w_off=i * 3 * C * C, bias=P['b_qkv'][i], c_off=i * arena_stride,
-                         ldc=2 * C, remap=(l, Lmax, q_off), split=(qs, C, C), split_alpha=q_alpha, small_m=sm, split_k=sm)
+                linear(qkv, i, u, arena, bias=P['b_qkv'][i], c_off=i * arena_stride, remap=(l, Lmax, q_off), **qkv_epi)
                 if cfg.uses_cos_attn:
                     ops.cos_qk_norm(arena, R, H, Lmax, q_off, l, P['scale_mul'], qkv_off=i * arena_stride, sm_off=i * H, q=qs, q_mul=LOG2E if pre else 1.0)
                 ops.attention(arena, o, R, H, Lmax, q_off, l, float(cfg.attn_scale), lvl_end, qkv_off=i * arena_stride, holes=holes, q=qs, prescaled=pre)
-            ln2 = (u, ada, a0 + 3 * C, a0 + 5 * C, n_ada, l, cfg.norm_eps)
-            if ad is not None:
-                ops.lora_down_rows(o, BK['A']['proj'][i], BK['scale'], slot, oa, R=R, l=l, K=C, kpad=kx, ldxa=kc, x_copy=oa, ld_copy=kc)
-            ops.gemm(oa, w_proj, x, M=M, N=C, K=kc, w_off=i * C * kc, bias=P['b_proj'][i], gate=ada, gate_off=a0, ldg=n_ada, gate_rows=l,
-                     residual=x, ln=ln2 if fuse_ln else None, small_m=sm, split_k=sm)
+            sc, sh = a0 + 3 * C, a0 + 5 * C
+            linear(proj, i, feed('proj', i, o) if feed_proj else o, x, bias=P['b_proj'][i], gate=ada, gate_off=a0, ldg=n_ada, gate_rows=l, residual=x,
+                   ln=(u, ada, sc, sh, n_ada, l, eps) if fuse_ln else None)
             if not fuse_ln:
-                ops.ln_modulate(x, *ln2[1:6], u, M, C, cfg.norm_eps)
-            if ad is not None:
-                ops.lora_down_rows(u, BK['A']['fc1'][i], BK['scale'], slot, ua, R=R, l=l, K=C, kpad=kx, ldxa=kc, x_copy=ua, ld_copy=kc)
-            ops.gemm(ua, w_fc1, hbuf, M=M, N=hid, K=kc, ldc=kh, w_off=i * hid * kc, bias=P['b_fc1'][i], act=ACT_GELU_TANH, small_m=sm, split_k=sm)
-            if ad is not None:                             # fc1 wrote the wide buffer itself: no copy
-                ops.lora_down_rows(hbuf, BK['A']['fc2'][i], BK['scale'], slot, hbuf, R=R, l=l, K=hid, kpad=kx, ldx=kh, ldxa=kh)
+                u = norm(sc, sh)
+            linear(fc1, i, feed('fc1', i, u) if feed_fc1 else u, hbuf, bias=P['b_fc1'][i], act=ACT_GELU_TANH, **fc1_out)
             # the row finished by fc2 is the input of the next block's first adaLN (or of the head's)
-            a1 = a0 + 6 * C
-            ln1 = (u, ada, a1 + 2 * C, a1 + 4 * C, n_ada, l, cfg.norm_eps) if i + 1 < cfg.depth else (u, ada, ah, ah + C, n_ada, l, cfg.norm_eps)
-            ops.gemm(hbuf, w_fc2, x, M=M, N=C, K=kh, w_off=i * C * kh, bias=P['b_fc2'][i], gate=ada, gate_off=a0 + C, ldg=n_ada,
-                     gate_rows=l, residual=x, ln=ln1 if fuse_ln else None, small_m=sm, split_k=sm)
+            last = i + 1 == cfg.depth
+            sc, sh = (ah, ah + C) if last else (a0 + 8 * C, a0 + 10 * C)
+            linear(fc2, i, feed('fc2', i, hbuf) if feed_fc2 else hbuf, x, bias=P['b_fc2'][i], gate=ada, gate_off=a0 + C, ldg=n_ada, gate_rows=l, residual=x,
+                   ln=(u, ada, sc, sh, n_ada, l, eps) if fuse_ln else None)
             if not fuse_ln:
-                ops.ln_modulate(x, *ln1[1:6], u, M, C, cfg.norm_eps)
+                u = norm(sc, sh, head=last)
         logits = torch.empty(M, cfg.head_ld, device=dev, dtype=torch.float32)
-        ops.gemm(u, P['w_head'], logits, M=M, N=cfg.head_ld, K=C, bias=P['b_head'], small_m=sm, split_k=sm)
+        linear(layers['head'], 0, u, logits, bias=P['b_head'])
         return logits
+
+    def _ada(self, cond: torch.Tensor, R: int, ad=None, x3: Optional[bool] = None):
+        """the ada rows (R, n_ada) fp32 of every block and the head from one GEMM on SiLU(cond); the operand form follows _pass_mode ('fp8' keeps the bf16 one)"""
+        x3 = self._pass_mode(ad, x3) == 'bf16x3'
+        P, C, dev = self._pack(), self.cfg.C, cond.device
+        cs = torch.empty(R, C, device=dev, dtype=self.compute_dtype)
+        ops.silu_cast(cond, cs)
+        if x3:
+            cs3 = torch.empty(R, 3 * C, device=dev, dtype=torch.bfloat16)
+            ops.split3(cs, cs3, R, C)
+        ada = torch.empty(R, P['n_ada'], device=dev, dtype=torch.float32)
+        sm = not self.deterministic_plan
+        out = dict(M=R, N=P['n_ada'], bias=P['b_ada'], small_m=sm, split_k=sm)
+        if x3:
+            ops.gemm(cs3, P['w_ada_x3'], ada, K=3 * C, **out)
+        elif ad is None:
+            ops.gemm(cs, P['w_ada'], ada, K=C, **out)
+        else:
+            # per-request adapters: the operand [cs | one 16-column group per (ada target, slot)] is widened once per generation - one skinny
+            # launch per target, each owning its 16 n columns (the last one also the padding) - against [W_ada | blockdiag]
+            BK, slot = ad
+            n, nt = BK['n'], self.cfg.depth + 1
+            ld = C + BK['kxa']
+            csa = torch.empty(R, ld, device=dev, dtype=self.compute_dtype)
+            for t in range(nt):
+                ops.lora_down_rows(cs, BK['A']['ada'][t], BK['scale'], slot, csa, R=R, l=1, K=C, kpad=16 * n if t + 1 < nt else BK['kxa'] - 16 * n * t,
+                                   ldxa=ld, xa_off=16 * n * t, x_copy=csa if t == 0 else None, ld_copy=ld)
+            ops.gemm(csa, BK['W']['ada'], ada, K=ld, lda=ld, ldw=ld, **out)
+        return ada
 
     def _kv8_append_and_attend(self, i: int, arena: 'KV8Arena', kvs, qs, o, R: int, l: int, q_off: int, Lmax: int, lvl_end, holes):
         """kv_precision='fp8', layer i, behind the qkv GEMM that wrote this pass's k | v rows to the scratch kvs [R*l][2C] and its prescaled queries to qs:
@@ -1604,135 +1658,6 @@ class ControlVAR(nn.Module):
             ops.cos_qk_norm(kvs, R, H, l, 0, l, self._pack()['scale_mul'], sm_off=i * H, q=qs, q_mul=1.4426950408889634)
         ops.kv_append_fp8(kvs, arena.q, arena.scale, R, H, Lmax, q_off, l, kv8_off=a_off, scale_off=s_off)
         ops.attention_kv8(arena.q, arena.scale, qs, o, R, H, Lmax, q_off, l, lvl_end, holes=holes, kv8_off=a_off, scale_off=s_off)
-
-    def _blocks_and_head_x3(self, P, x, ada, R: int, l: int, q_off: int, Lmax: int, arena, lvl_end, holes):
-        """_blocks_and_head of gemm_precision='bf16x3': the fp32 pass - fp32 residual stream, arena and query scratch, unscaled queries, the exact row-wise
-        attention - with every GEMM as ONE bf16 cvar_gemm over K' = 3 K: activation rows [hi | lo | hi] against weight rows [w_hi | w_hi | w_lo], fp32 output
-        with the fp32 mode's epilogue.  The adaLN rows leave cvar_ln_modulate_split3 split (no fp32 row); the attention output and the GELU output are fp32
-        round trips through cvar_split3 (the next lever).  ln_out of the GEMM makes bf16 / fp32 rows only, so adaLN is its own launch at every M."""
-        cfg = self.cfg
-        C, H, hid, n_ada = cfg.C, cfg.H, P['hid'], P['n_ada']
-        M, dev = R * l, x.device
-        bf, f32 = torch.bfloat16, torch.float32
-        u3 = torch.empty(M, 3 * C, device=dev, dtype=bf)            # split adaLN rows: operand of qkv / fc1 / head
-        o = torch.empty(M, C, device=dev, dtype=f32)
-        o3 = torch.empty(M, 3 * C, device=dev, dtype=bf)
-        hbuf = torch.empty(M, hid, device=dev, dtype=f32)
-        h3 = torch.empty(M, 3 * hid, device=dev, dtype=bf)
-        qs = torch.empty(M, C, device=dev, dtype=f32)
-        arena_stride = R * Lmax * 2 * C
-        sm = not self.deterministic_plan
-        ah = cfg.depth * 6 * C
-        ops.ln_modulate_split3(x, ada, 2 * C, 4 * C, n_ada, l, u3, M, C, cfg.norm_eps)
-        for i in range(cfg.depth):
-            a0 = i * 6 * C
-            ops.gemm(u3, P['w_qkv_x3'], arena, M=M, N=3 * C, K=3 * C, w_off=i * 3 * C * 3 * C, bias=P['b_qkv'][i], c_off=i * arena_stride,
-                     ldc=2 * C, remap=(l, Lmax, q_off), split=(qs, C, C), small_m=sm, split_k=sm)
-            if cfg.uses_cos_attn:
-                ops.cos_qk_norm(arena, R, H, Lmax, q_off, l, P['scale_mul'], qkv_off=i * arena_stride, sm_off=i * H, q=qs, q_mul=1.0)
-            ops.attention(arena, o, R, H, Lmax, q_off, l, float(cfg.attn_scale), lvl_end, qkv_off=i * arena_stride, holes=holes, q=qs, prescaled=False)
-            ops.split3(o, o3, M, C)
-            ops.gemm(o3, P['w_proj_x3'], x, M=M, N=C, K=3 * C, w_off=i * C * 3 * C, bias=P['b_proj'][i], gate=ada, gate_off=a0, ldg=n_ada, gate_rows=l,
-                     residual=x, small_m=sm, split_k=sm)
-            ops.ln_modulate_split3(x, ada, a0 + 3 * C, a0 + 5 * C, n_ada, l, u3, M, C, cfg.norm_eps)
-            ops.gemm(u3, P['w_fc1_x3'], hbuf, M=M, N=hid, K=3 * C, w_off=i * hid * 3 * C, bias=P['b_fc1'][i], act=ACT_GELU_TANH, small_m=sm, split_k=sm)
-            ops.split3(hbuf, h3, M, hid)
-            ops.gemm(h3, P['w_fc2_x3'], x, M=M, N=C, K=3 * hid, w_off=i * C * 3 * hid, bias=P['b_fc2'][i], gate=ada, gate_off=a0 + C, ldg=n_ada,
-                     gate_rows=l, residual=x, small_m=sm, split_k=sm)
-            a1 = a0 + 6 * C
-            sc, sh = (a1 + 2 * C, a1 + 4 * C) if i + 1 < cfg.depth else (ah, ah + C)
-            ops.ln_modulate_split3(x, ada, sc, sh, n_ada, l, u3, M, C, cfg.norm_eps)
-        logits = torch.empty(M, cfg.head_ld, device=dev, dtype=f32)
-        ops.gemm(u3, P['w_head_x3'], logits, M=M, N=cfg.head_ld, K=3 * C, bias=P['b_head'], small_m=sm, split_k=sm)
-        return logits
-
-    def _blocks_and_head_fp8(self, P, x, ada, R: int, l: int, q_off: int, Lmax: int, arena, lvl_end, holes):
-        """_blocks_and_head of gemm_precision='fp8': the bf16 pass - fp32 residual stream, bf16 arena / query scratch / attention output / GELU output, prescaled
-        queries, the MFMA attention, the bf16 head - with qkv, proj, fc1 and fc2 as cvar_gemm_fp8 on e4m3 operands (include/cvar_serve.h).  The adaLN rows leave
-        cvar_ln_modulate_fp8 quantised (no bf16 row); the attention output and the GELU output are bf16 round trips through cvar_quant_rows_fp8 (the
-        next lever).  ln_out of the GEMM makes bf16 / fp32 rows only, so adaLN is its own launch at every M; the last one (the head's) is the bf16 cvar_ln_modulate.
-        No plan slices K: deterministic_plan changes nothing in the four e4m3 GEMMs."""
-        cfg = self.cfg
-        C, H, hid, n_ada = cfg.C, cfg.H, P['hid'], P['n_ada']
-        M, dev = R * l, x.device
-        bf, f32, u8 = torch.bfloat16, torch.float32, torch.uint8
-        ldc8, ldh8 = ops.fp8_ldq(C), ops.fp8_ldq(hid)
-        u8q, u8s = torch.empty(M, ldc8, device=dev, dtype=u8), torch.empty(M, device=dev, dtype=f32)      # quantised adaLN rows: operand of qkv / fc1
-        o = torch.empty(M, C, device=dev, dtype=bf)
-        o8q, o8s = torch.empty(M, ldc8, device=dev, dtype=u8), torch.empty(M, device=dev, dtype=f32)
-        hbuf = torch.empty(M, hid, device=dev, dtype=bf)
-        h8q, h8s = torch.empty(M, ldh8, device=dev, dtype=u8), torch.empty(M, device=dev, dtype=f32)
-        qs = torch.empty(M, C, device=dev, dtype=bf)
-        u = torch.empty(M, C, device=dev, dtype=bf)                  # the head's adaLN rows
-        arena_stride = R * Lmax * 2 * C
-        kv8 = isinstance(arena, KV8Arena)                           # kv_precision='fp8': as in _blocks_and_head
-        kvs = torch.empty(M, 2 * C, device=dev, dtype=bf) if kv8 else None
-        LOG2E = 1.4426950408889634
-        q_alpha = 1.0 if cfg.uses_cos_attn else float(cfg.attn_scale) * LOG2E
-        sm = not self.deterministic_plan
-        ah = cfg.depth * 6 * C
-        ops.ln_modulate_fp8(x, ada, 2 * C, 4 * C, n_ada, l, u8q, u8s, M, C, cfg.norm_eps, ldq=ldc8)
-        for i in range(cfg.depth):
-            a0 = i * 6 * C
-            if kv8:
-                ops.gemm_fp8(u8q, u8s, P['w_qkv_f8'], P['s_qkv'], kvs, M=M, N=3 * C, K=ldc8, lda=ldc8, ldw=ldc8, w_off=i * 3 * C * ldc8, ws_off=i * 3 * C,
-                             bias=P['b_qkv'][i], ldc=2 * C, remap=(l, l, 0), split=(qs, C, C), split_alpha=q_alpha)
-                self._kv8_append_and_attend(i, arena, kvs, qs, o, R, l, q_off, Lmax, lvl_end, holes)
-            else:
-                ops.gemm_fp8(u8q, u8s, P['w_qkv_f8'], P['s_qkv'], arena, M=M, N=3 * C, K=ldc8, lda=ldc8, ldw=ldc8, w_off=i * 3 * C * ldc8, ws_off=i * 3 * C,
-                             bias=P['b_qkv'][i], c_off=i * arena_stride, ldc=2 * C, remap=(l, Lmax, q_off), split=(qs, C, C), split_alpha=q_alpha)
-                if cfg.uses_cos_attn:
-                    ops.cos_qk_norm(arena, R, H, Lmax, q_off, l, P['scale_mul'], qkv_off=i * arena_stride, sm_off=i * H, q=qs, q_mul=LOG2E)
-                ops.attention(arena, o, R, H, Lmax, q_off, l, float(cfg.attn_scale), lvl_end, qkv_off=i * arena_stride, holes=holes, q=qs, prescaled=True)
-            ops.quant_rows_fp8(o, o8q, o8s, M=M, K=C, ldq=ldc8)
-            ops.gemm_fp8(o8q, o8s, P['w_proj_f8'], P['s_proj'], x, M=M, N=C, K=ldc8, lda=ldc8, ldw=ldc8, w_off=i * C * ldc8, ws_off=i * C,
-                         bias=P['b_proj'][i], gate=ada, gate_off=a0, ldg=n_ada, gate_rows=l, residual=x)
-            ops.ln_modulate_fp8(x, ada, a0 + 3 * C, a0 + 5 * C, n_ada, l, u8q, u8s, M, C, cfg.norm_eps, ldq=ldc8)
-            ops.gemm_fp8(u8q, u8s, P['w_fc1_f8'], P['s_fc1'], hbuf, M=M, N=hid, K=ldc8, lda=ldc8, ldw=ldc8, w_off=i * hid * ldc8, ws_off=i * hid,
-                         bias=P['b_fc1'][i], act=ACT_GELU_TANH)
-            ops.quant_rows_fp8(hbuf, h8q, h8s, M=M, K=hid, ldq=ldh8)
-            ops.gemm_fp8(h8q, h8s, P['w_fc2_f8'], P['s_fc2'], x, M=M, N=C, K=ldh8, lda=ldh8, ldw=ldh8, w_off=i * C * ldh8, ws_off=i * C,
-                         bias=P['b_fc2'][i], gate=ada, gate_off=a0 + C, ldg=n_ada, gate_rows=l, residual=x)
-            if i + 1 < cfg.depth:
-                a1 = a0 + 6 * C
-                ops.ln_modulate_fp8(x, ada, a1 + 2 * C, a1 + 4 * C, n_ada, l, u8q, u8s, M, C, cfg.norm_eps, ldq=ldc8)
-        ops.ln_modulate(x, ada, ah, ah + C, n_ada, l, u, M, C, cfg.norm_eps)
-        logits = torch.empty(M, cfg.head_ld, device=dev, dtype=f32)
-        ops.gemm(u, P['w_head'], logits, M=M, N=cfg.head_ld, K=C, bias=P['b_head'], small_m=sm, split_k=sm)
-        return logits
-
-    def _ada(self, cond: torch.Tensor, R: int, ad=None, x3: Optional[bool] = None):
-        P = self._pack()
-        if (self.gemm_precision == 'bf16x3') if x3 is None else x3:
-            if ad is not None:
-                raise NotImplementedError(_X3_NO_BANK)
-            C = self.cfg.C
-            cs = torch.empty(R, C, device=cond.device, dtype=torch.float32)
-            ops.silu_cast(cond, cs)
-            cs3 = torch.empty(R, 3 * C, device=cond.device, dtype=torch.bfloat16)
-            ops.split3(cs, cs3, R, C)
-            ada = torch.empty(R, P['n_ada'], device=cond.device, dtype=torch.float32)
-            sm = not self.deterministic_plan
-            ops.gemm(cs3, P['w_ada_x3'], ada, M=R, N=P['n_ada'], K=3 * C, bias=P['b_ada'], small_m=sm, split_k=sm)
-            return ada
-        cs = torch.empty(R, self.cfg.C, device=cond.device, dtype=self.compute_dtype)
-        ops.silu_cast(cond, cs)
-        ada = torch.empty(R, P['n_ada'], device=cond.device, dtype=torch.float32)
-        sm = not self.deterministic_plan
-        if ad is not None:
-            # per-request adapters: the operand [cs | one 16-column group per (ada target, slot)] is widened once per generation - one skinny
-            # launch per target, each owning its 16 n columns (the last one also the padding) - against [W_ada | blockdiag]
-            BK, slot = ad
-            C, n, nt = self.cfg.C, BK['n'], self.cfg.depth + 1
-            ld = C + BK['kxa']
-            csa = torch.empty(R, ld, device=cond.device, dtype=self.compute_dtype)
-            for t in range(nt):
-                ops.lora_down_rows(cs, BK['A']['ada'][t], BK['scale'], slot, csa, R=R, l=1, K=C, kpad=16 * n if t + 1 < nt else BK['kxa'] - 16 * n * t,
-                                   ldxa=ld, xa_off=16 * n * t, x_copy=csa if t == 0 else None, ld_copy=ld)
-            ops.gemm(csa, BK['W']['ada'], ada, M=R, N=P['n_ada'], K=ld, lda=ld, ldw=ld, bias=P['b_ada'], small_m=sm, split_k=sm)
-            return ada
-        ops.gemm(cs, P['w_ada'], ada, M=R, N=P['n_ada'], K=self.cfg.C, bias=P['b_ada'], small_m=sm, split_k=sm)
-        return ada
 
     def _as_labels(self, B, label_B, seed):
         dev = self.device
