@@ -1,4 +1,4 @@
-"""ctypes binding of libcvar_hip.so (include/cvar.h, include/cvar_serve.h, include/cvar_accum.h, include/cvar_kvcache.h).  No torch types cross this boundary:
+"""ctypes binding of libcvar_hip.so (include/cvar.h, include/cvar_serve.h, include/cvar_accum.h, include/cvar_kvcache.h, include/cvar_wide.h).  No torch types cross this boundary:
 callers hand over raw device pointers (``tensor.data_ptr()``), sizes and the HIP stream handle.
 
 The library is mandatory on the product path: if it is missing or does not load, every op
@@ -148,6 +148,15 @@ KVCACHE_SIGNATURES = {
     'cvar_attention_kv8': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, C.POINTER(c_i), c_i, C.POINTER(c_i), c_p, c_p, c_p]),
 }
 
+# include/cvar_wide.h: the adaLN row kernels for rows wider than 2048 channels - each its namesake's arguments, C <= WIDE_CMAX.  A table of its own for
+# the same reason; no signature of the other four headers changed, so neither version moved
+WIDE_CMAX = 3072            # CVAR_WIDE_CMAX
+WIDE_SIGNATURES = {
+    'cvar_ln_modulate_wide': (c_i, [c_p, c_p, c_p, c_l, c_i, c_p, c_i, c_i, c_i, c_f, c_p]),
+    'cvar_ln_modulate_split3_wide': (c_i, [c_p, c_p, c_p, c_l, c_i, c_p, c_i, c_i, c_f, c_p]),
+    'cvar_ln_modulate_fp8_wide': (c_i, [c_p, c_p, c_p, c_l, c_i, c_p, c_l, c_p, c_i, c_i, c_f, c_p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -170,7 +179,8 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         except Exception:  # pragma: no cover
             pass
         lib = C.CDLL(path, mode=C.RTLD_GLOBAL)
-        for name, (res, args) in (*SIGNATURES.items(), *SERVE_SIGNATURES.items(), *ACCUM_SIGNATURES.items(), *KVCACHE_SIGNATURES.items()):
+        for name, (res, args) in (*SIGNATURES.items(), *SERVE_SIGNATURES.items(), *ACCUM_SIGNATURES.items(), *KVCACHE_SIGNATURES.items(),
+                                  *WIDE_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -1,6 +1,7 @@
 // Row-wise / element-wise kernels of the transformer path (HBM-bound; 16-byte vector accesses).
 #include "cvar_common.h"
 #include "fp8_quant.h"
+#include "../../include/cvar_wide.h"
 
 // ------------------------------------------------------------------------------------------------
 // adaLN: out = LN(x) * (1 + scale) + shift.   One wave per row, values kept in registers.
@@ -146,6 +147,51 @@ extern "C" int cvar_ln_modulate_fp8(const float* x, const float* scale, const fl
     if (C % 4 || C > 2048 || ld_ada % 4 || ldq % 128 || ldq < C ||
         (((uintptr_t)x | (uintptr_t)scale | (uintptr_t)shift | (uintptr_t)q) & 15)) return CVAR_EUNSUPPORTED;
     return ln_dispatch<fp8q_t>(x, scale, shift, (long)ld_ada, rows_per, (fp8q_t*)q, M, C, eps, as_stream(stream), (long)ldq, qscale);
+}
+
+// Rows wider than 2048 (include/cvar_wide.h): the same kernel text with NV = 9 .. 12 vectors per lane; C <= 2048 goes to ln_dispatch and so to the
+// very instantiations the three entry points above launch.
+static_assert(CVAR_WIDE_CMAX == 12 * 256, "the widest instantiation below is NV = 12");
+template <typename TO>
+static int ln_dispatch_wide(const float* x, const float* scale, const float* shift, long ld_ada, int rows_per, TO* out, int M, int C,
+                            float eps, hipStream_t st, long ldq = 0, float* qscale = nullptr) {
+    const int nv = (C + 255) / 256;
+    if (nv <= 8) return ln_dispatch<TO>(x, scale, shift, ld_ada, rows_per, out, M, C, eps, st, ldq, qscale);
+    const bool tail = (C % 256) != 0;
+    dim3 grid(cdiv(M, 4));
+    switch (nv) {
+        case 9: ln_launch<TO, 9>(tail, grid, st, x, scale, shift, ld_ada, rows_per, out, M, C, eps, ldq, qscale); break;
+        case 10: ln_launch<TO, 10>(tail, grid, st, x, scale, shift, ld_ada, rows_per, out, M, C, eps, ldq, qscale); break;
+        case 11: ln_launch<TO, 11>(tail, grid, st, x, scale, shift, ld_ada, rows_per, out, M, C, eps, ldq, qscale); break;
+        case 12: ln_launch<TO, 12>(tail, grid, st, x, scale, shift, ld_ada, rows_per, out, M, C, eps, ldq, qscale); break;
+        default: return CVAR_EUNSUPPORTED;
+    }
+    CVAR_CHECK_LAUNCH();
+    return CVAR_OK;
+}
+
+extern "C" int cvar_ln_modulate_wide(const float* x, const float* scale, const float* shift, int64_t ld_ada, int rows_per,
+                                     void* out, int out_dtype, int M, int C, float eps, void* stream) {
+    if (!x || !scale || !shift || !out || M <= 0 || rows_per <= 0) return CVAR_EINVAL;
+    if (C % 4 || C > CVAR_WIDE_CMAX || ld_ada % 4) return CVAR_EUNSUPPORTED;
+    if (out_dtype == CVAR_BF16) return ln_dispatch_wide<bf16_t>(x, scale, shift, (long)ld_ada, rows_per, (bf16_t*)out, M, C, eps, as_stream(stream));
+    if (out_dtype == CVAR_F32) return ln_dispatch_wide<float>(x, scale, shift, (long)ld_ada, rows_per, (float*)out, M, C, eps, as_stream(stream));
+    return CVAR_EUNSUPPORTED;
+}
+
+extern "C" int cvar_ln_modulate_split3_wide(const float* x, const float* scale, const float* shift, int64_t ld_ada, int rows_per,
+                                            void* out, int M, int C, float eps, void* stream) {
+    if (!x || !scale || !shift || !out || M <= 0 || rows_per <= 0) return CVAR_EINVAL;
+    if (C % 4 || C > CVAR_WIDE_CMAX || ld_ada % 4 || (((uintptr_t)x | (uintptr_t)scale | (uintptr_t)shift) & 15) || ((uintptr_t)out & 7)) return CVAR_EUNSUPPORTED;
+    return ln_dispatch_wide<bf16x3_t>(x, scale, shift, (long)ld_ada, rows_per, (bf16x3_t*)out, M, C, eps, as_stream(stream));
+}
+
+extern "C" int cvar_ln_modulate_fp8_wide(const float* x, const float* scale, const float* shift, int64_t ld_ada, int rows_per,
+                                         void* q, int64_t ldq, float* qscale, int M, int C, float eps, void* stream) {
+    if (!x || !scale || !shift || !q || !qscale || M <= 0 || rows_per <= 0) return CVAR_EINVAL;
+    if (C % 4 || C > CVAR_WIDE_CMAX || ld_ada % 4 || ldq % 128 || ldq < C ||
+        (((uintptr_t)x | (uintptr_t)scale | (uintptr_t)shift | (uintptr_t)q) & 15)) return CVAR_EUNSUPPORTED;
+    return ln_dispatch_wide<fp8q_t>(x, scale, shift, (long)ld_ada, rows_per, (fp8q_t*)q, M, C, eps, as_stream(stream), (long)ldq, qscale);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -18,6 +18,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from . import _lib
 from ._lib import CvarError
 from ._lib import ACT_GELU_TANH
 from .pyramid import packed_tables
@@ -1025,6 +1026,9 @@ class ControlVAR(nn.Module):
     ``more_smooth`` = Gumbel-softmax soft code embeddings.  ``separator`` (+18 special tokens, head V + 18, special_embed): upstream
     indexes special_embed with V + k and raises IndexError everywhere (control_var.py:549,606); built with the evidently intended
     index k for forward() / training and the joint inference branch - including upstream's placement quirks there (:507-509,538).
+    Width: ``embed_dim`` up to CVAR_WIDE_CMAX = 3072 at 64 channels per head (depth 48 by the factories' ``64 * depth``; d36 = 2304, d40 = 2560), in
+    every mode.  Above 2048 the adaLN rows come from the kernels of include/cvar_wide.h as a launch of their own at every pass size (DESIGN.md 4k);
+    a wider model raises ValueError.
     """
     _control = True
 
@@ -1096,10 +1100,11 @@ class ControlVAR(nn.Module):
         self.bidirectional = cfg.bidirectional
         self.Cvae, self.V = cfg.cvae, cfg.vocab
         self.depth, self.C, self.D, self.num_heads = depth, cfg.C, cfg.C, cfg.H
-        if cfg.C > 2048:
-            # surfaced here instead of as CVAR_EUNSUPPORTED from inside a GEMM call: the adaLN kernels keep a row of the residual stream in one wave's
-            # registers (cvar_ln_modulate / the row-finishing reduction: C <= 2048 = depth <= 32 at 64 channels per head)
-            raise ValueError(f'embed_dim {cfg.C} > 2048: the adaLN kernels of controlvar_amd hold one row per wave (depth <= 32)')
+        if cfg.C > _lib.WIDE_CMAX:
+            # surfaced here instead of as CVAR_EUNSUPPORTED from inside a kernel call: the adaLN kernels keep a row of the residual stream in one wave's
+            # registers (cvar_ln_modulate up to 2048, include/cvar_wide.h up to CVAR_WIDE_CMAX = depth <= 48 at 64 channels per head)
+            raise ValueError(f'embed_dim {cfg.C} > CVAR_WIDE_CMAX = {_lib.WIDE_CMAX}: the adaLN kernels of controlvar_amd hold one row per wave '
+                             f'(depth <= {_lib.WIDE_CMAX // 64})')
         self.patch_nums, self.mask_factor, self.multi_cond = tuple(patch_nums), mask_factor, cfg.multi_cond
         py = cfg.pyramid
         self.L, self.first_l = py.L, py.first_l
@@ -1483,6 +1488,9 @@ class ControlVAR(nn.Module):
         # operands.  (The order of these allocations is part of the pass: the caching allocator reuses freed blocks by it, and torch.cuda.max_memory_allocated()
         # counts whole blocks - the peak that tests/test_gpu_block_pass_launches.py holds a fresh process to follows from it.)
         fc1_out, fuse_ln, fed = {}, False, ()           # fed: the layers whose operand feed() has to make
+        # adaLN rows wider than 2048: the entry points of include/cvar_wide.h; narrow models call ops exactly as before
+        ln_rows, ln_rows3, ln_rows8 = ((ops.ln_modulate_wide, ops.ln_modulate_split3_wide, ops.ln_modulate_fp8_wide) if C > 2048 else
+                                       (ops.ln_modulate, ops.ln_modulate_split3, ops.ln_modulate_fp8))
         if mode is None:
             u = buf(C, T)                                             # adaLN rows: operand of qkv / fc1 / head
             o = buf(C, T)
@@ -1497,11 +1505,12 @@ class ControlVAR(nn.Module):
             fc1_out = dict(ldc=hid + kx)
             # Small passes (early scales, small batches): proj / fc2 also produce the adaLN input of the op that follows (cvar_gemm_desc.ln_out) - their split-K
             # reduction finishes rows, so LayerNorm + modulation ride in that launch instead of a cvar_ln_modulate of their own (same bits).  Large passes keep the
-            # separate launch: their GEMMs finish tiles, not rows.
-            fuse_ln = M < FUSE_LN_BELOW
+            # separate launch: their GEMMs finish tiles, not rows.  So do all passes of a model wider than 2048: ln_out stops there (include/cvar.h), and the
+            # separate launch is the wide kernel of include/cvar_wide.h.
+            fuse_ln = M < FUSE_LN_BELOW and C <= 2048
 
             def norm(sc, sh, head=False):
-                ops.ln_modulate(x, ada, sc, sh, n_ada, l, u, M, C, eps)
+                ln_rows(x, ada, sc, sh, n_ada, l, u, M, C, eps)
                 return u
 
             def linear(layer, i, a, out, **epi):
@@ -1531,7 +1540,7 @@ class ControlVAR(nn.Module):
             qs = buf(C, T)
 
             def norm(sc, sh, head=False):
-                ops.ln_modulate_split3(x, ada, sc, sh, n_ada, l, u3, M, C, eps)
+                ln_rows3(x, ada, sc, sh, n_ada, l, u3, M, C, eps)
                 return u3
 
             fed = ('proj', 'fc2')
@@ -1559,9 +1568,9 @@ class ControlVAR(nn.Module):
 
             def norm(sc, sh, head=False):
                 if head:
-                    ops.ln_modulate(x, ada, sc, sh, n_ada, l, ub, M, C, eps)
+                    ln_rows(x, ada, sc, sh, n_ada, l, ub, M, C, eps)
                     return ub
-                ops.ln_modulate_fp8(x, ada, sc, sh, n_ada, l, *u8, M, C, eps, ldq=ldq[C])
+                ln_rows8(x, ada, sc, sh, n_ada, l, *u8, M, C, eps, ldq=ldq[C])
                 return u8
 
             def feed(name, i, a):

@@ -222,6 +222,36 @@ def ln_modulate_fp8(x: torch.Tensor, ada: torch.Tensor, scale_off: int, shift_of
     return q, q_scale
 
 
+def ln_modulate_wide(x: torch.Tensor, ada: torch.Tensor, scale_off: int, shift_off: int, ld_ada: int, rows_per: int,
+                     out: torch.Tensor, M: int, Cdim: int, eps: float):
+    """ln_modulate for any C <= CVAR_WIDE_CMAX (cvar_ln_modulate_wide, include/cvar_wide.h): up to 2048 channels the kernels ln_modulate launches.
+    The models call this form, and the two below, where embed_dim > 2048; ln_modulate itself keeps cvar_ln_modulate's contract and refusals."""
+    base = _ptr(ada)
+    check(_lib.load().cvar_ln_modulate_wide(_ptr(x), base + 4 * scale_off, base + 4 * shift_off, ld_ada, rows_per,
+                                            _ptr(out), dt(out), M, Cdim, eps, _stream()), 'cvar_ln_modulate_wide')
+    return out
+
+
+def ln_modulate_split3_wide(x: torch.Tensor, ada: torch.Tensor, scale_off: int, shift_off: int, ld_ada: int, rows_per: int,
+                            out: torch.Tensor, M: int, Cdim: int, eps: float):
+    """ln_modulate_split3 for any C <= CVAR_WIDE_CMAX (cvar_ln_modulate_split3_wide, include/cvar_wide.h)"""
+    base = _ptr(ada)
+    check(_lib.load().cvar_ln_modulate_split3_wide(_ptr(x), base + 4 * scale_off, base + 4 * shift_off, ld_ada, rows_per,
+                                                   _ptr(out), M, Cdim, eps, _stream()), 'cvar_ln_modulate_split3_wide')
+    return out
+
+
+def ln_modulate_fp8_wide(x: torch.Tensor, ada: torch.Tensor, scale_off: int, shift_off: int, ld_ada: int, rows_per: int,
+                         q: torch.Tensor, q_scale: torch.Tensor, M: int, Cdim: int, eps: float, ldq: int = 0):
+    """ln_modulate_fp8 for any C <= CVAR_WIDE_CMAX (cvar_ln_modulate_fp8_wide, include/cvar_wide.h)"""
+    if q.dtype != torch.uint8 or q_scale.dtype != torch.float32:
+        raise TypeError('q is uint8 (e4m3 bytes), q_scale is float32')
+    base = _ptr(ada)
+    check(_lib.load().cvar_ln_modulate_fp8_wide(_ptr(x), base + 4 * scale_off, base + 4 * shift_off, ld_ada, rows_per,
+                                                _ptr(q), ldq or fp8_ldq(Cdim), _ptr(q_scale), M, Cdim, eps, _stream()), 'cvar_ln_modulate_fp8_wide')
+    return q, q_scale
+
+
 def gemm_fp8(A: torch.Tensor, a_scale: torch.Tensor, W: torch.Tensor, w_scale: torch.Tensor, out: torch.Tensor, *, M: int, N: int, K: int,
              lda: int = 0, ldw: int = 0, ldc: int = 0, bias: Optional[torch.Tensor] = None, act: int = ACT_NONE, alpha: float = 1.0,
              gate: Optional[torch.Tensor] = None, ldg: int = 0, gate_rows: int = 1, gate_off: int = 0,

@@ -138,6 +138,11 @@ def _pad8(n: int) -> int:
     return (n + 7) // 8 * 8
 
 
+def _ln_rows(C: int):
+    """the adaLN forward of rows of C channels: above 2048 the entry point of include/cvar_wide.h; narrow models call ops.ln_modulate exactly as before"""
+    return ops.ln_modulate_wide if C > 2048 else ops.ln_modulate
+
+
 class TrainEngine:
     """Teacher-forced forward + backward of ControlVAR / VAR over the HIP kernels (control_var.py:568-651 under autograd).
 
@@ -429,7 +434,7 @@ class TrainEngine:
         for i in range(depth):
             a0 = i * 6 * C
             x = self.Xs[i]
-            ops.ln_modulate(x, ada, a0 + 2 * C, a0 + 4 * C, n_ada, L, self.U[i], M, C, eps)
+            _ln_rows(C)(x, ada, a0 + 2 * C, a0 + 4 * C, n_ada, L, self.U[i], M, C, eps)
             ops.gemm(self.U[i], P['w_qkv'], self.arena[i], M=M, N=3 * C, K=C, w_off=i * 3 * C * C, bias=P['b_qkv'][i])
             if cfg.uses_cos_attn:
                 ops.cos_qk_norm(self.arena[i], B, H, L, 0, L, P['scale_mul'], sm_off=i * H, norms=self.NORMS[i])
@@ -441,14 +446,14 @@ class TrainEngine:
             # needs (d gamma1 = sum dx * f) is stored next to it
             ops.gemm(self.O[i], P['w_proj'], self.X1s[i], M=M, N=C, K=C, w_off=i * C * C, bias=P['b_proj'][i], gate=ada, ldg=n_ada, gate_rows=L,
                      gate_off=a0, gate_scale=dp1[i].contiguous() if dp1 is not None else None, residual=x, pre_act=self.F1[i])
-            ops.ln_modulate(self.X1s[i], ada, a0 + 3 * C, a0 + 5 * C, n_ada, L, self.U2[i], M, C, eps)
+            _ln_rows(C)(self.X1s[i], ada, a0 + 3 * C, a0 + 5 * C, n_ada, L, self.U2[i], M, C, eps)
             # fc1 with the GELU in its epilogue; the pre-activation the backward needs is stored alongside (no separate gelu pass)
             ops.gemm(self.U2[i], P['w_fc1'], self.Hh[i], M=M, N=hid, K=C, w_off=i * hid * C, bias=P['b_fc1'][i], act=ACT_GELU_TANH,
                      pre_act=self.A[i])
             ops.gemm(self.Hh[i], P['w_fc2'], self.Xs[i + 1], M=M, N=C, K=hid, w_off=i * C * hid, bias=P['b_fc2'][i], gate=ada, ldg=n_ada, gate_rows=L,
                      gate_off=a0 + C, gate_scale=dp2[i].contiguous() if dp2 is not None else None, residual=self.X1s[i], pre_act=self.F2[i])
         ah = depth * 6 * C
-        ops.ln_modulate(self.Xs[depth], ada, ah, ah + C, n_ada, L, self.UH, M, C, eps)
+        _ln_rows(C)(self.Xs[depth], ada, ah, ah + C, n_ada, L, self.UH, M, C, eps)
         ops.gemm(self.UH, P['w_head'], self.logits, M=M, N=V, K=C, bias=P['b_head'])
         self._saved = dict(ada=ada, cs=cs, cond=cond, labels=labels, types=types, tok=tok, dp1=dp1, dp2=dp2, B=B)
         return self.logits
@@ -740,7 +745,7 @@ class TrainEngine:
                       x_copy=self.Oa[i], ld_copy=kc)
         ops.gemm(self.Oa[i], self.Wa['proj'], self.X1s[i], M=M, N=C, K=kc, lda=kc, ldw=kc, w_off=i * C * kc, bias=P['b_proj'][i], gate=ada, ldg=n_ada,
                  gate_rows=L, gate_off=a0, gate_scale=dp1[i].contiguous() if dp1 is not None else None, residual=x, pre_act=self.F1[i])
-        ops.ln_modulate(self.X1s[i], ada, a0 + 3 * C, a0 + 5 * C, n_ada, L, self.U2, M, C, eps)
+        _ln_rows(C)(self.X1s[i], ada, a0 + 3 * C, a0 + 5 * C, n_ada, L, self.U2, M, C, eps)
         ops.lora_down(self.U2, self.LA['fc1'][i], self.U2a[i], M=M, K=C, r=r, scale=s, p=p, seed=seed, tag=self._tag(i, 'fc1'), ldu=kc, u_off=C,
                       x_copy=self.U2a[i], ld_copy=kc)
         ops.gemm(self.U2a[i], self.Wa['fc1'], self.Hha[i], M=M, N=hid, K=kc, lda=kc, ldw=kc, ldc=kh, w_off=i * hid * kc, bias=P['b_fc1'][i],
