@@ -132,6 +132,7 @@ import torch  # noqa: E402
 
 from . import ops  # noqa: E402
 from ._lib import ACT_GELU_GRAD, ACT_GELU_TANH, ACT_NONE  # noqa: E402
+from .spec import attention_levels  # noqa: E402
 
 
 def _pad8(n: int) -> int:
@@ -143,6 +144,9 @@ def _ln_rows(C: int):
     return ops.ln_modulate_wide if C > 2048 else ops.ln_modulate
 
 
+_MODS = dict(qkv='attn.mat_qkv', proj='attn.proj', fc1='ffn.fc1', fc2='ffn.fc2')          # linear of a block -> its module name in the state dict
+
+
 class TrainEngine:
     """Teacher-forced forward + backward of ControlVAR / VAR over the HIP kernels (control_var.py:568-651 under autograd).
 
@@ -150,6 +154,19 @@ class TrainEngine:
     MFMA GEMM as the forward on transposed operands (activations are transposed into zero-padded [N][Mpad] buffers),
     accumulated in fp32 into per-layer contiguous slabs so that each layer's slab can be all-reduced as soon as its
     backward is done (bucket = layer, overlapped with the rest of the backward on a side stream).
+
+    One walk serves the full model and a LoRA model (controlvar_amd/lora.py).  The walk owns the order of a block - adaLN, qkv,
+    cos-norm, attention, proj, adaLN, fc1, fc2 forward; gated_grad, the four data-gradient GEMMs, the three ln_modulate_bwd,
+    attention_bwd, cos_qk_norm_bwd and reducer.ready(i) backward - with every epilogue and offset written once.  A mode supplies
+    * its set of buffers in `_setup`, with `Xin`: linear -> (saved input (depth, M, ld), row stride ld; 0 = dense rows), where the forward
+      leaves the operand of a linear and the backward finds it again;
+    * the forward leaf that launches a linear (`ops.gemm` on the packed weight; `_lora_linear`);
+    * the backward leaf that follows a data-gradient GEMM (`_full_grads_of`: the weight and bias gradient; `_lora_grads_of`: du, the
+      branch's share of dx, dB, dA);
+    * its generator tail (`_ada_grads_full`, then `_embedding_grads`; `_ada_grads_lora`) and its gradient layout in `_setup_grads`:
+      `grad_views`, state_dict key -> (buffer, offset, shape), which `grads()` turns into views.
+    What only the full model has is said where it happens: GELU' fused into fc2's data-gradient GEMM, the parameter gradients of qkv
+    and head, colsum(DSM), the embedding tail.
 
     Gradient accumulation: ``forward_backward(..., accumulate=True)`` adds this micro-batch's gradient to what
     ``grads()`` holds - every element becomes fp32(old + plain), `plain` being the bits the non-accumulating call produces - so a
@@ -159,7 +176,7 @@ class TrainEngine:
 
     def __init__(self, var, drop_path: bool = True, reducer=None):
         self.var = var
-        self.cfg = var.cfg
+        self.cfg = cfg = var.cfg
         self.drop_path = drop_path
         self.reducer = reducer
         self._B = None
@@ -167,32 +184,59 @@ class TrainEngine:
         self._lora = None
         self._grads_key = None          # what the gradient buffers were allocated for: 'full' or ('lora', id of the LoRA state)
         self._staging = {}              # accumulating backward: fp32 staging buffers by name (_stage)
+        # the dimensions every method needs; those of a batch (M, Mp, Bp) and of a LoRA state (r, rp, Kx, kc, kh) are set by _setup
+        self.C, self.depth, self.V, self.L = cfg.C, cfg.depth, cfg.head_ld, cfg.pyramid.L      # head columns incl. separator labels, padded to 8 (spec.VarConfig.head_ld)
+        self.hid = round(cfg.C * cfg.mlp_ratio)
+        self.ah = cfg.depth * 6 * cfg.C                                                        # the head's rows of the adaLN generator
+        self.n_ada = self.ah + 2 * cfg.C
+        self.ncode = len(cfg.pyramid.code_positions()) - cfg.pyramid.first_l                   # teacher-forcing tokens per sample (separators excluded)
+        self.lvl_end, self.holes = attention_levels(cfg)
+        self.scale, self.eps = float(cfg.attn_scale), cfg.norm_eps
 
     # ---------------------------------------------------------------- buffers
     def _setup(self, B: int):
-        lora = getattr(self.var, '_lora', None)
-        if lora is not None:
-            return self._setup_lora(B, lora)
-        if self._lora is not None:                  # the adapters were merged away: back to the full path
-            self._lora, self._B = None, None
-        if self._B == B:
-            return
+        """the buffers of batch size B: what both modes have, and in its place the mode's own set.  LoRA: the base weights are
+        frozen, so nothing of their weight gradients exists (TA / TB, the slabs); the operand of each adapted linear is kept K-augmented,
+        [x | u | 0] with u = s drop(x) A^T and zero padding up to a 128-byte row step."""
         cfg, var = self.cfg, self.var
+        lora = getattr(var, '_lora', None)
+        if lora is None and self._lora is not None:                   # the adapters were merged away: back to the full path
+            self._lora, self._B = None, None
+        key = B if lora is None else (B, id(lora))
+        if self._B == key:
+            return
         dev, T = var.device, var.compute_dtype
-        C, depth, V = cfg.C, cfg.depth, cfg.head_ld          # head columns incl. separator labels, padded to 8 (spec.VarConfig.head_ld)
-        L = cfg.pyramid.L
+        C, depth, V, L, hid, n_ada = self.C, self.depth, self.V, self.L, self.hid, self.n_ada
         M = B * L
-        hid = round(C * cfg.mlp_ratio)
-        n_ada = depth * 6 * C + 2 * C
         self.M, self.Mp, self.Bp = M, _pad8(M), _pad8(B)
+        self.Xin = {}                                                 # the old plan's references go with its buffers
         f32 = dict(device=dev, dtype=torch.float32)
         tT = dict(device=dev, dtype=T)
+        if lora is not None:
+            rp = 128 // torch.tensor([], dtype=T).element_size()      # augmented K step: keeps cvar_gemm on its K-multiple-of-128-bytes path
+            self._lora, self.r, self.rp = lora, lora['r'], rp
+            self.Kx = -(-(depth + 1) * 16 // rp) * rp                 # [cs | u_0 ... u_depth] columns beyond C
+            self.kc, self.kh = kc, kh = C + rp, hid + rp
         # saved activations
         self.Xs = torch.empty(depth + 1, M, C, **f32)
         self.X1s = torch.empty(depth, M, C, **f32)
         self.U = torch.empty(depth, M, C, **tT); self.O = torch.empty(depth, M, C, **tT)
-        self.F1 = torch.empty(depth, M, C, **tT); self.U2 = torch.empty(depth, M, C, **tT); self.F2 = torch.empty(depth, M, C, **tT)
-        self.A = torch.empty(depth, M, hid, **tT); self.Hh = torch.empty(depth, M, hid, **tT)
+        self.F1 = torch.empty(depth, M, C, **tT)
+        if lora is None:
+            self.U2 = torch.empty(depth, M, C, **tT)
+        else:                                                         # fc1's input is kept in its augmented buffer: one (M, C) scratch serves every layer
+            self.U2 = torch.empty(M, C, **tT).expand(depth, M, C)
+        self.F2 = torch.empty(depth, M, C, **tT)
+        if lora is None:
+            self.A = torch.empty(depth, M, hid, **tT); self.Hh = torch.empty(depth, M, hid, **tT)
+            self.Xin = dict(qkv=(self.U, 0), proj=(self.O, 0), fc1=(self.U2, 0), fc2=(self.Hh, 0))
+        else:
+            Oa = torch.zeros(depth, M, kc, **tT)                      # [o | u_proj | 0]
+            U2a = torch.zeros(depth, M, kc, **tT)                     # [u2 | u_fc1 | 0]
+            self.Hh = torch.zeros(depth, M, kh, **tT)                 # [gelu(a) | u_fc2 | 0]
+            self.A = torch.empty(depth, M, kh, **tT)                  # fc1 pre-activation (row stride of the fc1 output)
+            self.csa = torch.zeros(B, C + self.Kx, **tT)
+            self.Xin = dict(proj=(Oa, kc), fc1=(U2a, kc), fc2=(self.Hh, kh), ada=(self.csa[None], C + self.Kx))
         self.arena = torch.empty(depth, B, L, 3 * C, **tT)
         self.LSE = torch.empty(depth, B, cfg.H, L, **f32)
         self.NORMS = torch.empty(depth, B, L, cfg.H, 2, **f32) if cfg.uses_cos_attn else None
@@ -206,56 +250,111 @@ class TrainEngine:
         self.DF = torch.empty(M, C, **tT); self.DU = torch.empty(M, C, **tT)
         self.DH = torch.empty(M, hid, **tT)
         self.DQKV = torch.empty(B, L, 3 * C, **tT)
-        nmax = max(hid, 3 * C, V)
-        self.TA = torch.zeros(nmax * self.Mp, **tT)           # zero padding columns stay zero
-        self.TB = torch.zeros(nmax * self.Mp, **tT)
-        self.ncode = len(cfg.pyramid.code_positions()) - cfg.pyramid.first_l         # teacher-forcing tokens per sample (separators excluded)
-        self.TA32 = torch.zeros(C * _pad8(B * self.ncode), **f32)
-        self.TB32 = torch.zeros(cfg.cvae * _pad8(B * self.ncode), **f32)
+        if lora is None:
+            nmax = max(hid, 3 * C, V)
+            self.TA = torch.zeros(nmax * self.Mp, **tT)               # zero padding columns stay zero
+            self.TB = torch.zeros(nmax * self.Mp, **tT)
+            self.TA32 = torch.zeros(C * _pad8(B * self.ncode), **f32)
+            self.TB32 = torch.zeros(cfg.cvae * _pad8(B * self.ncode), **f32)
+        else:
+            self.DUr = torch.empty(M, 16, **tT)
+            self.DUa = torch.empty(B, 16, **tT)
         self.dada = torch.zeros(B, n_ada, **f32)
         self.ws = torch.empty(max(ops.train_ws_floats(M, B, C), 64 * max(hid, 3 * C, V, n_ada), L * C, B * cfg.H * L,
                                   6 * C * C if cfg.shared_aln else 0) + 16, **f32)
-        self._setup_grads()
-        self._B = B
+        if lora is not None:
+            self.lws = torch.empty(max(ops.lora_wgrad_ws_floats(M, hid), ops.lora_wgrad_ws_floats(M, C), ops.lora_wgrad_ws_floats(B, 6 * C)), **f32)
+            self._aug = None
+        self._setup_grads(lora)
+        self._B = key
         self._transposed_weights()
 
-    def _setup_grads(self):
-        """gradient buffers of the full model: once per engine, whatever the batch size (a window of micro-batches accumulates into them)"""
-        if self._grads_key == 'full':
+    def _setup_grads(self, lora=None):
+        """gradient buffers and their layout: once per engine (full model) or per adapter state (LoRA), whatever the batch size (a window of
+        micro-batches accumulates into them).  The layout is declared here alone: `grad_views`, state_dict key -> (buffer, offset, shape)."""
+        key = 'full' if lora is None else ('lora', id(lora))
+        if self._grads_key == key:
             return
         cfg = self.cfg
-        C, depth, V = cfg.C, cfg.depth, cfg.head_ld
-        L = cfg.pyramid.L
-        hid = round(C * cfg.mlp_ratio)
-        n_ada = depth * 6 * C + 2 * C
+        C, depth, V, L, hid, n_ada, ah, H = self.C, self.depth, self.V, self.L, self.hid, self.n_ada, self.ah, cfg.H
         f32 = dict(device=self.var.device, dtype=torch.float32)
-        # gradient slabs: [layer][w_qkv | w_proj | w_fc1 | w_fc2 | b_qkv | b_proj | b_fc1 | b_fc2]
-        self.slab_off = {}
-        o = 0
-        for name, n in (('w_qkv', 3 * C * C), ('w_proj', C * C), ('w_fc1', hid * C), ('w_fc2', C * hid), ('b_qkv', 3 * C), ('b_proj', C),
-                        ('b_fc1', hid), ('b_fc2', C), ('scale_mul', _pad8(cfg.H))):
-            self.slab_off[name] = o
-            o += n
-        self.slab = o
-        self.G_layers = torch.zeros(depth, self.slab, **f32)
-        self.G_ada = torch.zeros(n_ada * C + n_ada, **f32)                       # [w_ada | b_ada]
-        misc = [('w_head', V * C), ('b_head', V), ('w_we', C * cfg.cvae), ('b_we', C), ('pos', L * C), ('lvl', len(cfg.patch_nums) * C),
-                ('pos_start', cfg.pyramid.first_l * C), ('class_emb', (cfg.num_classes + 1) * C), ('cond_embed', 5 * C)]
-        if cfg.shared_aln:      # SURVEY.md 8f N4: the shared generator's gradient = sum over blocks of the per-block (folded) ones
-            misc += [('w_shared', 6 * C * C), ('b_shared', 6 * C)]
-        if cfg.type_pos:
-            misc += [('type', cfg.mask_factor * C)]
-        if cfg.separator:
-            misc += [('special', cfg.n_special * C)]
-        self.misc_off = {}
-        o = 0
-        for name, n in misc:
-            self.misc_off[name] = (o, n)
-            o += n
-        self.G_misc = torch.zeros(o, **f32)
-        self.buckets = [self.G_layers[i] for i in range(depth)] + [self.G_ada, self.G_misc]
+        views = {}
+        if lora is None:
+            # gradient slabs: [layer][w_qkv | w_proj | w_fc1 | w_fc2 | b_qkv | b_proj | b_fc1 | b_fc2 | scale_mul]
+            self.slab_off, o = {}, 0
+            for name, n in (('w_qkv', 3 * C * C), ('w_proj', C * C), ('w_fc1', hid * C), ('w_fc2', C * hid), ('b_qkv', 3 * C), ('b_proj', C),
+                            ('b_fc1', hid), ('b_fc2', C), ('scale_mul', _pad8(H))):
+                self.slab_off[name] = o
+                o += n
+            self.slab = o
+            self.G_layers = torch.zeros(depth, self.slab, **f32)
+            self.G_ada = torch.zeros(n_ada * C + n_ada, **f32)                       # [w_ada | b_ada]: 6C rows of each per block, then the head's 2C
+            # (key in the block, slab entry, offset in it, shape); the k-bias third of b_qkv has no key (zero_k_bias is a buffer)
+            layer = [(_MODS['qkv'] + '.weight', 'w_qkv', 0, (3 * C, C)), (_MODS['proj'] + '.weight', 'w_proj', 0, (C, C)),
+                     (_MODS['fc1'] + '.weight', 'w_fc1', 0, (hid, C)), (_MODS['fc2'] + '.weight', 'w_fc2', 0, (C, hid)),
+                     ('attn.q_bias', 'b_qkv', 0, (C,)), ('attn.v_bias', 'b_qkv', 2 * C, (C,)), (_MODS['proj'] + '.bias', 'b_proj', 0, (C,)),
+                     (_MODS['fc1'] + '.bias', 'b_fc1', 0, (hid,)), (_MODS['fc2'] + '.bias', 'b_fc2', 0, (C,))]
+            if cfg.uses_cos_attn:
+                layer.append(('attn.scale_mul_1H11', 'scale_mul', 0, (1, H, 1, 1)))
+            Gl, Ga, ba = self.G_layers.view(-1), self.G_ada, n_ada * C
+            for i in range(depth):
+                p = f'blocks.{i}.'
+                for k, name, o, shape in layer:
+                    views[p + k] = (Gl, i * self.slab + self.slab_off[name] + o, shape)
+                if cfg.sa_block:        # constants in the folded bias (models._pack): [gamma1, gamma2, w1 - 1, w2 - 1, b1, b2]
+                    for j, k in enumerate(('gamma1', 'gamma2', 'norm1.weight', 'norm2.weight', 'norm1.bias', 'norm2.bias')):
+                        if j >= 2 or cfg.layer_scale >= 0:
+                            views[p + k] = (Ga, ba + (i * 6 + j) * C, (C,))
+                elif cfg.shared_aln:    # folded bias_i = shared bias + ada_gss_i (models._pack): d ada_gss_i = d bias_i
+                    views[p + 'ada_gss'] = (Ga, ba + i * 6 * C, (1, 1, 6, C))
+                else:
+                    views[p + 'ada_lin.1.weight'] = (Ga, i * 6 * C * C, (6 * C, C))
+                    views[p + 'ada_lin.1.bias'] = (Ga, ba + i * 6 * C, (6 * C,))
+            if cfg.sa_block:            # head = Sequential(LayerNorm, Linear) (control_var.py:205-207)
+                views['head.0.weight'], views['head.0.bias'] = (Ga, ba + ah, (C,)), (Ga, ba + ah + C, (C,))
+            else:
+                views['head_nm.ada_lin.1.weight'], views['head_nm.ada_lin.1.bias'] = (Ga, ah * C, (2 * C, C)), (Ga, ba + ah, (2 * C,))
+            # (region, its size, key or None, shape); the head's rows beyond head_out (padding of head_ld) have no key
+            hd, py, Vo = 'head.1.' if cfg.sa_block else 'head.', cfg.pyramid, cfg.head_out
+            nl, fl, nc = len(cfg.patch_nums), py.first_l, cfg.num_classes + 1
+            misc = [('w_head', V * C, hd + 'weight', (Vo, C)), ('b_head', V, hd + 'bias', (Vo,)), ('w_we', C * cfg.cvae, 'word_embed.weight', (C, cfg.cvae)),
+                    ('b_we', C, 'word_embed.bias', (C,)), ('pos', L * C, 'pos_1LC', (1, L, C)), ('lvl', nl * C, 'lvl_embed.weight', (nl, C)),
+                    ('pos_start', fl * C, 'pos_start', (1, fl, C)), ('class_emb', nc * C, 'class_emb.weight', (nc, C)),
+                    ('cond_embed', 5 * C, 'cond_embed.weight' if cfg.mask_factor == 2 else None, (5, C))]
+            if cfg.shared_aln:      # SURVEY.md 8f N4: the shared generator's gradient = sum over blocks of the per-block (folded) ones
+                misc += [('w_shared', 6 * C * C, 'shared_ada_lin.1.weight', (6 * C, C)), ('b_shared', 6 * C, 'shared_ada_lin.1.bias', (6 * C,))]
+            if cfg.type_pos:
+                misc += [('type', cfg.mask_factor * C, 'type_embed.weight', (cfg.mask_factor, C))]
+            if cfg.separator:
+                misc += [('special', cfg.n_special * C, 'special_embed.weight', (cfg.n_special, C))]
+            self.misc_off, o = {}, 0
+            for name, n, _, _ in misc:
+                self.misc_off[name] = (o, n)
+                o += n
+            self.G_misc = torch.zeros(o, **f32)
+            views.update({k: (self.G_misc, self.misc_off[name][0], shape) for name, _, k, shape in misc if k is not None})
+            self.buckets = [self.G_layers[i] for i in range(depth)] + [self.G_ada, self.G_misc]
+        else:
+            # adapter gradient slabs: one per layer [proj A, B | fc1 A, B | fc2 A, B], then every ada_lin adapter (the all-reduce buckets)
+            r = lora['r']
+            dims = dict(proj=(C, C), fc1=(C, hid), fc2=(hid, C))
+            groups = [[(f'blocks.{i}.{_MODS[kind]}', *dims[kind]) for kind in ('proj', 'fc1', 'fc2')] for i in range(depth)]
+            groups.append([(f'blocks.{t}.ada_lin.1', C, 6 * C) for t in range(depth)] + [('head_nm.ada_lin.1', C, 2 * C)])
+            self.lora_off, o, starts = {}, 0, []
+            for group in groups:
+                starts.append(o)
+                for name, k_in, n_out in group:
+                    for ab, shape in (('A', (r, k_in)), ('B', (n_out, r))):
+                        self.lora_off[f'{name}.lora_{ab}.default.weight'] = (o, shape[0] * shape[1], shape)
+                        o += shape[0] * shape[1]
+            if set(self.lora_off) != {n for n, p in self.var.named_parameters() if p.requires_grad}:
+                raise RuntimeError('LoRA: the trainable parameters are not exactly the adapters of add_lora')
+            self.G_lora = torch.zeros(o, **f32)
+            self.buckets = [self.G_lora[a:b] for a, b in zip(starts, starts[1:] + [o])]
+            views = {k: (self.G_lora, o, shape) for k, (o, _, shape) in self.lora_off.items()}
+        self.grad_views = views
         self._staging = {}
-        self._grads_key = 'full'
+        self._grads_key = key
 
     def _stage(self, name: str, n: int) -> torch.Tensor:
         """fp32 staging buffer of an accumulating backward (allocated on first use, kept): what cannot take the accumulate flag at its producer
@@ -267,19 +366,16 @@ class TrainEngine:
 
     def _transposed_weights(self):
         """W^T copies for the data-gradient GEMMs (refreshed after every optimizer step).  LoRA: of the frozen base weights."""
-        P, cfg = self.var._pack(base=True), self.cfg
-        C, depth, V = cfg.C, cfg.depth, cfg.head_ld
-        hid = P['w_fc1'].shape[1]
-        T = self.var.compute_dtype
-        dev = self.var.device
-        mk = lambda *s: torch.empty(*s, device=dev, dtype=T)
-        self.WT = dict(qkv=mk(depth, C, 3 * C), proj=mk(depth, C, C), fc1=mk(depth, C, hid), fc2=mk(depth, hid, C), head=mk(C, V), ada=mk(C, P['n_ada']))
+        P = self.var._pack(base=True)
+        C, depth, V, hid, n_ada = self.C, self.depth, self.V, self.hid, self.n_ada
+        mk = lambda *s: torch.empty(*s, device=self.var.device, dtype=self.var.compute_dtype)
+        self.WT = dict(qkv=mk(depth, C, 3 * C), proj=mk(depth, C, C), fc1=mk(depth, C, hid), fc2=mk(depth, hid, C), head=mk(C, V), ada=mk(C, n_ada))
         ops.transpose(P['w_qkv'], self.WT['qkv'], depth, 3 * C, C, C)
         ops.transpose(P['w_proj'], self.WT['proj'], depth, C, C, C)
         ops.transpose(P['w_fc1'], self.WT['fc1'], depth, hid, C, C)
         ops.transpose(P['w_fc2'], self.WT['fc2'], depth, C, hid, hid)
         ops.transpose(P['w_head'], self.WT['head'], 1, V, C, C)
-        ops.transpose(P['w_ada'], self.WT['ada'], 1, P['n_ada'], C, C)
+        ops.transpose(P['w_ada'], self.WT['ada'], 1, n_ada, C, C)
         self._wt_gen = self._pack_gen()
 
     def _pack_gen(self):
@@ -287,63 +383,7 @@ class TrainEngine:
 
     def grads(self) -> Dict[str, torch.Tensor]:
         """state_dict key -> gradient view (fp32); a LoRA model: the adapter keys only"""
-        if self._lora is not None:
-            return {k: self.G_lora[o:o + n].view(*shape) for k, (o, n, shape) in self.lora_off.items()}
-        cfg = self.cfg
-        C, depth, V, Vo = cfg.C, cfg.depth, cfg.head_ld, cfg.head_out
-        hid = round(C * cfg.mlp_ratio)
-        so = self.slab_off
-        g: Dict[str, torch.Tensor] = {}
-        for i in range(depth):
-            s = self.G_layers[i]
-            p = f'blocks.{i}.'
-            g[p + 'attn.mat_qkv.weight'] = s[so['w_qkv']:so['w_qkv'] + 3 * C * C].view(3 * C, C)
-            g[p + 'attn.proj.weight'] = s[so['w_proj']:so['w_proj'] + C * C].view(C, C)
-            g[p + 'ffn.fc1.weight'] = s[so['w_fc1']:so['w_fc1'] + hid * C].view(hid, C)
-            g[p + 'ffn.fc2.weight'] = s[so['w_fc2']:so['w_fc2'] + C * hid].view(C, hid)
-            g[p + 'attn.q_bias'] = s[so['b_qkv']:so['b_qkv'] + C]
-            g[p + 'attn.v_bias'] = s[so['b_qkv'] + 2 * C:so['b_qkv'] + 3 * C]
-            g[p + 'attn.proj.bias'] = s[so['b_proj']:so['b_proj'] + C]
-            g[p + 'ffn.fc1.bias'] = s[so['b_fc1']:so['b_fc1'] + hid]
-            g[p + 'ffn.fc2.bias'] = s[so['b_fc2']:so['b_fc2'] + C]
-            if cfg.uses_cos_attn:
-                g[p + 'attn.scale_mul_1H11'] = s[so['scale_mul']:so['scale_mul'] + cfg.H].view(1, cfg.H, 1, 1)
-            n_ada = depth * 6 * C + 2 * C
-            if cfg.sa_block:        # constants in the folded bias (models._pack): [gamma1, gamma2, w1 - 1, w2 - 1, b1, b2]
-                gb = self.G_ada[n_ada * C:][i * 6 * C:(i + 1) * 6 * C]
-                if cfg.layer_scale >= 0:
-                    g[p + 'gamma1'], g[p + 'gamma2'] = gb[0:C], gb[C:2 * C]
-                g[p + 'norm1.weight'], g[p + 'norm2.weight'] = gb[2 * C:3 * C], gb[3 * C:4 * C]
-                g[p + 'norm1.bias'], g[p + 'norm2.bias'] = gb[4 * C:5 * C], gb[5 * C:6 * C]
-            elif cfg.shared_aln:    # folded bias_i = shared bias + ada_gss_i (models._pack): d ada_gss_i = d bias_i
-                g[p + 'ada_gss'] = self.G_ada[n_ada * C:][i * 6 * C:(i + 1) * 6 * C].view(1, 1, 6, C)
-            else:
-                g[p + 'ada_lin.1.weight'] = self.G_ada[:n_ada * C].view(n_ada, C)[i * 6 * C:(i + 1) * 6 * C]
-                g[p + 'ada_lin.1.bias'] = self.G_ada[n_ada * C:][i * 6 * C:(i + 1) * 6 * C]
-        n_ada = depth * 6 * C + 2 * C
-        mo = lambda k: self.G_misc[self.misc_off[k][0]:self.misc_off[k][0] + self.misc_off[k][1]]
-        py = cfg.pyramid
-        if cfg.sa_block:            # head = Sequential(LayerNorm, Linear) (control_var.py:205-207)
-            hb = self.G_ada[n_ada * C:][depth * 6 * C:]
-            g['head.0.weight'], g['head.0.bias'] = hb[:C], hb[C:]
-            g['head.1.weight'] = mo('w_head').view(V, C)[:Vo]; g['head.1.bias'] = mo('b_head')[:Vo]
-        else:
-            g['head_nm.ada_lin.1.weight'] = self.G_ada[:n_ada * C].view(n_ada, C)[depth * 6 * C:]
-            g['head_nm.ada_lin.1.bias'] = self.G_ada[n_ada * C:][depth * 6 * C:]
-            g['head.weight'] = mo('w_head').view(V, C)[:Vo]; g['head.bias'] = mo('b_head')[:Vo]
-        g['word_embed.weight'] = mo('w_we').view(C, cfg.cvae); g['word_embed.bias'] = mo('b_we')
-        g['pos_1LC'] = mo('pos').view(1, py.L, C); g['lvl_embed.weight'] = mo('lvl').view(len(cfg.patch_nums), C)
-        g['pos_start'] = mo('pos_start').view(1, py.first_l, C)
-        g['class_emb.weight'] = mo('class_emb').view(cfg.num_classes + 1, C)
-        if cfg.mask_factor == 2:
-            g['cond_embed.weight'] = mo('cond_embed').view(5, C)
-        if cfg.shared_aln:
-            g['shared_ada_lin.1.weight'] = mo('w_shared').view(6 * C, C); g['shared_ada_lin.1.bias'] = mo('b_shared')
-        if cfg.type_pos:
-            g['type_embed.weight'] = mo('type').view(cfg.mask_factor, C)
-        if cfg.separator:
-            g['special_embed.weight'] = mo('special').view(cfg.n_special, C)
-        return g
+        return {k: buf[o:o + math.prod(shape)].view(shape) for k, (buf, o, shape) in self.grad_views.items()}
 
     # ---------------------------------------------------------------- forward + backward
     @torch.no_grad()
@@ -355,7 +395,7 @@ class TrainEngine:
         1 / M scale are this micro-batch's own; the 1 / N of a window of N belongs to the optimizer's gradient scale (FusedAdamW.step)."""
         self.forward_train(label_B, x_wo_first, cond_type, drop_seed, mask_first)
         dev = self.var.device
-        M, V = self.M, self.cfg.head_ld
+        M, V = self.M, self.V
         tg = targets.to(device=dev, dtype=torch.int32).contiguous().view(-1)
         if ignore_mask is not None:                                  # train_control_var_hpu.py:233-237
             w = ignore_mask.to(device=dev, dtype=torch.float32).contiguous().view(-1)
@@ -373,21 +413,13 @@ class TrainEngine:
         """teacher-forced forward that keeps every block's activations; returns logits (B*L, V) fp32"""
         cfg, var = self.cfg, self.var
         P = var._pack(check=True, base=True)
-        py, C, depth, V, H = cfg.pyramid, cfg.C, cfg.depth, cfg.head_ld, cfg.H
-        L, fl = py.L, py.first_l
+        C, depth, V, L, hid, n_ada, ah, H, eps = self.C, self.depth, self.V, self.L, self.hid, self.n_ada, self.ah, cfg.H, self.eps
         dev, T = var.device, var.compute_dtype
         B = x_wo_first.shape[0]
         self._setup(B)
         if self._wt_gen != self._pack_gen():       # the W^T copies follow the packed weights (any optimizer, manual edits, resume)
             self._transposed_weights()
-        lo = self._lora
-        M, Mp = self.M, self.Mp
-        hid = P['w_fc1'].shape[1]
-        n_ada = P['n_ada']
-        eps = cfg.norm_eps
-        from .spec import attention_levels
-        lvl_end, holes = attention_levels(cfg)
-        scale = float(cfg.attn_scale)
+        lo, M = self._lora, self.M
         from .models import _check_index_range
         _check_index_range(label_B, 0, cfg.num_classes, 'label_B')
         labels = label_B.to(dev)
@@ -410,10 +442,13 @@ class TrainEngine:
             keep = 1 - dpr
             dp1 = (torch.rand(depth, B, device=dev, generator=g) < keep).float() / keep
             dp2 = (torch.rand(depth, B, device=dev, generator=g) < keep).float() / keep
-        if lo is not None:                                            # adapter dropout: active in train() only; drop_seed seeds it too
+        if lo is None:          # the leaf that launches an adapted linear (proj, fc1, fc2, the adaLN generator): the GEMM on the packed weight
+            linear = lambda kind, i, x, out, M, N, K, **epi: ops.gemm(x, P['w_' + kind], out, M=M, N=N, K=K, w_off=i * N * K, **epi)
+        else:                   # adapter dropout: active in train() only; drop_seed seeds it too
             self._lp = lo['dropout'] if var.training else 0.0
             self._lseed = drop_seed if drop_seed is not None else int(torch.empty((), dtype=torch.int64).random_().item())
             self._lora_pack()
+            linear = self._lora_linear
         # ---- forward
         x0 = self.Xs[0]
         cond = torch.empty(B, C, device=dev, dtype=torch.float32)
@@ -427,36 +462,92 @@ class TrainEngine:
         cs = torch.empty(B, C, device=dev, dtype=T)
         ops.silu_cast(cond, cs)
         ada = torch.empty(B, n_ada, device=dev, dtype=torch.float32)
-        if lo is None:
-            ops.gemm(cs, P['w_ada'], ada, M=B, N=n_ada, K=C, bias=P['b_ada'])
-        else:
-            self._lora_ada_forward(cs, ada, P, B)
+        linear('ada', 0, cs, ada, B, n_ada, C, bias=P['b_ada'])
+        ln = _ln_rows(C)
+        ldh = self.Xin['fc2'][1]                                      # fc1 writes fc2's operand in place: with fc2's row stride
         for i in range(depth):
             a0 = i * 6 * C
-            x = self.Xs[i]
-            _ln_rows(C)(x, ada, a0 + 2 * C, a0 + 4 * C, n_ada, L, self.U[i], M, C, eps)
+            x, x1 = self.Xs[i], self.X1s[i]
+            ln(x, ada, a0 + 2 * C, a0 + 4 * C, n_ada, L, self.U[i], M, C, eps)
             ops.gemm(self.U[i], P['w_qkv'], self.arena[i], M=M, N=3 * C, K=C, w_off=i * 3 * C * C, bias=P['b_qkv'][i])
             if cfg.uses_cos_attn:
                 ops.cos_qk_norm(self.arena[i], B, H, L, 0, L, P['scale_mul'], sm_off=i * H, norms=self.NORMS[i])
-            ops.attention(self.arena[i], self.O[i], B, H, L, 0, L, scale, lvl_end, lse=self.LSE[i], holes=holes)
-            if lo is not None:
-                self._lora_block_forward(i, ada, P, dp1, dp2)
-                continue
+            ops.attention(self.arena[i], self.O[i], B, H, L, 0, L, self.scale, self.lvl_end, lse=self.LSE[i], holes=self.holes)
             # x1 = x + (gamma1 * keep1) * proj(o): gate / DropPath scale / residual in the GEMM epilogue; the branch output the backward
             # needs (d gamma1 = sum dx * f) is stored next to it
-            ops.gemm(self.O[i], P['w_proj'], self.X1s[i], M=M, N=C, K=C, w_off=i * C * C, bias=P['b_proj'][i], gate=ada, ldg=n_ada, gate_rows=L,
-                     gate_off=a0, gate_scale=dp1[i].contiguous() if dp1 is not None else None, residual=x, pre_act=self.F1[i])
-            _ln_rows(C)(self.X1s[i], ada, a0 + 3 * C, a0 + 5 * C, n_ada, L, self.U2[i], M, C, eps)
+            linear('proj', i, self.O[i], x1, M, C, C, bias=P['b_proj'][i], gate=ada, ldg=n_ada, gate_rows=L, gate_off=a0,
+                   gate_scale=dp1[i].contiguous() if dp1 is not None else None, residual=x, pre_act=self.F1[i])
+            ln(x1, ada, a0 + 3 * C, a0 + 5 * C, n_ada, L, self.U2[i], M, C, eps)
             # fc1 with the GELU in its epilogue; the pre-activation the backward needs is stored alongside (no separate gelu pass)
-            ops.gemm(self.U2[i], P['w_fc1'], self.Hh[i], M=M, N=hid, K=C, w_off=i * hid * C, bias=P['b_fc1'][i], act=ACT_GELU_TANH,
-                     pre_act=self.A[i])
-            ops.gemm(self.Hh[i], P['w_fc2'], self.Xs[i + 1], M=M, N=C, K=hid, w_off=i * C * hid, bias=P['b_fc2'][i], gate=ada, ldg=n_ada, gate_rows=L,
-                     gate_off=a0 + C, gate_scale=dp2[i].contiguous() if dp2 is not None else None, residual=self.X1s[i], pre_act=self.F2[i])
-        ah = depth * 6 * C
-        _ln_rows(C)(self.Xs[depth], ada, ah, ah + C, n_ada, L, self.UH, M, C, eps)
+            linear('fc1', i, self.U2[i], self.Hh[i], M, hid, C, ldc=ldh, bias=P['b_fc1'][i], act=ACT_GELU_TANH, pre_act=self.A[i])
+            linear('fc2', i, self.Hh[i], self.Xs[i + 1], M, C, hid, bias=P['b_fc2'][i], gate=ada, ldg=n_ada, gate_rows=L, gate_off=a0 + C,
+                   gate_scale=dp2[i].contiguous() if dp2 is not None else None, residual=x1, pre_act=self.F2[i])
+        ln(self.Xs[depth], ada, ah, ah + C, n_ada, L, self.UH, M, C, eps)
         ops.gemm(self.UH, P['w_head'], self.logits, M=M, N=V, K=C, bias=P['b_head'])
         self._saved = dict(ada=ada, cs=cs, cond=cond, labels=labels, types=types, tok=tok, dp1=dp1, dp2=dp2, B=B)
         return self.logits
+
+    def backward(self, accumulate: bool = False):
+        """backward from self.dlogits (compute dtype, (B*L, V)) through head, blocks, adaLN generator and - full model - embeddings.
+        accumulate: every gradient element becomes fp32(old + plain).  The weight-gradient GEMMs, bias sums, the adapter gradients and
+        the word-embedding gradient add at their producer; the adaLN generator's gradient and the small embedding gradients - several of
+        which are DERIVED from other entries of the gradient buffer - are computed on staging copies exactly as in a plain step and then
+        added.  A LoRA model: data gradients through the frozen base plus the adapter gradients into self.G_lora."""
+        cfg = self.cfg
+        acc = bool(accumulate)
+        full = self._lora is None
+        grads_of = self._full_grads_of if full else self._lora_grads_of       # the leaf behind the data-gradient GEMM of a linear
+        ready = self.reducer.ready if self.reducer is not None else (lambda idx: None)
+        P = self.var._pack(base=True)
+        C, depth, V, L, M, hid, n_ada, ah, H, eps, ws = self.C, self.depth, self.V, self.L, self.M, self.hid, self.n_ada, self.ah, cfg.H, self.eps, self.ws
+        ada, dp1, dp2, B = (self._saved[k] for k in ('ada', 'dp1', 'dp2', 'B'))
+        # ---- head
+        self.dada.zero_()
+        ops.gemm(self.dlogits, self.WT['head'], self.DU, M=M, N=C, K=V)
+        if full:                        # head and qkv carry no adapter: they have a parameter gradient in the full model only
+            mo = self.misc_off
+            self._wgrad(self.dlogits, V, self.UH, C, self.G_misc, mo['w_head'][0], mo['b_head'][0], acc)
+        ops.ln_modulate_bwd(self.Xs[depth], self.DU, ada, ah, n_ada, L, None, self.dX, self.dada, ah, ah + C, n_ada, M, C, eps, ws)
+        # ---- blocks
+        for i in reversed(range(depth)):
+            a0 = i * 6 * C
+            # FFN branch.  Full model: dH = (dF W2) * gelu'(A) in one GEMM; LoRA: cvar_lora_dx applies GELU' after adding the branch's share
+            gelu = dict(act=ACT_GELU_GRAD, aux=self.A[i]) if full else {}
+            ops.gated_grad(self.dX, self.F2[i], ada, a0 + C, n_ada, dp2[i].contiguous() if dp2 is not None else None, self.DF, self.dada, a0 + C, n_ada, B, L, C, ws)
+            ops.gemm(self.DF, self.WT['fc2'], self.DH, M=M, N=hid, K=C, w_off=i * hid * C, **gelu)
+            grads_of(i, 'fc2', self.DF, C, hid, acc)
+            ops.gemm(self.DH, self.WT['fc1'], self.DU, M=M, N=C, K=hid, w_off=i * C * hid)
+            grads_of(i, 'fc1', self.DH, hid, C, acc)
+            ops.ln_modulate_bwd(self.X1s[i], self.DU, ada, a0 + 3 * C, n_ada, L, self.dX, self.dX, self.dada, a0 + 3 * C, a0 + 5 * C, n_ada, M, C, eps, ws)
+            # attention branch
+            ops.gated_grad(self.dX, self.F1[i], ada, a0, n_ada, dp1[i].contiguous() if dp1 is not None else None, self.DF, self.dada, a0, n_ada, B, L, C, ws)
+            ops.gemm(self.DF, self.WT['proj'], self.DU, M=M, N=C, K=C, w_off=i * C * C)
+            grads_of(i, 'proj', self.DF, C, C, acc)
+            ops.attention_bwd(self.arena[i], self.O[i], self.DU, self.LSE[i], self.DQKV, ws, B, H, L, L, self.scale, self.lvl_end, holes=self.holes)
+            if cfg.uses_cos_attn:           # normalisation + learned temperature of basic_var.py:99-104 (a parameter of the base: frozen under LoRA)
+                ops.cos_qk_norm_bwd(self.arena[i], self.DQKV, B, H, L, L, P['scale_mul'], self.NORMS[i], self.DSM, sm_off=i * H)
+                if full:
+                    ops.colsum(self.DSM, H, self.G_layers, M, H, ws, accumulate=acc, out_off=i * self.slab + self.slab_off['scale_mul'])
+            ops.gemm(self.DQKV, self.WT['qkv'], self.DU, M=M, N=C, K=3 * C, w_off=i * C * 3 * C)
+            if full:
+                grads_of(i, 'qkv', self.DQKV, 3 * C, C, acc)      # the k-bias third is unused (zero_k_bias is a buffer)
+            ops.ln_modulate_bwd(self.Xs[i], self.DU, ada, a0 + 2 * C, n_ada, L, self.dX, self.dX, self.dada, a0 + 2 * C, a0 + 4 * C, n_ada, M, C, eps, ws)
+            ready(i)
+        # ---- adaLN parameter generator, then - full model - the embeddings (dX now holds d loss / d x0)
+        if full:
+            dcond, Gm = self._ada_grads_full(acc)
+            ready(depth)
+            self._embedding_grads(dcond, Gm, acc)
+            ready(depth + 1)
+        else:
+            self._ada_grads_lora(acc)
+            ready(depth)
+
+    # ---------------------------------------------------------------- full model: weight gradients, generator and embedding tail
+    def _full_grads_of(self, i, kind, dY, n_out, k_in, acc):
+        """weight and bias gradient of linear `kind` of block i into its layer's slab"""
+        go, so = i * self.slab, self.slab_off
+        self._wgrad(dY, n_out, self.Xin[kind][0][i], k_in, self.G_layers, go + so['w_' + kind], go + so['b_' + kind], acc)
 
     @torch.no_grad()
     def _wgrad(self, dY, n_out: int, X, k_in: int, G, w_off: int, b_off=None, acc: bool = False):
@@ -481,65 +572,12 @@ class TrainEngine:
         if b_off is not None:
             ops.rowsum(self.TA, Mp, G, n_out, M, accumulate=acc, out_off=b_off)
 
-    def backward(self, accumulate: bool = False):
-        """backward from self.dlogits (compute dtype, (B*L, V)) through head, blocks, adaLN generator and embeddings.  accumulate: every
-        gradient element becomes fp32(old + plain).  The weight-gradient GEMMs, bias sums and the word-embedding gradient add at their
-        producer; the adaLN generator's gradient and the small embedding gradients - several of which are DERIVED from other entries of
-        the gradient buffer (lvl / type from pos, pos_start a copy, w_shared / b_shared sums over G_ada, class_emb / cond_embed zeroed
-        and scattered into) - are computed on staging copies exactly as in a plain step and then added."""
-        cfg, var = self.cfg, self.var
-        acc = bool(accumulate)
-        if self._lora is not None:
-            return self._backward_lora(acc)
-        P = var._pack()
-        py, C, depth, V, H = cfg.pyramid, cfg.C, cfg.depth, cfg.head_ld, cfg.H
-        L, fl = py.L, py.first_l
-        dev, T = var.device, var.compute_dtype
-        sv = self._saved
-        ada, cs, cond, labels, types, tok, dp1, dp2, B = (sv[k] for k in ('ada', 'cs', 'cond', 'labels', 'types', 'tok', 'dp1', 'dp2', 'B'))
-        M, Mp = self.M, self.Mp
-        hid = P['w_fc1'].shape[1]
-        n_ada = P['n_ada']
-        eps = cfg.norm_eps
-        from .spec import attention_levels
-        lvl_end, holes = attention_levels(cfg)
-        scale = float(cfg.attn_scale)
-        ah = depth * 6 * C
-        # ---- backward: head
-        TA, TB, ws = self.TA, self.TB, self.ws
-        so = self.slab_off
-        mo = self.misc_off
-        self.dada.zero_()
-        ops.gemm(self.dlogits, self.WT['head'], self.DU, M=M, N=C, K=V)
-        self._wgrad(self.dlogits, V, self.UH, C, self.G_misc, mo['w_head'][0], mo['b_head'][0], acc)
-        ops.ln_modulate_bwd(self.Xs[depth], self.DU, ada, ah, n_ada, L, None, self.dX, self.dada, ah, ah + C, n_ada, M, C, eps, ws)
-        # ---- backward: blocks
-        for i in reversed(range(depth)):
-            a0 = i * 6 * C
-            G = self.G_layers
-            go = i * self.slab
-            # FFN branch
-            ops.gated_grad(self.dX, self.F2[i], ada, a0 + C, n_ada, dp2[i].contiguous() if dp2 is not None else None, self.DF, self.dada, a0 + C, n_ada, B, L, C, ws)
-            ops.gemm(self.DF, self.WT['fc2'], self.DH, M=M, N=hid, K=C, w_off=i * hid * C, act=ACT_GELU_GRAD, aux=self.A[i])   # dH = (dF W2) * gelu'(A)
-            self._wgrad(self.DF, C, self.Hh[i], hid, G, go + so['w_fc2'], go + so['b_fc2'], acc)
-            ops.gemm(self.DH, self.WT['fc1'], self.DU, M=M, N=C, K=hid, w_off=i * C * hid)
-            self._wgrad(self.DH, hid, self.U2[i], C, G, go + so['w_fc1'], go + so['b_fc1'], acc)
-            ops.ln_modulate_bwd(self.X1s[i], self.DU, ada, a0 + 3 * C, n_ada, L, self.dX, self.dX, self.dada, a0 + 3 * C, a0 + 5 * C, n_ada, M, C, eps, ws)
-            # attention branch
-            ops.gated_grad(self.dX, self.F1[i], ada, a0, n_ada, dp1[i].contiguous() if dp1 is not None else None, self.DF, self.dada, a0, n_ada, B, L, C, ws)
-            ops.gemm(self.DF, self.WT['proj'], self.DU, M=M, N=C, K=C, w_off=i * C * C)
-            self._wgrad(self.DF, C, self.O[i], C, G, go + so['w_proj'], go + so['b_proj'], acc)
-            ops.attention_bwd(self.arena[i], self.O[i], self.DU, self.LSE[i], self.DQKV, ws, B, H, L, L, scale, lvl_end, holes=holes)
-            if cfg.uses_cos_attn:           # normalisation + learned temperature of basic_var.py:99-104
-                ops.cos_qk_norm_bwd(self.arena[i], self.DQKV, B, H, L, L, P['scale_mul'], self.NORMS[i], self.DSM, sm_off=i * H)
-                ops.colsum(self.DSM, H, G, M, H, ws, accumulate=acc, out_off=go + so['scale_mul'])
-            ops.gemm(self.DQKV, self.WT['qkv'], self.DU, M=M, N=C, K=3 * C, w_off=i * C * 3 * C)
-            self._wgrad(self.DQKV, 3 * C, self.U[i], C, G, go + so['w_qkv'], go + so['b_qkv'], acc)      # the k-bias third is unused (zero_k_bias is a buffer)
-            ops.ln_modulate_bwd(self.Xs[i], self.DU, ada, a0 + 2 * C, n_ada, L, self.dX, self.dX, self.dada, a0 + 2 * C, a0 + 4 * C, n_ada, M, C, eps, ws)
-            if self.reducer is not None:
-                self.reducer.ready(i)
-        # ---- backward: adaLN parameter generator (one GEMM for all blocks + head)
-        Bp = self.Bp
+    def _ada_grads_full(self, acc):
+        """gradient of the adaLN parameter generator (one GEMM for all blocks + head) -> (d cond, Gm: where this micro-batch's G_misc values go).
+        accumulating: they go to staging copies (Ga, Gm) - what is derived from them must be derived from them, not from the window's sum"""
+        cfg, dev, T = self.cfg, self.var.device, self.var.compute_dtype
+        C, depth, n_ada, Bp, ws, mo = self.C, self.depth, self.n_ada, self.Bp, self.ws, self.misc_off
+        cs, cond, B = (self._saved[k] for k in ('cs', 'cond', 'B'))
         dada_T = self.dada.to(T)
         dsilu = torch.empty(B, C, device=dev, dtype=torch.float32)
         ops.gemm(dada_T, self.WT['ada'], dsilu, M=B, N=C, K=n_ada)
@@ -547,7 +585,6 @@ class TrainEngine:
         tB = torch.zeros(C, Bp, device=dev, dtype=T)
         ops.transpose(dada_T, tA, 1, B, n_ada, n_ada, ld_out=Bp)
         ops.transpose(cs, tB, 1, B, C, C, ld_out=Bp)
-        # accumulating: this micro-batch's values go to staging copies (Ga, Gm) - what is derived below must be derived from them, not from the window's sum
         Ga = self._stage('ada', self.G_ada.numel()) if acc else self.G_ada
         Gm = self._stage('misc', self.G_misc.numel()) if acc else self.G_misc
         ops.gemm(tA, tB, Ga, M=n_ada, N=C, K=Bp)
@@ -559,9 +596,16 @@ class TrainEngine:
             ops.add_inplace(self.G_ada, Ga, self.G_ada.numel())
         dcond = torch.empty(B, C, device=dev, dtype=torch.float32)
         ops.silu_bwd(cond, dsilu, dcond)
-        if self.reducer is not None:
-            self.reducer.ready(depth)
-        # ---- backward: embeddings (dX now holds d loss / d x0)
+        return dcond, Gm
+
+    def _embedding_grads(self, dcond, Gm, acc):
+        """the small embedding gradients from self.dX = d loss / d x0 and d cond.  Several are DERIVED from other entries of the gradient buffer
+        (lvl / type from pos, pos_start a copy, class_emb / cond_embed zeroed and scattered into): all of it is computed in Gm - self.G_misc,
+        or its staging copy when accumulating, which is then added"""
+        cfg, dev = self.cfg, self.var.device
+        py, C, L, ws, mo = cfg.pyramid, self.C, self.L, self.ws, self.misc_off
+        fl = py.first_l
+        labels, types, tok, B = (self._saved[k] for k in ('labels', 'types', 'tok', 'B'))
         ops.colsum(self.dX, L * C, Gm, B, L * C, ws, out_off=mo['pos'][0])
         for k, (b0, e0) in enumerate(zip(py.begin, py.end)):
             ops.colsum(Gm, C, Gm, e0 - b0, C, ws, a_off=mo['pos'][0] + b0 * C, out_off=mo['lvl'][0] + k * C)
@@ -594,244 +638,6 @@ class TrainEngine:
         if acc:         # misc layout: [w_head | b_head | w_we | b_we | pos ... ]: the head added at its GEMM, word_embed at its kernel unless it took the slow path
             o0 = mo['w_we'][0] if we_staged else mo['pos'][0]
             ops.add_inplace(self.G_misc, Gm, self.G_misc.numel() - o0, y_off=o0, x_off=o0)
-        if self.reducer is not None:
-            self.reducer.ready(depth + 1)
-
-    # ---------------------------------------------------------------- LoRA (controlvar_amd/lora.py; DESIGN.md "LoRA")
-    # The base weights are frozen: their gradients are neither computed nor stored.  Each target's rank-r branch enters the base
-    # GEMM - and so its fused epilogue (bias, gate, DropPath scale, residual, GELU, pre_act) - by K-augmentation: the operand [x | u]
-    # (u = s drop(x) A^T from cvar_lora_down, zero padding up to a 128-byte row step) against the packed weight [W | B | 0].  The
-    # backward runs the base data-gradient GEMM, then cvar_lora_down for du = dY B, cvar_lora_dx for the branch's share of dx, and
-    # cvar_lora_wgrad for dB = dY^T u and dA = s du^T drop(x).  Targets: tag 4 i + (0 proj, 1 fc1, 2 fc2, 3 ada_lin), head_nm 4 depth + 3.
-    def _setup_lora(self, B: int, lora):
-        key = (B, id(lora))
-        if self._B == key:
-            return
-        cfg, var = self.cfg, self.var
-        dev, T = var.device, var.compute_dtype
-        C, depth, V = cfg.C, cfg.depth, cfg.head_ld
-        L = cfg.pyramid.L
-        M = B * L
-        hid = round(C * cfg.mlp_ratio)
-        n_ada = depth * 6 * C + 2 * C
-        r = lora['r']
-        rp = 128 // torch.tensor([], dtype=T).element_size()          # augmented K step: keeps cvar_gemm on its K-multiple-of-128-bytes path
-        self._lora, self.r, self.rp = lora, r, rp
-        self.M, self.Mp, self.Bp = M, _pad8(M), _pad8(B)
-        self.Kx = -(-(depth + 1) * 16 // rp) * rp                     # [cs | u_0 ... u_depth] columns beyond C
-        f32 = dict(device=dev, dtype=torch.float32)
-        tT = dict(device=dev, dtype=T)
-        self.Xs = torch.empty(depth + 1, M, C, **f32)
-        self.X1s = torch.empty(depth, M, C, **f32)
-        self.U = torch.empty(depth, M, C, **tT); self.O = torch.empty(depth, M, C, **tT)
-        self.F1 = torch.empty(depth, M, C, **tT); self.U2 = torch.empty(M, C, **tT); self.F2 = torch.empty(depth, M, C, **tT)
-        self.Oa = torch.zeros(depth, M, C + rp, **tT)               # [o | u_proj | 0]
-        self.U2a = torch.zeros(depth, M, C + rp, **tT)              # [u2 | u_fc1 | 0]
-        self.Hha = torch.zeros(depth, M, hid + rp, **tT)            # [gelu(a) | u_fc2 | 0]
-        self.Aa = torch.empty(depth, M, hid + rp, **tT)             # fc1 pre-activation (row stride of the fc1 output)
-        self.csa = torch.zeros(B, C + self.Kx, **tT)
-        self.arena = torch.empty(depth, B, L, 3 * C, **tT)
-        self.LSE = torch.empty(depth, B, cfg.H, L, **f32)
-        self.NORMS = torch.empty(depth, B, L, cfg.H, 2, **f32) if cfg.uses_cos_attn else None
-        self.DSM = torch.empty(M, cfg.H, **f32) if cfg.uses_cos_attn else None
-        self.UH = torch.empty(M, C, **tT)
-        self.logits = torch.empty(M, V, **f32)
-        self.loss_tok = torch.empty(M, **f32)
-        self.dlogits = torch.empty(M, V, **tT)
-        self.dX = torch.empty(M, C, **f32)
-        self.DF = torch.empty(M, C, **tT); self.DU = torch.empty(M, C, **tT)
-        self.DH = torch.empty(M, hid, **tT)
-        self.DQKV = torch.empty(B, L, 3 * C, **tT)
-        self.DUr = torch.empty(M, 16, **tT)
-        self.DUa = torch.empty(B, 16, **tT)
-        self.ncode = len(cfg.pyramid.code_positions()) - cfg.pyramid.first_l
-        self.dada = torch.zeros(B, n_ada, **f32)
-        self.ws = torch.empty(max(ops.train_ws_floats(M, B, C), 64 * max(hid, 3 * C, V, n_ada), L * C, B * cfg.H * L) + 16, **f32)
-        self.lws = torch.empty(max(ops.lora_wgrad_ws_floats(M, hid), ops.lora_wgrad_ws_floats(M, C), ops.lora_wgrad_ws_floats(B, 6 * C)), **f32)
-        # adapter gradient slabs: one per layer [proj A, B | fc1 A, B | fc2 A, B], then every ada_lin adapter (the all-reduce buckets)
-        self.lora_off = {}
-        o = 0
-        dims = dict(proj=(C, C), fc1=(C, hid), fc2=(hid, C))
-        mods = (('proj', 'attn.proj'), ('fc1', 'ffn.fc1'), ('fc2', 'ffn.fc2'))
-        bounds = []
-        for i in range(depth):
-            for kind, name in mods:
-                k_in, n_out = dims[kind]
-                for ab, shape in (('A', (r, k_in)), ('B', (n_out, r))):
-                    self.lora_off[f'blocks.{i}.{name}.lora_{ab}.default.weight'] = (o, shape[0] * shape[1], shape)
-                    o += shape[0] * shape[1]
-            bounds.append(o)
-        for t in range(depth + 1):
-            n_out = 6 * C if t < depth else 2 * C
-            name = f'blocks.{t}.ada_lin.1' if t < depth else 'head_nm.ada_lin.1'
-            for ab, shape in (('A', (r, C)), ('B', (n_out, r))):
-                self.lora_off[f'{name}.lora_{ab}.default.weight'] = (o, shape[0] * shape[1], shape)
-                o += shape[0] * shape[1]
-        if set(self.lora_off) != {n for n, p in var.named_parameters() if p.requires_grad}:
-            raise RuntimeError('LoRA: the trainable parameters are not exactly the adapters of add_lora')
-        if self._grads_key != ('lora', id(lora)):                  # once per adapter state, whatever the batch size (a window accumulates into it)
-            self.G_lora = torch.zeros(o, **f32)
-            starts = [0] + bounds
-            self.buckets = [self.G_lora[starts[i]:starts[i + 1]] for i in range(depth)] + [self.G_lora[bounds[-1]:]]
-            self._grads_key = ('lora', id(lora))
-        self._aug = None
-        self._B = key
-        self._transposed_weights()
-
-    def _lora_pack(self):
-        """operands of the adapter branch in the compute dtype: A (16 rows, zero beyond r), B^T (16 rows) per target, and the K-augmented
-        GEMM weights [W | B | 0] (base part copied once per base pack, the B columns at every forward)"""
-        from .lora import adapters
-        var, cfg, lo = self.var, self.cfg, self._lora
-        P = var._pack(base=True)
-        T, dev = var.compute_dtype, var.device
-        C, depth, r, rp = cfg.C, cfg.depth, self.r, self.rp
-        hid = P['w_fc1'].shape[1]
-        n_ada = P['n_ada']
-        ad = adapters(var)
-        names = dict(proj='attn.proj', fc1='ffn.fc1', fc2='ffn.fc2')
-        if self._aug is None or self._aug[0] is not P:
-            W = {}
-            for kind, (n_out, k_in) in (('proj', (C, C)), ('fc1', (hid, C)), ('fc2', (C, hid))):
-                w = torch.zeros(depth, n_out, k_in + rp, device=dev, dtype=T)
-                w[:, :, :k_in] = P['w_' + kind]
-                W[kind] = w
-            w = torch.zeros(n_ada, C + self.Kx, device=dev, dtype=T)
-            w[:, :C] = P['w_ada']
-            W['ada'] = w
-            self._aug = (P, W)
-        W = self._aug[1]
-        self.Wa = W
-        self.LA, self.LBT = {}, {}
-        for kind, (n_out, k_in) in (('proj', (C, C)), ('fc1', (hid, C)), ('fc2', (C, hid))):
-            As = torch.stack([ad[f'blocks.{i}.{names[kind]}'][0] for i in range(depth)])          # (depth, r, k_in)
-            Bs = torch.stack([ad[f'blocks.{i}.{names[kind]}'][1] for i in range(depth)])          # (depth, n_out, r)
-            self.LA[kind] = torch.zeros(depth, 16, k_in, device=dev, dtype=T)
-            self.LA[kind][:, :r] = As
-            self.LBT[kind] = torch.zeros(depth, 16, n_out, device=dev, dtype=T)
-            self.LBT[kind][:, :r] = Bs.transpose(1, 2)
-            W[kind][:, :, k_in:k_in + r] = Bs
-        tn = [f'blocks.{t}.ada_lin.1' for t in range(depth)] + ['head_nm.ada_lin.1']
-        self.LA['ada'] = torch.zeros(depth + 1, 16, C, device=dev, dtype=T)
-        self.LA['ada'][:, :r] = torch.stack([ad[n][0] for n in tn])
-        self.LBT['ada'] = torch.zeros(depth + 1, 16, 6 * C, device=dev, dtype=T)
-        for t, n in enumerate(tn):
-            Bt = ad[n][1]
-            self.LBT['ada'][t, :r, :Bt.shape[0]] = Bt.t()
-            W['ada'][t * 6 * C:t * 6 * C + Bt.shape[0], C + 16 * t:C + 16 * t + r] = Bt
-
-    def _tag(self, i: int, kind: str) -> int:
-        return 4 * i + ('proj', 'fc1', 'fc2', 'ada').index(kind)
-
-    def _lora_ada_forward(self, cs, ada, P, B):
-        C, depth, lo = self.cfg.C, self.cfg.depth, self._lora
-        ld = C + self.Kx
-        for t in range(depth + 1):
-            ops.lora_down(cs, self.LA['ada'][t], self.csa, M=B, K=C, r=self.r, scale=lo['scale'], p=self._lp, seed=self._lseed,
-                          tag=self._tag(t, 'ada'), ldu=ld, u_off=C + 16 * t, x_copy=self.csa if t == 0 else None, ld_copy=ld)
-        ops.gemm(self.csa, self.Wa['ada'], ada, M=B, N=P['n_ada'], K=ld, lda=ld, ldw=ld, bias=P['b_ada'])
-
-    def _lora_block_forward(self, i, ada, P, dp1, dp2):
-        cfg, lo = self.cfg, self._lora
-        C, M, L, r, rp = cfg.C, self.M, cfg.pyramid.L, self.r, self.rp
-        hid = P['w_fc1'].shape[1]
-        n_ada = P['n_ada']
-        eps = cfg.norm_eps
-        s, p, seed = lo['scale'], self._lp, self._lseed
-        a0 = i * 6 * C
-        x = self.Xs[i]
-        kc, kh = C + rp, hid + rp
-        ops.lora_down(self.O[i], self.LA['proj'][i], self.Oa[i], M=M, K=C, r=r, scale=s, p=p, seed=seed, tag=self._tag(i, 'proj'), ldu=kc, u_off=C,
-                      x_copy=self.Oa[i], ld_copy=kc)
-        ops.gemm(self.Oa[i], self.Wa['proj'], self.X1s[i], M=M, N=C, K=kc, lda=kc, ldw=kc, w_off=i * C * kc, bias=P['b_proj'][i], gate=ada, ldg=n_ada,
-                 gate_rows=L, gate_off=a0, gate_scale=dp1[i].contiguous() if dp1 is not None else None, residual=x, pre_act=self.F1[i])
-        _ln_rows(C)(self.X1s[i], ada, a0 + 3 * C, a0 + 5 * C, n_ada, L, self.U2, M, C, eps)
-        ops.lora_down(self.U2, self.LA['fc1'][i], self.U2a[i], M=M, K=C, r=r, scale=s, p=p, seed=seed, tag=self._tag(i, 'fc1'), ldu=kc, u_off=C,
-                      x_copy=self.U2a[i], ld_copy=kc)
-        ops.gemm(self.U2a[i], self.Wa['fc1'], self.Hha[i], M=M, N=hid, K=kc, lda=kc, ldw=kc, ldc=kh, w_off=i * hid * kc, bias=P['b_fc1'][i],
-                 act=ACT_GELU_TANH, pre_act=self.Aa[i])
-        ops.lora_down(self.Hha[i], self.LA['fc2'][i], self.Hha[i], M=M, K=hid, r=r, scale=s, p=p, seed=seed, tag=self._tag(i, 'fc2'), ldx=kh, ldu=kh,
-                      u_off=hid)
-        ops.gemm(self.Hha[i], self.Wa['fc2'], self.Xs[i + 1], M=M, N=C, K=kh, lda=kh, ldw=kh, w_off=i * C * kh, bias=P['b_fc2'][i], gate=ada, ldg=n_ada,
-                 gate_rows=L, gate_off=a0 + C, gate_scale=dp2[i].contiguous() if dp2 is not None else None, residual=self.X1s[i], pre_act=self.F2[i])
-
-    def _lora_grads_of(self, i, kind, name, dY, n_out, x, k_in, ldx, x_off_u, aux=None, ldaux=0, acc=False):
-        """du = dY B; dx (self.DU / self.DH, in place) += branch share (* gelu'(aux)); dB = dY^T u; dA = s du^T drop(x).  x: the augmented
-        saved input [x | u] with row stride ldx, u at column x_off_u"""
-        lo, M, r = self._lora, self.M, self.r
-        s, p, seed, tag = lo['scale'], self._lp, self._lseed, self._tag(i, kind)
-        G = self.G_lora
-        oA = self.lora_off[f'{name}.lora_A.default.weight'][0]
-        oB = self.lora_off[f'{name}.lora_B.default.weight'][0]
-        ops.lora_down(dY, self.LBT[kind][i], self.DUr, M=M, K=n_out, r=r, scale=1.0, ldu=16)
-        dx = self.DH if kind == 'fc2' else self.DU
-        ops.lora_dx(dx, self.DUr, self.LA[kind][i], M=M, K=k_in, r=r, scale=s, p=p, seed=seed, tag=tag, lddu=16, aux=aux, ldaux=ldaux)
-        ops.lora_wgrad(dY, x, G, self.lws, M=M, N=n_out, r=r, ldz=ldx, z_off=x_off_u, out_off=oB, accumulate=acc)
-        ops.lora_wgrad(x, self.DUr, G, self.lws, M=M, N=k_in, r=r, scale=s, p=p, seed=seed, tag=tag, ldy=ldx, ldz=16, out_off=oA, os_n=1, os_j=k_in,
-                       accumulate=acc)
-
-    def _backward_lora(self, acc: bool = False):
-        """backward of a LoRA model: data gradients through the frozen base (no weight-gradient GEMMs, no embedding gradients) plus
-        the adapter gradients into self.G_lora (acc: added to it by cvar_lora_wgrad_acc)"""
-        cfg, var = self.cfg, self.var
-        P = var._pack(base=True)
-        py, C, depth, V, H = cfg.pyramid, cfg.C, cfg.depth, cfg.head_ld, cfg.H
-        L = py.L
-        T = var.compute_dtype
-        sv = self._saved
-        ada, dp1, dp2, B = (sv[k] for k in ('ada', 'dp1', 'dp2', 'B'))
-        M, r, rp = self.M, self.r, self.rp
-        hid = P['w_fc1'].shape[1]
-        n_ada = P['n_ada']
-        eps = cfg.norm_eps
-        from .spec import attention_levels
-        lvl_end, holes = attention_levels(cfg)
-        scale = float(cfg.attn_scale)
-        ah = depth * 6 * C
-        ws = self.ws
-        kc, kh = C + rp, hid + rp
-        self.dada.zero_()
-        ops.gemm(self.dlogits, self.WT['head'], self.DU, M=M, N=C, K=V)
-        ops.ln_modulate_bwd(self.Xs[depth], self.DU, ada, ah, n_ada, L, None, self.dX, self.dada, ah, ah + C, n_ada, M, C, eps, ws)
-        for i in reversed(range(depth)):
-            a0 = i * 6 * C
-            p_ = f'blocks.{i}.'
-            # FFN branch: fc2's data-gradient GEMM runs without its GELU' - cvar_lora_dx applies it after adding the branch's share
-            ops.gated_grad(self.dX, self.F2[i], ada, a0 + C, n_ada, dp2[i].contiguous() if dp2 is not None else None, self.DF, self.dada, a0 + C, n_ada, B, L, C, ws)
-            ops.gemm(self.DF, self.WT['fc2'], self.DH, M=M, N=hid, K=C, w_off=i * hid * C)
-            self._lora_grads_of(i, 'fc2', p_ + 'ffn.fc2', self.DF, C, self.Hha[i], hid, kh, hid, aux=self.Aa[i], ldaux=kh, acc=acc)
-            ops.gemm(self.DH, self.WT['fc1'], self.DU, M=M, N=C, K=hid, w_off=i * C * hid)
-            self._lora_grads_of(i, 'fc1', p_ + 'ffn.fc1', self.DH, hid, self.U2a[i], C, kc, C, acc=acc)
-            ops.ln_modulate_bwd(self.X1s[i], self.DU, ada, a0 + 3 * C, n_ada, L, self.dX, self.dX, self.dada, a0 + 3 * C, a0 + 5 * C, n_ada, M, C, eps, ws)
-            # attention branch
-            ops.gated_grad(self.dX, self.F1[i], ada, a0, n_ada, dp1[i].contiguous() if dp1 is not None else None, self.DF, self.dada, a0, n_ada, B, L, C, ws)
-            ops.gemm(self.DF, self.WT['proj'], self.DU, M=M, N=C, K=C, w_off=i * C * C)
-            self._lora_grads_of(i, 'proj', p_ + 'attn.proj', self.DF, C, self.Oa[i], C, kc, C, acc=acc)
-            ops.attention_bwd(self.arena[i], self.O[i], self.DU, self.LSE[i], self.DQKV, ws, B, H, L, L, scale, lvl_end, holes=holes)
-            if cfg.uses_cos_attn:
-                ops.cos_qk_norm_bwd(self.arena[i], self.DQKV, B, H, L, L, P['scale_mul'], self.NORMS[i], self.DSM, sm_off=i * H)
-            ops.gemm(self.DQKV, self.WT['qkv'], self.DU, M=M, N=C, K=3 * C, w_off=i * C * 3 * C)
-            ops.ln_modulate_bwd(self.Xs[i], self.DU, ada, a0 + 2 * C, n_ada, L, self.dX, self.dX, self.dada, a0 + 2 * C, a0 + 4 * C, n_ada, M, C, eps, ws)
-            if self.reducer is not None:
-                self.reducer.ready(i)
-        # adaLN generator adapters: dY = d ada (B rows), u_t in the columns of [cs | u_0 ... u_depth]
-        lo = self._lora
-        s, p, seed = lo['scale'], self._lp, self._lseed
-        dada_T = self.dada.to(T)
-        ld = C + self.Kx
-        for t in range(depth + 1):
-            n_out = 6 * C if t < depth else 2 * C
-            name = f'blocks.{t}.ada_lin.1' if t < depth else 'head_nm.ada_lin.1'
-            oA = self.lora_off[f'{name}.lora_A.default.weight'][0]
-            oB = self.lora_off[f'{name}.lora_B.default.weight'][0]
-            ops.lora_down(dada_T, self.LBT['ada'][t], self.DUa, M=B, K=n_out, r=r, scale=1.0, ldx=n_ada, x_off=t * 6 * C, lda=6 * C, ldu=16)
-            ops.lora_wgrad(dada_T, self.csa, self.G_lora, self.lws, M=B, N=n_out, r=r, ldy=n_ada, y_off=t * 6 * C, ldz=ld, z_off=C + 16 * t, out_off=oB,
-                           accumulate=acc)
-            ops.lora_wgrad(self.csa, self.DUa, self.G_lora, self.lws, M=B, N=C, r=r, scale=s, p=p, seed=seed, tag=self._tag(t, 'ada'), ldy=ld, ldz=16,
-                           out_off=oA, os_n=1, os_j=C, accumulate=acc)
-        if self.reducer is not None:
-            self.reducer.ready(depth)
-
 
     def _word_embed_grads(self, tok, B, L, fl, C, Mt, Mtp, Gm, acc=False, src=None, src_has_first=True):
         """src: gradient rows of the word-embedded tokens - self.dX with L rows per sample of which the first fl are skipped, or a compact
@@ -853,6 +659,100 @@ class TrainEngine:
         for b in range(B):
             ops.colsum(src, C, Gm, L - fl, C, self.ws, accumulate=(b > 0), a_off=(b * rows + skip) * C, out_off=mo['b_we'][0])
         return acc
+
+    # ---------------------------------------------------------------- LoRA (controlvar_amd/lora.py; DESIGN.md "LoRA")
+    # The base weights are frozen: their gradients are neither computed nor stored.  Each target's rank-r branch enters the base
+    # GEMM - and so its fused epilogue (bias, gate, DropPath scale, residual, GELU, pre_act) - by K-augmentation: the operand [x | u]
+    # (u = s drop(x) A^T from cvar_lora_down, zero padding up to a 128-byte row step) against the packed weight [W | B | 0].  The
+    # backward runs the base data-gradient GEMM, then cvar_lora_down for du = dY B, cvar_lora_dx for the branch's share of dx, and
+    # cvar_lora_wgrad for dB = dY^T u and dA = s du^T drop(x).  Targets: tag 4 i + (0 proj, 1 fc1, 2 fc2, 3 ada_lin), head_nm 4 depth + 3.
+    def _lora_pack(self):
+        """operands of the adapter branch in the compute dtype: A (16 rows, zero beyond r), B^T (16 rows) per target, and the K-augmented
+        GEMM weights [W | B | 0] (base part copied once per base pack, the B columns at every forward)"""
+        from .lora import adapters
+        var = self.var
+        P = var._pack(base=True)
+        T, dev = var.compute_dtype, var.device
+        C, depth, hid, n_ada, r, rp = self.C, self.depth, self.hid, self.n_ada, self.r, self.rp
+        ad = adapters(var)
+        if self._aug is None or self._aug[0] is not P:
+            W = {}
+            for kind, (n_out, k_in) in (('proj', (C, C)), ('fc1', (hid, C)), ('fc2', (C, hid))):
+                w = torch.zeros(depth, n_out, k_in + rp, device=dev, dtype=T)
+                w[:, :, :k_in] = P['w_' + kind]
+                W[kind] = w
+            w = torch.zeros(n_ada, C + self.Kx, device=dev, dtype=T)
+            w[:, :C] = P['w_ada']
+            W['ada'] = w
+            self._aug = (P, W)
+        W = self._aug[1]
+        self.Wa = W
+        self.LA, self.LBT = {}, {}
+        for kind, (n_out, k_in) in (('proj', (C, C)), ('fc1', (hid, C)), ('fc2', (C, hid))):
+            As = torch.stack([ad[f'blocks.{i}.{_MODS[kind]}'][0] for i in range(depth)])          # (depth, r, k_in)
+            Bs = torch.stack([ad[f'blocks.{i}.{_MODS[kind]}'][1] for i in range(depth)])          # (depth, n_out, r)
+            self.LA[kind] = torch.zeros(depth, 16, k_in, device=dev, dtype=T)
+            self.LA[kind][:, :r] = As
+            self.LBT[kind] = torch.zeros(depth, 16, n_out, device=dev, dtype=T)
+            self.LBT[kind][:, :r] = Bs.transpose(1, 2)
+            W[kind][:, :, k_in:k_in + r] = Bs
+        tn = [f'blocks.{t}.ada_lin.1' for t in range(depth)] + ['head_nm.ada_lin.1']
+        self.LA['ada'] = torch.zeros(depth + 1, 16, C, device=dev, dtype=T)
+        self.LA['ada'][:, :r] = torch.stack([ad[n][0] for n in tn])
+        self.LBT['ada'] = torch.zeros(depth + 1, 16, 6 * C, device=dev, dtype=T)
+        for t, n in enumerate(tn):
+            Bt = ad[n][1]
+            self.LBT['ada'][t, :r, :Bt.shape[0]] = Bt.t()
+            W['ada'][t * 6 * C:t * 6 * C + Bt.shape[0], C + 16 * t:C + 16 * t + r] = Bt
+
+    def _tag(self, i: int, kind: str) -> int:
+        return 4 * i + ('proj', 'fc1', 'fc2', 'ada').index(kind)
+
+    def _lora_linear(self, kind, i, x, out, M, N, K, **epi):
+        """forward leaf: u = s drop(x) A^T of every adapter that feeds this GEMM into the augmented operand [x | u | 0] (x copied in the same
+        pass), then the GEMM on [W | B | 0].  The generator's depth + 1 adapters share one operand, 16 columns each; fc2 finds x already in
+        its augmented buffer, where fc1 wrote it"""
+        lo = self._lora
+        xa, ld = self.Xin[kind]
+        xa, there = xa[i], kind == 'fc2'
+        for j, t in enumerate(range(self.depth + 1) if kind == 'ada' else (i,)):
+            ops.lora_down(x, self.LA[kind][t], xa, M=M, K=K, r=self.r, scale=lo['scale'], p=self._lp, seed=self._lseed, tag=self._tag(t, kind),
+                          ldx=ld if there else 0, ldu=ld, u_off=K + 16 * j, x_copy=None if there or j else xa, ld_copy=0 if there else ld)
+        ops.gemm(xa, self.Wa[kind], out, M=M, N=N, K=ld, lda=ld, ldw=ld, w_off=i * N * ld, **epi)
+
+    def _lora_grads_of(self, i, kind, dY, n_out, k_in, acc):
+        """backward leaf: du = dY B; dx (self.DU / self.DH, in place) += branch share (fc2: * gelu'(A)); dB = dY^T u; dA = s du^T drop(x).
+        x: the augmented saved input [x | u] of the linear, u at column k_in"""
+        lo, M, r = self._lora, self.M, self.r
+        s, p, seed, tag = lo['scale'], self._lp, self._lseed, self._tag(i, kind)
+        x, ldx = self.Xin[kind]
+        x, G = x[i], self.G_lora
+        oA = self.lora_off[f'blocks.{i}.{_MODS[kind]}.lora_A.default.weight'][0]
+        oB = self.lora_off[f'blocks.{i}.{_MODS[kind]}.lora_B.default.weight'][0]
+        fc2 = kind == 'fc2'
+        ops.lora_down(dY, self.LBT[kind][i], self.DUr, M=M, K=n_out, r=r, scale=1.0, ldu=16)
+        ops.lora_dx(self.DH if fc2 else self.DU, self.DUr, self.LA[kind][i], M=M, K=k_in, r=r, scale=s, p=p, seed=seed, tag=tag, lddu=16,
+                    aux=self.A[i] if fc2 else None, ldaux=ldx if fc2 else 0)
+        ops.lora_wgrad(dY, x, G, self.lws, M=M, N=n_out, r=r, ldz=ldx, z_off=k_in, out_off=oB, accumulate=acc)
+        ops.lora_wgrad(x, self.DUr, G, self.lws, M=M, N=k_in, r=r, scale=s, p=p, seed=seed, tag=tag, ldy=ldx, ldz=16, out_off=oA, os_n=1, os_j=k_in,
+                       accumulate=acc)
+
+    def _ada_grads_lora(self, acc):
+        """adaLN generator adapters: dY = d ada (B rows), u_t in the columns of [cs | u_0 ... u_depth]"""
+        lo, C, depth, n_ada, r = self._lora, self.C, self.depth, self.n_ada, self.r
+        s, p, seed, B = lo['scale'], self._lp, self._lseed, self._saved['B']
+        dada_T = self.dada.to(self.var.compute_dtype)
+        ld = C + self.Kx
+        for t in range(depth + 1):
+            n_out = 6 * C if t < depth else 2 * C
+            name = f'blocks.{t}.ada_lin.1' if t < depth else 'head_nm.ada_lin.1'
+            oA = self.lora_off[f'{name}.lora_A.default.weight'][0]
+            oB = self.lora_off[f'{name}.lora_B.default.weight'][0]
+            ops.lora_down(dada_T, self.LBT['ada'][t], self.DUa, M=B, K=n_out, r=r, scale=1.0, ldx=n_ada, x_off=t * 6 * C, lda=6 * C, ldu=16)
+            ops.lora_wgrad(dada_T, self.csa, self.G_lora, self.lws, M=B, N=n_out, r=r, ldy=n_ada, y_off=t * 6 * C, ldz=ld, z_off=C + 16 * t, out_off=oB,
+                           accumulate=acc)
+            ops.lora_wgrad(self.csa, self.DUa, self.G_lora, self.lws, M=B, N=C, r=r, scale=s, p=p, seed=seed, tag=self._tag(t, 'ada'), ldy=ld, ldz=16,
+                           out_off=oA, os_n=1, os_j=C, accumulate=acc)
 
 
 class BucketReducer:
