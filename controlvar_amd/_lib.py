@@ -1,4 +1,4 @@
-"""ctypes binding of libcvar_hip.so (include/cvar.h, include/cvar_serve.h, include/cvar_accum.h, include/cvar_kvcache.h, include/cvar_wide.h).  No torch types cross this boundary:
+"""ctypes binding of libcvar_hip.so (include/cvar.h, include/cvar_serve.h, include/cvar_accum.h, include/cvar_kvcache.h, include/cvar_wide.h, include/cvar_policy.h).  No torch types cross this boundary:
 callers hand over raw device pointers (``tensor.data_ptr()``), sizes and the HIP stream handle.
 
 The library is mandatory on the product path: if it is missing or does not load, every op
@@ -157,6 +157,12 @@ WIDE_SIGNATURES = {
     'cvar_ln_modulate_fp8_wide': (c_i, [c_p, c_p, c_p, c_l, c_i, c_p, c_l, c_p, c_i, c_i, c_f, c_p]),
 }
 
+# include/cvar_policy.h: the clipped policy-gradient loss beside cvar_ce_fwd_bwd (policy-gradient fine-tuning).  A table of its own for the
+# same reason; no signature of the other five headers changed, so neither version moved
+POLICY_SIGNATURES = {
+    'cvar_pg_fwd_bwd': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_l, c_i, c_p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -180,7 +186,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
             pass
         lib = C.CDLL(path, mode=C.RTLD_GLOBAL)
         for name, (res, args) in (*SIGNATURES.items(), *SERVE_SIGNATURES.items(), *ACCUM_SIGNATURES.items(), *KVCACHE_SIGNATURES.items(),
-                                  *WIDE_SIGNATURES.items()):
+                                  *WIDE_SIGNATURES.items(), *POLICY_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

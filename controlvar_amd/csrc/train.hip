@@ -4,6 +4,7 @@
 // All reductions are two-level with a fixed order (no atomics): results are bit-reproducible.
 #include "cvar_common.h"
 #include "../../include/cvar_accum.h"
+#include "../../include/cvar_policy.h"
 
 constexpr int RED_S = 8;      // row segments of the per-sequence column reductions (scalar fallbacks)
 // The vector kernels split every sequence into red_segments(R, l) row segments so that R * segments blocks fill the chip
@@ -691,6 +692,80 @@ extern "C" int cvar_ce_fwd_bwd(const float* logits, const int32_t* target, const
     if (!dlogits || out_dtype == CVAR_F32) hipLaunchKernelGGL(ce_kernel<float>, grid, block, 0, as_stream(stream), logits, target, weight, gscale, loss_tok, (float*)dlogits, V);
     else if (out_dtype == CVAR_BF16) hipLaunchKernelGGL(ce_kernel<bf16_t>, grid, block, 0, as_stream(stream), logits, target, weight, gscale, loss_tok, (bf16_t*)dlogits, V);
     else return CVAR_EUNSUPPORTED;
+    CVAR_CHECK_LAUNCH();
+    return CVAR_OK;
+}
+
+// ---- clipped policy-gradient loss forward + backward (include/cvar_policy.h): ce_kernel's row pass - the same loops and reduction
+// order up to mx and se - then the per-row scalars (ratio, clip decision, k3 KL term), computed by every thread from wave-uniform values and stored
+// by thread 0; the gradient pass is ce_kernel's with g = ((c * w) * gscale) in the place of (w * gscale)
+template <typename TO>
+__global__ __launch_bounds__(256) void pg_kernel(const float* __restrict__ logits, const int* __restrict__ target, const float* __restrict__ adv,
+                                                const float* __restrict__ weight, const float* __restrict__ old_lp, const float* __restrict__ ref_lp,
+                                                float clip_lo, float clip_hi, float kl_coef, float gscale, float* __restrict__ loss_tok,
+                                                float* __restrict__ logprob, float* __restrict__ ratio, float* __restrict__ kl, int* __restrict__ clipped,
+                                                float* __restrict__ coef, TO* __restrict__ dlogits, int V) {
+    __shared__ float red[4];
+    const long m = blockIdx.x;
+    const float* lr = logits + m * V;
+    float mx = -INFINITY;
+    for (int v = threadIdx.x; v < V; v += 256) mx = fmaxf(mx, lr[v]);
+    mx = wave_max(mx);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    __syncthreads();
+    float se = 0.f;
+    for (int v = threadIdx.x; v < V; v += 256) se += __expf(lr[v] - mx);
+    se = wave_sum(se);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = se;
+    __syncthreads();
+    se = (red[0] + red[1]) + (red[2] + red[3]);
+    const int tg = target[m];
+    const float lp = -((logf(se) + mx) - lr[tg]);
+    const float a = adv[m];
+    const float r = old_lp ? expf(lp - old_lp[m]) : 1.0f;
+    const float s1 = r * a, s2 = fminf(fmaxf(r, 1.0f - clip_lo), 1.0f + clip_hi) * a;
+    const bool active = s1 <= s2;                                   // a tie is active
+    float k = 0.f, dk = 0.f;                                        // k3 estimator and -(its derivative in lp)
+    if (ref_lp) {
+        const float d = ref_lp[m] - lp, e = expf(d);
+        k = (e - d) - 1.0f;
+        dk = 1.0f - e;
+    }
+    const float c = (active ? s1 : 0.0f) - kl_coef * dk;            // -d loss / d lp
+    const float cw = c * (weight ? weight[m] : 1.0f);
+    if (threadIdx.x == 0) {
+        const float obj = old_lp ? fminf(s1, s2) : a * lp;          // no old policy: the score-function surrogate (the ratio is the constant 1)
+        loss_tok[m] = -obj + kl_coef * k;
+        if (logprob) logprob[m] = lp;
+        if (ratio) ratio[m] = r;
+        if (kl) kl[m] = k;
+        if (clipped) clipped[m] = active ? 0 : 1;
+        if (coef) coef[m] = cw;
+    }
+    if (dlogits) {
+        const float g = cw * gscale;
+        const float inv = 1.0f / se;
+        for (int v = threadIdx.x; v < V; v += 256) {
+            const float pr = __expf(lr[v] - mx) * inv;
+            Elem<TO>::st(dlogits + m * V + v, (pr - (v == tg ? 1.0f : 0.0f)) * g);
+        }
+    }
+}
+extern "C" int cvar_pg_fwd_bwd(const float* logits, const int32_t* target, const float* adv, const float* weight, const float* old_lp, const float* ref_lp,
+                               float clip_lo, float clip_hi, float kl_coef, float gscale, float* loss_tok, float* logprob, float* ratio, float* kl,
+                               int32_t* clipped, float* coef, void* dlogits, int out_dtype, int64_t M, int V, void* stream) {
+    if (!logits || !target || !adv || !loss_tok || M <= 0 || V <= 1) return CVAR_EINVAL;
+    if (!(clip_lo >= 0.0f) || !(clip_hi >= 0.0f) || !(kl_coef >= 0.0f)) return CVAR_EINVAL;
+    if (out_dtype != CVAR_F32 && out_dtype != CVAR_BF16) return CVAR_EUNSUPPORTED;
+    dim3 grid((unsigned)M), block(256);
+    if (!dlogits || out_dtype == CVAR_F32)
+        hipLaunchKernelGGL(pg_kernel<float>, grid, block, 0, as_stream(stream), logits, target, adv, weight, old_lp, ref_lp, clip_lo, clip_hi, kl_coef, gscale,
+                           loss_tok, logprob, ratio, kl, clipped, coef, (float*)dlogits, V);
+    else
+        hipLaunchKernelGGL(pg_kernel<bf16_t>, grid, block, 0, as_stream(stream), logits, target, adv, weight, old_lp, ref_lp, clip_lo, clip_hi, kl_coef, gscale,
+                           loss_tok, logprob, ratio, kl, clipped, coef, (bf16_t*)dlogits, V);
     CVAR_CHECK_LAUNCH();
     return CVAR_OK;
 }

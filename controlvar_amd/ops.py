@@ -663,6 +663,15 @@ def ce_fwd_bwd(logits, target, weight, gscale, loss_tok, dlogits, M, V):
                                       dt(dlogits) if dlogits is not None else CVAR_F32, M, V, _stream()), 'cvar_ce_fwd_bwd')
 
 
+def pg_fwd_bwd(logits, target, adv, weight, old_lp, ref_lp, clip_lo, clip_hi, kl_coef, gscale, loss_tok, M, V, dlogits=None, logprob=None,
+               ratio=None, kl=None, clipped=None, coef=None):
+    """the clipped policy-gradient loss on the rows cvar_ce_fwd_bwd takes (cvar_pg_fwd_bwd, include/cvar_policy.h): weight / old_lp / ref_lp and
+    every output but loss_tok may be None"""
+    check(_lib.load().cvar_pg_fwd_bwd(_ptr(logits), _ptr(target), _ptr(adv), _ptr(weight), _ptr(old_lp), _ptr(ref_lp), float(clip_lo), float(clip_hi),
+                                      float(kl_coef), float(gscale), _ptr(loss_tok), _ptr(logprob), _ptr(ratio), _ptr(kl), _ptr(clipped), _ptr(coef),
+                                      _ptr(dlogits), dt(dlogits) if dlogits is not None else CVAR_F32, M, V, _stream()), 'cvar_pg_fwd_bwd')
+
+
 def scatter_add_rows(src, ld_src, idx, dst, n, Cdim, src_off: int = 0):
     check(_lib.load().cvar_scatter_add_rows(_ptr(src) + 4 * src_off, ld_src, _ptr(idx), _ptr(dst), n, Cdim, _stream()), 'cvar_scatter_add_rows')
 

@@ -8,6 +8,7 @@
 from __future__ import annotations
 
 import math
+from dataclasses import dataclass
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 NOWD_KEYS = ('cls_token', 'start_token', 'task_token', 'cfg_uncond', 'pos_embed', 'pos_1LC', 'pos_start', 'start_pos', 'lvl_embed',
@@ -137,6 +138,71 @@ from .spec import attention_levels  # noqa: E402
 
 def _pad8(n: int) -> int:
     return (n + 7) // 8 * 8
+
+
+@dataclass
+class PolicyLoss:
+    """The clipped policy-gradient loss of a training step on token ids (cvar_pg_fwd_bwd, include/cvar_policy.h), in the place of
+    the cross-entropy: per token, with lp its log-probability under the model being trained,
+        ratio = exp(lp - old_logprob),  loss = -min(ratio * A, clamp(ratio, 1 - clip[0], 1 + clip[1]) * A) + kl_coef * k3(ref_logprob - lp).
+    advantages   (B,) - one per sample, broadcast over its tokens - or (B, L), signed;
+    old_logprob  (B, L) log-probabilities of the policy the tokens were drawn from (Trainer.token_logprobs); None: the ratio is exactly 1
+                 and nothing clips - REINFORCE with the advantage as the token weight;
+    ref_logprob  (B, L) log-probabilities of the frozen reference policy of the KL term; None: no KL term (kl_coef must then be 0);
+    clip         (below, above) >= 0, or one number for both.
+    (B, L) tensors are in the token order of the training labels: per scale the two halves, control first when mask_first (TokenScores).
+    Everything is checked on the host when the object is built and, against the batch, by rows()."""
+    advantages: torch.Tensor
+    old_logprob: Optional[torch.Tensor] = None
+    ref_logprob: Optional[torch.Tensor] = None
+    clip: Tuple[float, float] = (0.2, 0.2)
+    kl_coef: float = 0.0
+
+    def __post_init__(self):
+        clip = self.clip
+        if isinstance(clip, (int, float)) and not isinstance(clip, bool):
+            clip = (clip, clip)
+        if (not isinstance(clip, (tuple, list)) or len(clip) != 2
+                or not all(isinstance(c, (int, float)) and not isinstance(c, bool) and math.isfinite(c) and c >= 0 for c in clip)):
+            raise ValueError(f'clip={self.clip!r}: two finite numbers >= 0 (below, above), or one for both')
+        self.clip = (float(clip[0]), float(clip[1]))
+        k = self.kl_coef
+        if isinstance(k, bool) or not isinstance(k, (int, float)) or not math.isfinite(k) or k < 0:
+            raise ValueError(f'kl_coef={k!r}: a finite number >= 0')
+        self.kl_coef = float(k)
+        if self.kl_coef > 0 and self.ref_logprob is None:
+            raise ValueError('kl_coef > 0 needs ref_logprob: the KL term is taken against a reference policy (Trainer.token_logprobs before the first update)')
+        for name in ('advantages', 'old_logprob', 'ref_logprob'):
+            t = getattr(self, name)
+            if t is None and name != 'advantages':
+                continue
+            if not torch.is_tensor(t) or not t.is_floating_point():
+                raise ValueError(f'{name}: expected a floating-point tensor, got {type(t).__name__ if not torch.is_tensor(t) else t.dtype}')
+            if t.dim() not in ((1, 2) if name == 'advantages' else (2,)):
+                raise ValueError(f'{name}: expected {"(B,) or (B, L)" if name == "advantages" else "(B, L)"}, got {tuple(t.shape)}')
+
+    def check(self, B: int, L: int):
+        """the shapes against a batch of B samples of L tokens (host only)"""
+        for name in ('advantages', 'old_logprob', 'ref_logprob'):
+            t = getattr(self, name)
+            ok = ((B,), (B, L)) if name == 'advantages' else ((B, L),)
+            if t is not None and tuple(t.shape) not in ok:
+                raise ValueError(f'{name}: expected shape {" or ".join(str(o) for o in ok)}, got {tuple(t.shape)}')
+
+    def rows(self, B: int, L: int, device=None):
+        """-> (advantages, old_logprob or None, ref_logprob or None), each (B * L,) fp32 contiguous on `device`, advantages broadcast"""
+        self.check(B, L)
+        out = []
+        for name in ('advantages', 'old_logprob', 'ref_logprob'):
+            t = getattr(self, name)
+            if t is None:
+                out.append(None)
+                continue
+            t = t.to(device=device, dtype=torch.float32)
+            if t.dim() == 1:
+                t = t[:, None].expand(B, L)
+            out.append(t.contiguous().view(-1))
+        return tuple(out)
 
 
 def _ln_rows(C: int):
@@ -389,10 +455,14 @@ class TrainEngine:
     @torch.no_grad()
     def forward_backward(self, label_B: torch.Tensor, x_wo_first: torch.Tensor, cond_type: Optional[torch.Tensor], targets: torch.Tensor,
                          ignore_mask: Optional[torch.Tensor] = None, drop_seed: Optional[int] = None, mask_first: bool = True,
-                         accumulate: bool = False):
+                         accumulate: bool = False, policy: Optional[PolicyLoss] = None):
         """-> (loss scalar tensor, per-token loss (B*L,)); gradients land in self.grads(): overwritten, or with accumulate=True added to what
         it holds - fp32(old + this micro-batch's plain gradient) per element, whatever the batch size of the earlier calls.  The loss and its
-        1 / M scale are this micro-batch's own; the 1 / N of a window of N belongs to the optimizer's gradient scale (FusedAdamW.step)."""
+        1 / M scale are this micro-batch's own; the 1 / N of a window of N belongs to the optimizer's gradient scale (FusedAdamW.step).
+        policy: the clipped policy-gradient loss in the place of the cross-entropy (PolicyLoss) - one other loss launch on the
+        same logits and dlogits, nothing else; the per-token logprob, ratio, clipped, kl and coef stay on the engine as self.policy_out."""
+        if policy is not None:
+            policy.check(x_wo_first.shape[0], self.L)                 # refused before any device work
         self.forward_train(label_B, x_wo_first, cond_type, drop_seed, mask_first)
         dev = self.var.device
         M, V = self.M, self.V
@@ -402,7 +472,14 @@ class TrainEngine:
             gscale = 1.0 / (M * (float(w.mean()) + 1e-6))
         else:
             w, gscale = None, 1.0 / M
-        ops.ce_fwd_bwd(self.logits, tg, w, gscale, self.loss_tok, self.dlogits, M, V)
+        if policy is None:
+            ops.ce_fwd_bwd(self.logits, tg, w, gscale, self.loss_tok, self.dlogits, M, V)
+        else:
+            adv, old, ref = policy.rows(self._saved['B'], self.L, dev)
+            po = self.policy_out = dict(logprob=torch.empty(M, device=dev), ratio=torch.empty(M, device=dev), kl=torch.empty(M, device=dev),
+                                        coef=torch.empty(M, device=dev), clipped=torch.empty(M, device=dev, dtype=torch.int32))
+            ops.pg_fwd_bwd(self.logits, tg, adv, w, old, ref, policy.clip[0], policy.clip[1], policy.kl_coef, gscale, self.loss_tok, M, V,
+                           dlogits=self.dlogits, **po)
         loss = (self.loss_tok * w).mean() / (w.mean() + 1e-6) if w is not None else self.loss_tok.mean()
         self.backward(accumulate=accumulate)
         return loss, self.loss_tok
@@ -959,8 +1036,15 @@ class Trainer:
         # tokenizer sums in a batch-dependent order, so the ids equal the two-call form's exactly in both precision modes
         # (tests/test_gpu_train.py::test_tokenize_one_pass_equals_the_two_call_form)
         B = masks.shape[0]
-        both = self.vae.img_to_idxBl(torch.cat((masks, images), dim=0))
+        return self._inputs_of(self.vae.img_to_idxBl(torch.cat((masks, images), dim=0)), B, mask_first)
+
+    @torch.no_grad()
+    def _inputs_of(self, both: List[torch.Tensor], B: int, mask_first: bool = True):
+        """the ids of a batch -> (teacher-forcing input x, labels): per scale (2 B, pn^2) ids, the control halves of the B samples above their
+        image halves - what the one-pass tokenizer returns and what step_tokens stacks - or, for a plain VAR, (B, pn^2)"""
         hboth = self.vae.idxBl_to_h(both)
+        if self.var.cfg.mask_factor != 2:
+            return torch.cat(hboth, dim=1), torch.cat(both, dim=1)
         mi, ii = [t[:B] for t in both], [t[B:] for t in both]
         mh, ih = [t[:B] for t in hboth], [t[B:] for t in hboth]
         if not mask_first:
@@ -987,13 +1071,18 @@ class Trainer:
         One call = one micro-batch.  The returned dict carries ``micro`` (index inside the window) and ``synced`` (this call closed the window
         and stepped the optimizer).  A call that does not sync returns its micro-batch loss and ``grad_norm`` / ``clip_coef`` None; the one
         that does returns the last micro-batch's ``loss`` next to ``window_loss``, the mean of the window's micro-batch losses."""
-        micro, accumulate, sync = self.window.begin()
         if mask_first is None:
             import random
             mask_first = not (getattr(self.var, 'bidirectional', False) and random.random() < 0.5)
+        return self._micro_batch(lambda: self.tokenize(images, masks, mask_first), cls, types, ignore_mask, drop_seed, mask_first)
+
+    def _micro_batch(self, inputs, cls, types, ignore_mask, drop_seed, mask_first: bool, policy: Optional[PolicyLoss] = None) -> Dict[str, object]:
+        """one micro-batch of the window on the (x, labels) that inputs() returns: schedule, forward + backward, and - when it closes the window -
+        all-reduce, clipping, AdamW.  The body of step() and of step_tokens()"""
+        micro, accumulate, sync = self.window.begin()
         s = self.sched
         _, max_lr, _, max_wd = lr_wd_annealing(s['sche'], self.opt, s['peak_lr'], s['wd'], s['wd_end'], self.it, s['wp_it'], s['max_it'], wp0=s['wp0'], wpe=s['wpe'])
-        x, labels = self.tokenize(images, masks, mask_first)
+        x, labels = inputs()
         self.engine._setup(x.shape[0])
         if (self.world > 1 or self.force_reducer) and self.comm and sync:         # the all-reduce rides on the backward that closes the window
             if self._reducer_for is not self.engine.buckets:
@@ -1002,13 +1091,14 @@ class Trainer:
             self.engine.reducer = self._reducer
         else:
             self.engine.reducer = None
-        loss, _ = self.engine.forward_backward(cls, x, types, labels, ignore_mask, drop_seed, mask_first, accumulate=accumulate)
+        loss, _ = self.engine.forward_backward(cls, x, types, labels, ignore_mask, drop_seed, mask_first, accumulate=accumulate, policy=policy)
+        extra = self._policy_report(x.shape[0], ignore_mask) if policy is not None else {}
         n = self.window.n
         if n > 1:
             self._loss_sum = loss if micro == 0 else self._loss_sum + loss
         if not sync:
             self.window.end()
-            return dict(loss=loss, grad_norm=None, clip_coef=None, lr=max_lr, wd=max_wd, mask_first=mask_first, synced=False, micro=micro)
+            return dict(loss=loss, grad_norm=None, clip_coef=None, lr=max_lr, wd=max_wd, mask_first=mask_first, synced=False, micro=micro, **extra)
         if self.engine.reducer is not None:
             self.engine.reducer.wait()
         norm_coef = self.opt.step(self.engine.grads(), self.clip, self.world, n)
@@ -1017,7 +1107,94 @@ class Trainer:
         self.window.end()
         window_loss = self._loss_sum / n if n > 1 else loss
         return dict(loss=loss, window_loss=window_loss, grad_norm=norm_coef[0], clip_coef=norm_coef[1], lr=max_lr, wd=max_wd, mask_first=mask_first,
-                    synced=True, micro=micro)
+                    synced=True, micro=micro, **extra)
+
+    # ---------------------------------------------------------------- training on token ids
+    def _policy_report(self, B: int, ignore_mask) -> Dict[str, object]:
+        """what a policy step adds to the returned dict: means over the tokens that count (weight != 0; all of them without ignore_mask) as
+        device scalars, and the (B, L) log-probabilities the step saw"""
+        po = self.engine.policy_out
+        if ignore_mask is None:
+            mean = lambda t: t.float().mean()
+        else:
+            live = (ignore_mask.to(device=po['ratio'].device).reshape(-1) != 0).float()
+            mean = lambda t: (t.float() * live).sum() / live.sum().clamp(min=1.0)
+        return dict(mean_ratio=mean(po['ratio']), clip_frac=mean(po['clipped']), mean_kl=mean(po['kl']), token_logprob=po['logprob'].view(B, -1))
+
+    def _check_tokens(self, ids_img, ids_ctrl, cls, types, mask_first: Optional[bool]):
+        """the host side of step_tokens / token_logprobs, before any device work -> (per scale the stacked ids _inputs_of takes, B, mask_first)"""
+        from .models import _check_index_range, _flat_ids
+        cfg = self.var.cfg
+        if cfg.separator:
+            raise NotImplementedError('training on token ids: separator models are not offered (their label row carries special tokens between the '
+                                      'halves, which the (B, L) token layout does not hold)')
+        bidir = bool(getattr(self.var, 'bidirectional', False))
+        if mask_first is None:
+            if bidir:
+                raise ValueError('mask_first: a bidirectional model lays either half first - say which order these ids are in (step() draws it, '
+                                 'given ids have one)')
+            mask_first = True
+        if not mask_first and not bidir:
+            raise ValueError('mask_first=False: only a bidirectional model lays the image half first')
+        if not torch.is_tensor(cls) or cls.dim() != 1 or cls.is_floating_point():
+            raise ValueError(f'cls: expected integer class labels of shape (B,), got {tuple(cls.shape) if torch.is_tensor(cls) else type(cls).__name__}')
+        B, pns, mf = cls.shape[0], cfg.pyramid.patch_nums, cfg.mask_factor
+        _check_index_range(cls, 0, cfg.num_classes, 'cls')
+        if mf == 2 and types is not None:
+            if not torch.is_tensor(types) or tuple(types.shape) != (B,) or types.is_floating_point():
+                raise ValueError(f'types: expected integer control types of shape ({B},)')
+            _check_index_range(types, 0, 4, 'types')
+        img = _flat_ids('ids_img', ids_img, B, pns, cfg.vocab)
+        if mf == 2:
+            if ids_ctrl is None:
+                raise ValueError('ids_ctrl: a ControlVAR sample is its control half and its image half - pass both')
+            ctrl = _flat_ids('ids_ctrl', ids_ctrl, B, pns, cfg.vocab)
+            flat = torch.cat((ctrl.to(self.var.device), img.to(self.var.device)), dim=0).long()
+        else:
+            if ids_ctrl is not None:
+                raise ValueError('ids_ctrl: a plain VAR has the image half only')
+            flat = img.to(self.var.device).long()
+        both, o = [], 0
+        for pn in pns:
+            both.append(flat[:, o:o + pn * pn])
+            o += pn * pn
+        return both, B, mask_first
+
+    @torch.no_grad()
+    def step_tokens(self, ids_img, ids_ctrl, cls, types, *, ignore_mask=None, policy: Optional[PolicyLoss] = None, drop_seed=None,
+                    mask_first: Optional[bool] = None) -> Dict[str, object]:
+        """step() on token ids instead of pixels: one micro-batch with step()'s window, schedule, all-reduce, clipping and return dict, without
+        the tokenizer.  ids_img / ids_ctrl: each half's multi-scale ids in the forms score_infer_cfg takes - the list of (B, pn^2) tensors
+        vae.img_to_idxBl returns or one (B, sum pn^2) tensor - so a sampled sequence or a pre-tokenised dataset trains as it is; ids_ctrl=None
+        for a plain VAR.  On the ids of tokenize() the step equals step() on the pixels bit for bit.
+        policy: a PolicyLoss replaces the cross-entropy by the clipped policy-gradient loss; the dict then also carries mean_ratio, clip_frac,
+        mean_kl (device scalars over the tokens that count) and token_logprob (B, L) in TokenScores' token order.
+        Shapes and the id range are checked on the host before any device work.  Separator models are refused; a bidirectional model needs
+        mask_first said (True: these ids go control first)."""
+        both, B, mask_first = self._check_tokens(ids_img, ids_ctrl, cls, types, mask_first)
+        if policy is not None:
+            if not isinstance(policy, PolicyLoss):
+                raise TypeError(f'policy: a PolicyLoss, got {type(policy).__name__}')
+            policy.check(B, self.var.cfg.pyramid.L)
+        if ignore_mask is not None and ignore_mask.numel() != B * self.var.cfg.pyramid.L:
+            raise ValueError(f'ignore_mask: expected {B} x {self.var.cfg.pyramid.L} token weights, got {tuple(ignore_mask.shape)}')
+        return self._micro_batch(lambda: self._inputs_of(both, B, mask_first), cls, types, ignore_mask, drop_seed, mask_first, policy)
+
+    @torch.no_grad()
+    def token_logprobs(self, ids_img, ids_ctrl, cls, types, *, drop_seed=None, mask_first: Optional[bool] = None) -> torch.Tensor:
+        """-> (B, L) fp32: the log-probability of every given token under the model as the TRAINING forward sees it (the model's current mode,
+        DropPath and adapter dropout drawn from drop_seed), in TokenScores' token order - the producer of PolicyLoss.old_logprob /
+        ref_logprob.  The forward is forward_train and the log-probability the negated per-token loss of a loss-only cvar_ce_fwd_bwd, so with
+        unchanged parameters and the same drop_seed a following policy step sees ratio == 1.0f in every token (a model with cond_drop_rate > 0
+        draws its condition dropout per forward, outside drop_seed).  No backward runs, no gradient buffer is written, the accumulation window
+        and `it` stay where they are.  mask_first=None: True, except that a bidirectional model must say it.  Refusals as step_tokens."""
+        both, B, mask_first = self._check_tokens(ids_img, ids_ctrl, cls, types, mask_first)
+        x, labels = self._inputs_of(both, B, mask_first)
+        eng = self.engine
+        eng.forward_train(cls, x, types, drop_seed, mask_first)
+        tg = labels.to(device=self.var.device, dtype=torch.int32).contiguous().view(-1)
+        ops.ce_fwd_bwd(eng.logits, tg, None, 1.0, eng.loss_tok, None, eng.M, eng.V)
+        return (-eng.loss_tok).view(B, -1)
 
 
 class _TeacherForcedFn(torch.autograd.Function):
