@@ -5,6 +5,7 @@
 #include "cvar_common.h"
 #include "../../include/cvar_accum.h"
 #include "../../include/cvar_policy.h"
+#include "../../include/cvar_distill.h"
 
 constexpr int RED_S = 8;      // row segments of the per-sequence column reductions (scalar fallbacks)
 // The vector kernels split every sequence into red_segments(R, l) row segments so that R * segments blocks fill the chip
@@ -766,6 +767,73 @@ extern "C" int cvar_pg_fwd_bwd(const float* logits, const int32_t* target, const
     else
         hipLaunchKernelGGL(pg_kernel<bf16_t>, grid, block, 0, as_stream(stream), logits, target, adv, weight, old_lp, ref_lp, clip_lo, clip_hi, kl_coef, gscale,
                            loss_tok, logprob, ratio, kl, clipped, coef, (bf16_t*)dlogits, V);
+    CVAR_CHECK_LAUNCH();
+    return CVAR_OK;
+}
+
+// ---- soft-target (distillation) loss forward + backward (include/cvar_distill.h): ce_kernel's row pass once over the student row
+// (mx, se) and once, with the same text, over the teacher row (mz, sz); the third pass forms p_v and q_v, accumulates the row's
+// KL(teacher || student) per thread in the loop's order and stores (p_v - q_v) * g.  The KL goes through the same wave tree and four-wave sum
+template <typename TO>
+__global__ __launch_bounds__(256) void kd_kernel(const float* __restrict__ logits, const float* __restrict__ teacher, long ldt, const float* __restrict__ weight,
+                                                float gscale, float* __restrict__ loss_tok, TO* __restrict__ dlogits, int V) {
+    __shared__ float red[4];
+    const long m = blockIdx.x;
+    const float* lr = logits + m * V;
+    const float* tr = teacher + m * ldt;
+    float mx = -INFINITY;
+    for (int v = threadIdx.x; v < V; v += 256) mx = fmaxf(mx, lr[v]);
+    mx = wave_max(mx);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    __syncthreads();
+    float se = 0.f;
+    for (int v = threadIdx.x; v < V; v += 256) se += __expf(lr[v] - mx);
+    se = wave_sum(se);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = se;
+    __syncthreads();
+    se = (red[0] + red[1]) + (red[2] + red[3]);
+    __syncthreads();
+    float mz = -INFINITY;
+    for (int v = threadIdx.x; v < V; v += 256) mz = fmaxf(mz, tr[v]);
+    mz = wave_max(mz);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mz;
+    __syncthreads();
+    mz = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    __syncthreads();
+    float sz = 0.f;
+    for (int v = threadIdx.x; v < V; v += 256) sz += __expf(tr[v] - mz);
+    sz = wave_sum(sz);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sz;
+    __syncthreads();
+    sz = (red[0] + red[1]) + (red[2] + red[3]);
+    __syncthreads();
+    const float lse_x = logf(se) + mx, lse_z = logf(sz) + mz;
+    const float g = (weight ? weight[m] : 1.0f) * gscale;
+    const float inv = 1.0f / se, invz = 1.0f / sz;
+    float kl = 0.f;
+    for (int v = threadIdx.x; v < V; v += 256) {
+        const float x = lr[v], z = tr[v];
+        const float q = __expf(z - mz) * invz;
+        kl += q * ((z - lse_z) - (x - lse_x));
+        if (dlogits) {
+            const float pr = __expf(x - mx) * inv;
+            Elem<TO>::st(dlogits + m * V + v, (pr - q) * g);
+        }
+    }
+    kl = wave_sum(kl);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = kl;
+    __syncthreads();
+    if (threadIdx.x == 0) loss_tok[m] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+extern "C" int cvar_kd_fwd_bwd(const float* logits, const float* teacher, int ldt, const float* weight, float gscale, float* loss_tok,
+                               void* dlogits, int out_dtype, int64_t M, int V, void* stream) {
+    if (!logits || !teacher || !loss_tok || M <= 0 || V <= 1 || ldt < V) return CVAR_EINVAL;
+    if (out_dtype != CVAR_F32 && out_dtype != CVAR_BF16) return CVAR_EUNSUPPORTED;
+    dim3 grid((unsigned)M), block(256);
+    if (!dlogits || out_dtype == CVAR_F32) hipLaunchKernelGGL(kd_kernel<float>, grid, block, 0, as_stream(stream), logits, teacher, (long)ldt, weight, gscale, loss_tok, (float*)dlogits, V);
+    else hipLaunchKernelGGL(kd_kernel<bf16_t>, grid, block, 0, as_stream(stream), logits, teacher, (long)ldt, weight, gscale, loss_tok, (bf16_t*)dlogits, V);
     CVAR_CHECK_LAUNCH();
     return CVAR_OK;
 }

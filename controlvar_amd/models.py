@@ -737,7 +737,7 @@ def _request_table(B: int, cfg, top_k, top_p, g_seed, four_way: bool, vocab: int
                              f'{name}: one triple of guidance scales or shape {want} expected, got {a.shape}')
         return a
 
-    cfg_r = rows('cfg', cfg, 3 if four_way else None).astype(np.float64)
+    cfg_r = rows('cfg', cfg, 3 if four_way else None).astype(np.float64) if cfg is not None else None      # None: no guidance rows, the weights are [1]
     k_r = rows('top_k', top_k)
     if k_r.dtype.kind == 'f':
         if not np.all(k_r == np.round(k_r)):
@@ -765,7 +765,9 @@ def _request_table(B: int, cfg, top_k, top_p, g_seed, four_way: bool, vocab: int
     for si in range(nstage):
         ratio = si / (nstage - 1)
         for b in range(B):
-            if four_way:
+            if cfg_r is None:
+                coef[si, b, 0] = 1.0
+            elif four_way:
                 t1, t2, t3 = [c * ratio for c in cfg_r[b].tolist()]
                 coef[si, b] = [1 + t1, t2 - t1, t3 - t2, -t3]
             else:
@@ -850,6 +852,28 @@ class TokenScores:
             m = m & self.sampled
         lp = self.logprob.double()
         return torch.where(m, lp, torch.zeros((), dtype=lp.dtype, device=lp.device)).sum(dim=1)
+
+
+class DistillTargets(NamedTuple):
+    """What a generation call returns beside its images under ``distill_targets=True`` (guidance distillation): the sample the
+    teacher drew and the guided distribution it drew every token from, in the forms Trainer.step_tokens takes -
+        trainer.step_tokens(t.ids_img, t.ids_ctrl, cls, types, distill=t.loss(), mask_first=t.mask_first)
+      ids_img, ids_ctrl  (B, sum pn^2) int32: the ids the first branch continued with, i.e. after the teacher-forcing overwrites of
+                         conditional_infer_cfg (last_trace['idx'] holds the draw before them); ids_ctrl is None for a plain VAR
+      logits             (B, L, V) fp32: the sampler's combined logits sum_k coef_k logits_k of every scale in token order, bit for bit
+                         what trace=True records
+      sampled            (B, L) bool, as TokenScores.sampled: False where the token was teacher-forced
+      mask_first         the order of the halves in `logits` / `sampled` (control first)"""
+    ids_img: torch.Tensor
+    ids_ctrl: Optional[torch.Tensor]
+    logits: torch.Tensor
+    sampled: torch.Tensor
+    mask_first: bool
+
+    def loss(self):
+        """the DistillLoss of a training step on this batch: the guided logits as soft targets, the teacher-forced tokens weighted 0"""
+        from .train import DistillLoss
+        return DistillLoss(self.logits, weights=self.sampled)
 
 
 def _score_buffers(B: int, L: int, dev):
@@ -967,6 +991,10 @@ _KV8_NO_X3 = ("kv_precision='fp8' is not offered under gemm_precision='bf16x3': 
               "and an e4m3 K/V cache would undo it; run it on a compute_dtype=torch.bfloat16 model with gemm_precision None or 'fp8'")
 _FP8_NO_BANK = ("gemm_precision='fp8': the per-request adapter bank (attach_adapters / adapter=) is not offered - its K-augmented bf16 operands [W | B_0 ...] have no "
                 "e4m3 form in this mode; merge one adapter with add_lora, or run the bank on gemm_precision=None")
+
+
+_NO_UNGUIDED = ('{}: cfg=None (generation without guidance rows) is not offered here - it is built for autoregressive_infer_cfg, conditional_infer_cfg '
+                'and their graphed generators; pass cfg=0.0 for the unguided distribution on the guided rows')
 
 
 def _no_bank_message(precision) -> str:
@@ -1693,29 +1721,56 @@ class ControlVAR(nn.Module):
         return cond_type.to(device=dev, dtype=torch.int32)
 
     @torch.no_grad()
-    def _prepare_rows(self, B, label_B, cond_type, four_way, seed):
-        """labels / condition types of all CFG rows: [cond ; uncond] or the 4-branch layout (control_var.py:252-263,381-400)"""
+    def _prepare_rows(self, B, label_B, cond_type, four_way, seed, nrep: Optional[int] = None):
+        """labels / condition types of all CFG rows: [cond ; uncond] or the 4-branch layout (control_var.py:252-263,381-400); nrep == 1
+        (cfg=None): the conditional rows alone"""
         cfg = self.cfg
         labels = self._as_labels(B, label_B, seed)
         empty = torch.full_like(labels, self.num_classes)
-        nrep = 4 if four_way else 2
+        nrep = self._guidance_rows(four_way) if nrep is None else nrep
         labels_all = torch.cat([labels] + [empty] * (nrep - 1)).contiguous()
         types_all = None
         if cfg.mask_factor == 2:
             types = self._as_types(B, cond_type, seed)
             e4 = torch.full_like(types, 4)
-            types_all = (torch.cat([types, types, e4, e4]) if four_way else torch.cat([types, e4])).contiguous()
+            types_all = (types if nrep == 1 else torch.cat([types, types, e4, e4]) if four_way else torch.cat([types, e4])).contiguous()
         return labels_all, types_all
+
+    @staticmethod
+    def _guidance_rows(four_way: bool, unguided: bool = False) -> int:
+        """nrep, the transformer rows per sample: [cond ; uncond] on the joint call, the four branches on the conditional call (four_way, which
+        also says: control laid first, the given half teacher-forced, one cfg triple), one row without guidance (cfg=None)"""
+        return 1 if unguided else 4 if four_way else 2
+
+    def _check_unguided(self, four_way: bool, adapter=None, what: str = 'cfg=None'):
+        """what generation without guidance rows does not offer, said on the host before any device work"""
+        if self.sampler == 'torch':
+            raise NotImplementedError(f"{what}: sampler='torch' is not offered (it reproduces the reference's generator calls, and the reference has no "
+                                      "call without guidance rows); set model.sampler = 'counter'")
+        if self.cfg.separate_decoding and not self.cfg.indep and not four_way:
+            raise NotImplementedError(f'{what}: the two-pass separate_decoding branch (control_var.py:428-485) is not offered')
+        if self.cfg.separator:
+            raise NotImplementedError(f'{what}: separator models are not offered (their scale loop lays two guidance rows per sample)')
+        if adapter is not None or getattr(self, '_adapter_bank', None) is not None:
+            raise NotImplementedError(f'{what}: per-request adapters (adapter= / a model with an adapter bank) are not offered without guidance rows - '
+                                      'the bank operands and slots are laid out for [cond ; uncond]; merge one adapter with add_lora, or detach the bank')
 
     @torch.no_grad()
     def _generate(self, B, label_B, g_seed, cfg_scale, top_k, top_p, more_smooth, cond_type, four_way, c_mask, c_img,
-                  force_idx=None, trace: bool = False, gumbel=None, adapter=None, logprobs: bool = False):
-        """-> f_hat, or (f_hat, TokenScores) with logprobs=True"""
+                  force_idx=None, trace: bool = False, gumbel=None, adapter=None, logprobs: bool = False, targets: Optional[dict] = None):
+        """-> f_hat, or (f_hat, TokenScores) with logprobs=True.  cfg_scale=None: generation without guidance rows (nrep == 1).
+        targets (distill_targets=True): the dict _generate_core fills; the call then traces (last_trace holds the combined logits)"""
+        if cfg_scale is None:
+            self._check_unguided(four_way, adapter)
+        if targets is not None:
+            self._check_distill_targets(four_way, more_smooth)
+            trace = True
+        nrep = self._guidance_rows(four_way, cfg_scale is None)
         # adapter= and logprobs=True select the per-request path, as a per-row cfg does
         if adapter is not None or logprobs or _per_request(cfg_scale, top_k, top_p, g_seed, four_way):
             return self._generate_rows(B, label_B, g_seed, cfg_scale, top_k, top_p, more_smooth, cond_type, four_way, c_mask, c_img, force_idx, trace,
-                                       adapter=adapter, logprobs=logprobs)
-        if four_way:
+                                       adapter=adapter, logprobs=logprobs, targets=targets)
+        if four_way and cfg_scale is not None:
             cfg_scale = tuple(cfg_scale)
         if top_k > self.cfg.vocab:                     # helpers.py:8-10: torch.topk raises on k > V; top_k <= 0 means no top-k filter
             raise RuntimeError(f'selected index k out of range (top_k={top_k} > vocabulary {self.cfg.vocab})')
@@ -1741,7 +1796,7 @@ class ControlVAR(nn.Module):
         for name, ids in (('c_mask', c_mask), ('c_img', c_img), ('_force_idx', force_idx)):
             if ids is not None:
                 _check_index_range(torch.cat([t.reshape(-1) for t in ids]), 0, self.cfg.vocab - 1, name)
-        labels_all, types_all = self._prepare_rows(B, label_B, cond_type, four_way, seed)
+        labels_all, types_all = self._prepare_rows(B, label_B, cond_type, four_way, seed, nrep)
         mask_first = self._draw_order(four_way)
         if self.cfg.separator and (four_way or more_smooth or (self.cfg.separate_decoding and not self.cfg.indep)):
             raise NotImplementedError('separator: conditional_infer_cfg ignores the special tokens (control_var.py:270-330), the two-pass branch fails with a '
@@ -1751,7 +1806,7 @@ class ControlVAR(nn.Module):
         if self.cfg.separate_decoding and not self.cfg.indep and not four_way:              # control_var.py:428-485
             f_hat = self._generate_two_pass(B, labels_all, types_all, how, force_idx, trace, mask_first)
         else:
-            f_hat = self._generate_core(B, labels_all, types_all, four_way, how, c_mask, c_img, force_idx, trace, mask_first)
+            f_hat = self._generate_core(B, labels_all, types_all, four_way, how, c_mask, c_img, force_idx, trace, mask_first, nrep=nrep, targets=targets)
         if draws is not None:
             draws.finish()
         return f_hat
@@ -1798,7 +1853,7 @@ class ControlVAR(nn.Module):
 
     @torch.no_grad()
     def _generate_rows(self, B, label_B, g_seed, cfg_scale, top_k, top_p, more_smooth, cond_type, four_way, c_mask, c_img, force_idx=None, trace: bool = False,
-                       adapter=None, logprobs: bool = False):
+                       adapter=None, logprobs: bool = False, targets: Optional[dict] = None):
         """per-request mode (an addition of this library): any of cfg / top_k / top_p / g_seed given per batch row.  Row b produces exactly
         what the scalar call produces at B = 1 with (label_b, cond_type_b, cfg_b, top_k_b, top_p_b, g_seed = seed_b): combined logits, kept-set
         size, margin, ids and image - bit for bit under deterministic_plan=True (the sampler always is; the plan makes the logits independent
@@ -1807,10 +1862,11 @@ class ControlVAR(nn.Module):
         self._check_per_request(label_B, cond_type, four_way, more_smooth)
         if logprobs:
             self._check_logprobs()
-        slots = self._adapter_slots(adapter, B, 4 if four_way else 2)
+        nrep = self._guidance_rows(four_way, cfg_scale is None)
+        slots = self._adapter_slots(adapter, B, nrep)
         table = _request_table(B, cfg_scale, top_k, top_p, g_seed, four_way, self.cfg.vocab, len(self.cfg.pyramid.patch_nums), slots=slots)
         f_hat, scores = self._run_rows(B, label_B, cond_type, four_way, table, c_mask=c_mask, c_img=c_img, force_idx=force_idx, trace=trace,
-                                       logprobs=logprobs, sampled=self._sampled_pattern(four_way, c_mask, c_img, force_idx))
+                                       logprobs=logprobs, sampled=self._sampled_pattern(four_way, c_mask, c_img, force_idx), nrep=nrep, targets=targets)
         return (f_hat, scores) if logprobs else f_hat
 
     def _row_state(self, B: int, table: _RequestTable, logprobs: bool, forced=None, sample: bool = True):
@@ -1825,7 +1881,7 @@ class ControlVAR(nn.Module):
 
     @torch.no_grad()
     def _run_rows(self, B, label_B, cond_type, four_way, table: _RequestTable, *, c_mask=None, c_img=None, force_idx=None, trace: bool = False,
-                  logprobs: bool = False, sampled=None, mask_first: Optional[bool] = None, edit=None, score_halves=None):
+                  logprobs: bool = False, sampled=None, mask_first: Optional[bool] = None, edit=None, score_halves=None, nrep: Optional[int] = None, targets: Optional[dict] = None):
         """the per-request runner behind _generate_rows, edit_infer_cfg and score_infer_cfg: the validated table and the entry point's own extras
         -> (f_hat, TokenScores or None).  mask_first=None draws the (control, image) order (one per call, as the scalar path).
         edit: the host halves (src_ctrl, keep_ctrl, src_img, keep_img) of _edit_half - the forced-token table is built for the drawn order.
@@ -1834,7 +1890,7 @@ class ControlVAR(nn.Module):
         for name, ids in (('c_mask', c_mask), ('c_img', c_img), ('_force_idx', force_idx)):
             if ids is not None:
                 _check_index_range(torch.cat([t.reshape(-1) for t in ids]), 0, self.cfg.vocab - 1, name)
-        labels_all, types_all = self._prepare_rows(B, label_B, cond_type, four_way, 0)
+        labels_all, types_all = self._prepare_rows(B, label_B, cond_type, four_way, 0, nrep)
         if mask_first is None:
             mask_first = self._draw_order(four_way)
         if self.cfg.separator and four_way:
@@ -1852,7 +1908,7 @@ class ControlVAR(nn.Module):
                 force_idx.append((ids.repeat(4, 1) if four_way else ids).contiguous())
                 o += pn * pn
         _, how = self._row_state(B, table, logprobs or score_halves is not None, forced, sample=score_halves is None)
-        f_hat = self._generate_core(B, labels_all, types_all, four_way, how, c_mask, c_img, force_idx, trace, mask_first)
+        f_hat = self._generate_core(B, labels_all, types_all, four_way, how, c_mask, c_img, force_idx, trace, mask_first, nrep=nrep, targets=targets)
         if trace and forced is not None:
             self.last_trace['forced'] = forced
         return f_hat, (self._token_scores(how.score, mask_first, sampled, forced) if how.score is not None else None)
@@ -1882,6 +1938,30 @@ class ControlVAR(nn.Module):
             b += 2 * n
         return col
 
+    def _check_distill_targets(self, four_way: bool, more_smooth=False):
+        """what distill_targets=True does not offer, said on the host before any device work"""
+        if more_smooth:
+            raise NotImplementedError('distill_targets: more_smooth is not offered (the next scale is then fed soft embeddings, not the ids a student '
+                                      'could be teacher-forced along)')
+        if self.cfg.separator:
+            raise NotImplementedError('distill_targets: separator models are not offered (their scales carry special tokens between the halves, which '
+                                      'the (B, L) token layout does not hold)')
+        if self.bidirectional:
+            raise NotImplementedError('distill_targets: bidirectional models are not offered (they draw the order of the halves per call)')
+        if self.cfg.separate_decoding and not self.cfg.indep and not four_way:
+            raise NotImplementedError('distill_targets: the two-pass separate_decoding branch (control_var.py:428-485) is not offered')
+
+    def _distill_targets(self, targets: dict, B: int, sampled) -> DistillTargets:
+        """the filled dict of _generate_core and the trace of the same call -> DistillTargets"""
+        mf, pns, L = self.cfg.mask_factor, self.cfg.pyramid.patch_nums, self.cfg.pyramid.L
+        ids, mask_first = targets['ids'], targets['mask_first']
+        first = torch.cat([i[:, :pn * pn] for i, pn in zip(ids, pns)], dim=1).contiguous()
+        second = torch.cat([i[:, pn * pn:] for i, pn in zip(ids, pns)], dim=1).contiguous() if mf == 2 else None
+        ids_img, ids_ctrl = (first, None) if mf == 1 else (second, first) if mask_first else (first, second)
+        logits = torch.cat(self.last_trace['logits'], dim=1)
+        col = torch.ones(L, dtype=torch.bool) if sampled is None else sampled
+        return DistillTargets(ids_img, ids_ctrl, logits, col.to(self.device)[None].expand(B, -1).contiguous(), mask_first)
+
     def _draw_scale(self, how, logits, B: int, nrep: int, l: int, si: int, ratio: float, ldv: int, cols, tr, force_idx):
         """draw the ids of one scale (sampling call si, at `ratio` of the way through the scales) from its logits, as `how` says (_ScalarDraw /
         _RowDraw) -> (idx (n_draw B, l) int32, the soft embeddings of more_smooth or None).  cols: this scale's columns of the (B, L) tables.
@@ -1904,9 +1984,11 @@ class ControlVAR(nn.Module):
             if nrep == 4:
                 t1, t2, t3 = [c * ratio for c in how.cfg]
                 coef = [1 + t1, t2 - t1, t3 - t2, -t3]
-            else:
+            elif nrep == 2:
                 t = how.cfg * ratio
                 coef = [1 + t, -t]
+            else:
+                coef = [1.0]                                             # no guidance rows: the combined logits are the row's own
             expo, g_si = self._torch_noise(how.draws, n_draw * B, l, how.more_smooth)
             smooth = {}
             if how.more_smooth and how.top_k != 1:
@@ -1925,9 +2007,12 @@ class ControlVAR(nn.Module):
 
     @torch.no_grad()
     def _generate_core(self, B, labels_all, types_all, four_way, how, c_mask=None, c_img=None, force_idx=None, trace: bool = False,
-                       mask_first: bool = True):
+                       mask_first: bool = True, nrep: Optional[int] = None, targets: Optional[dict] = None):
         """the 10-scale loop on device-resident inputs only (capturable in a HIP graph: no host sync, static shapes).
-        how: a _ScalarDraw, or a _RowDraw (per-request mode) with what rides on it - the forced-token table, the adapters, the score buffers."""
+        how: a _ScalarDraw, or a _RowDraw (per-request mode) with what rides on it - the forced-token table, the adapters, the score buffers.
+        nrep: the transformer rows per sample (_guidance_rows; None: 4 or 2 by four_way) - 1 runs R = B rows through every pass and the arena.
+        targets (distill_targets): a dict that receives 'ids', per scale the ids the first branch continues with (B, l), after the overwrites,
+        and 'mask_first', the order they are laid in."""
         row = isinstance(how, _RowDraw)
         if row and not how.sample and (how.score is None or force_idx is None or trace):
             raise ValueError('score_only: score buffers and force_idx are required')
@@ -1938,9 +2023,10 @@ class ControlVAR(nn.Module):
         vae: VQVAE = self.vae_proxy[0]
         py, mf, C = cfg.pyramid, cfg.mask_factor, cfg.C
         dev = self.device
-        nrep = 4 if four_way else 2
+        nrep = self._guidance_rows(four_way) if nrep is None else nrep
         R = nrep * B
-        nb = R if four_way else B
+        n_draw = nrep if four_way else 1                                 # the conditional call draws (and continues) every branch on its own ids
+        nb = n_draw * B
         x = torch.empty(R * py.l[-1], C, device=dev, dtype=torch.float32)
         cond = torch.empty(R, C, device=dev, dtype=torch.float32)
         self._first_tokens(P, labels_all, types_all, x, cond, R, py.first_l, P['lvl_pos'], mask_first)
@@ -1950,6 +2036,8 @@ class ControlVAR(nn.Module):
         S = py.patch_nums[-1]
         f_hat = torch.zeros(nb, mf, cfg.cvae, S, S, device=dev, dtype=torch.float32)
         tr = {'idx': [], 'margin': [], 'logits': []} if trace else None
+        if targets is not None:
+            targets.update(ids=[], mask_first=mask_first)
         nstage = len(py.patch_nums)
         # `indep` models hand the rows of the training mask to every inference pass (control_var.py:283,497); those rows hide something
         # only under separate_decoding (otherwise every cached key is visible anyway)
@@ -1961,10 +2049,13 @@ class ControlVAR(nn.Module):
             cols = slice(py.begin[si], py.end[si])
             idx, soft = self._draw_scale(how, logits, B, nrep, l, si, ratio, cfg.head_ld, cols, tr, force_idx)
             if four_way:                                                 # teacher forcing (control_var.py:309-324)
+                nf = 3 if nrep == 4 else 1                               # the branches that see the given half: three of four, or the one there is
                 if c_mask is not None:
-                    idx[:3 * B, :pn * pn] = c_mask[si].to(device=dev, dtype=torch.int32).repeat(3, 1)
+                    idx[:nf * B, :pn * pn] = c_mask[si].to(device=dev, dtype=torch.int32).repeat(nf, 1)
                 if c_img is not None:
-                    idx[:3 * B, pn * pn:] = c_img[si].to(device=dev, dtype=torch.int32).repeat(3, 1)
+                    idx[:nf * B, pn * pn:] = c_img[si].to(device=dev, dtype=torch.int32).repeat(nf, 1)
+            if targets is not None:
+                targets['ids'].append(idx[:B].clone())
             if score is not None:
                 ops.score_rows(logits, B, nrep, l, cfg.vocab, how.rows[3][si], idx[:B], None, score[0][:, cols], score[1][:, cols], score[2][:, cols],
                                score[3][:, cols], ldv=cfg.head_ld)
@@ -1988,7 +2079,7 @@ class ControlVAR(nn.Module):
                 x[:R * ln].view(R, ln, C)[:, [cut, ln - 1]] = self._special_rows(gen_table, [py.end[si] + cut, py.end[si] + ln - 1], [mapping[2 * si], mapping[2 * si + 1]])
             elif si != nstage - 1:
                 ln = py.l[si + 1]
-                ops.word_embed(tok, P['w_we'], P['b_we'], gen_table, x, nb, 1 if four_way else 2, ln,
+                ops.word_embed(tok, P['w_we'], P['b_we'], gen_table, x, nb, nrep // n_draw, ln,
                                cfg.cvae, C, ln, 0, lvl_off=py.end[si])
         if trace:
             tr['f_hat'] = f_hat[:B].clone()
@@ -2091,7 +2182,8 @@ class ControlVAR(nn.Module):
         returns (images, TokenScores) - copies, as the images are.  sampled: the (L,) host pattern of the sampled tokens (None: all); an edit
         graph (forced, the forced-token table) reads it off that table instead"""
         dev, vocab, nstage = self.device, self.cfg.vocab, len(self.cfg.pyramid.patch_nums)
-        nrep = 4 if four_way else 2
+        unguided = cfg is None                               # captured without guidance rows: labels_all / types_all hold B rows, and so does every replay
+        nrep = self._guidance_rows(four_way, unguided)
         if per_request:
             slots0 = self._adapter_slots(-1, B, nrep) if adapters else None
             table0 = _request_table(B, cfg, top_k, top_p, 0, four_way, vocab, nstage, slots=slots0)     # also validates the defaults
@@ -2103,7 +2195,7 @@ class ControlVAR(nn.Module):
         def body():
             if prologue is not None:
                 prologue()
-            return finish(self._generate_core(B, labels_all, types_all, four_way, how, **(teach or {})))
+            return finish(self._generate_core(B, labels_all, types_all, four_way, how, nrep=nrep, **(teach or {})))
 
         graph, out, owned = self._capture(body)
 
@@ -2116,6 +2208,9 @@ class ControlVAR(nn.Module):
             # everything that can refuse runs before the first static buffer is written
             if per_request:
                 self._check_per_request(label_B, cond_type, four_way)
+                if (request['cfg'] is None) != unguided:
+                    raise ValueError('run() got cfg=None: this graph was captured with guidance rows - capture it with cfg=None' if not unguided else
+                                     f'run() got cfg={request["cfg"]!r}: this graph was captured with cfg=None and holds no guidance rows to weigh')
                 adapter = request['adapter']
                 if adapter is not None and not adapters:
                     raise TypeError('run() got adapter=: this graph was captured without adapters=True, so it holds none of the adapter launches - '
@@ -2123,7 +2218,7 @@ class ControlVAR(nn.Module):
                 slots = self._adapter_slots(-1 if adapter is None else adapter, B, nrep) if adapters else None
                 check_shapes(label_B, cond_type)
                 table = _request_table(B, request['cfg'], request['top_k'], request['top_p'], g_seed, four_way, vocab, nstage, slots=slots)
-                la, ta = self._prepare_rows(B, label_B, cond_type, four_way, 0)
+                la, ta = self._prepare_rows(B, label_B, cond_type, four_way, 0, nrep)
                 copy_given = refresh(given) if refresh is not None else None
             else:
                 _refuse_request_keywords(g_seed, request)
@@ -2131,7 +2226,7 @@ class ControlVAR(nn.Module):
                     check_shapes(label_B, cond_type)
                 copy_given = refresh(given) if refresh is not None else None
                 seed = int(g_seed) if g_seed is not None else int(torch.empty((), dtype=torch.int64).random_().item())
-                la, ta = self._prepare_rows(B, label_B, cond_type, four_way, seed)
+                la, ta = self._prepare_rows(B, label_B, cond_type, four_way, seed, nrep)
             labels_all.copy_(la)
             if types_all is not None:
                 types_all.copy_(ta)
@@ -2191,6 +2286,8 @@ class ControlVAR(nn.Module):
         logprobs=True (with per_request=True): the graph holds the score launches and the (B, L) score buffers, and run returns
         (images, TokenScores) as autoregressive_infer_cfg(logprobs=True) does."""
         four_way = False
+        if cfg is None:                                     # cfg=None: the captured loop runs B rows, as autoregressive_infer_cfg(cfg=None); run takes cfg=None only
+            self._check_unguided(four_way, True if adapters else None, 'graphed_generator(cfg=None)')
         self._check_graph_adapters(per_request, adapters)
         self._check_graph_logprobs(per_request, logprobs, four_way)
         if self.sampler == 'torch':
@@ -2200,7 +2297,7 @@ class ControlVAR(nn.Module):
             raise NotImplementedError('the captured generator fixes the (control, image) order; bidirectional models draw it per call')
         lab0 = torch.zeros(B, dtype=torch.int64)
         ty0 = torch.zeros(B, dtype=torch.int64) if self.cfg.mask_factor == 2 else None
-        labels_all, types_all = self._prepare_rows(B, lab0, ty0, four_way, 0)
+        labels_all, types_all = self._prepare_rows(B, lab0, ty0, four_way, 0, self._guidance_rows(four_way, cfg is None))
         inner = self._graph_runner(B, four_way, labels_all, types_all, cfg, top_k, top_p, self._decode_pair, per_request=per_request, adapters=adapters,
                                    logprobs=logprobs, check_rows=False)
         if per_request:
@@ -2231,6 +2328,8 @@ class ControlVAR(nn.Module):
         logprobs=True (with per_request=True): run returns (images, TokenScores) as conditional_infer_cfg(logprobs=True) does."""
         if self.mask_factor != 2:
             raise NotImplementedError('graphed_conditional_generator needs mask_factor == 2 (control_var.py:333)')
+        if cfg is None:                                     # cfg=None: the captured loop runs B rows, as conditional_infer_cfg(cfg=None)
+            self._check_unguided(True, True if adapters else None, 'graphed_conditional_generator(cfg=None)')
         self._check_graph_adapters(per_request, adapters)
         self._check_graph_logprobs(per_request, logprobs, True)
         if self.sampler == 'torch':
@@ -2245,19 +2344,21 @@ class ControlVAR(nn.Module):
         if int(B) != B or B < 1:
             raise ValueError(f'B={B!r}: a positive batch size')
         if not per_request:                                 # per_request: _request_table checks the defaults, which may come per row
-            try:
-                cfg = tuple(float(c) for c in cfg)
-            except TypeError:
-                cfg = ()
-            if len(cfg) != 3:
-                raise ValueError('cfg: three guidance scales (t1, t2, t3) as in conditional_infer_cfg')
+            if cfg is not None:
+                try:
+                    cfg = tuple(float(c) for c in cfg)
+                except TypeError:
+                    cfg = ()
+                if len(cfg) != 3:
+                    raise ValueError('cfg: three guidance scales (t1, t2, t3) as in conditional_infer_cfg')
             if top_k > self.cfg.vocab:                      # as _generate (helpers.py:8-10)
                 raise RuntimeError(f'selected index k out of range (top_k={top_k} > vocabulary {self.cfg.vocab})')
         dev = self.device
         vae: VQVAE = self.vae_proxy[0]
         pns = self.cfg.pyramid.patch_nums
         Ltot, side_px = sum(pn * pn for pn in pns), 16 * pns[-1]
-        labels_all, types_all = self._prepare_rows(B, torch.zeros(B, dtype=torch.int64), torch.zeros(B, dtype=torch.int64), True, 0)
+        labels_all, types_all = self._prepare_rows(B, torch.zeros(B, dtype=torch.int64), torch.zeros(B, dtype=torch.int64), True, 0,
+                                                   self._guidance_rows(True, cfg is None))
         ids_buf = torch.zeros(B, Ltot, device=dev, dtype=torch.int32)
         pix_buf = torch.zeros(B, 3, side_px, side_px, device=dev, dtype=torch.float32) if source == 'pixels' else None
         ids_Bl = vae._split(ids_buf)                        # per-scale views of the static buffer: what _generate_core teacher-forces from
@@ -2322,6 +2423,8 @@ class ControlVAR(nn.Module):
         separator models are refused.  adapter: one adapter id per row or one int, as in autoregressive_infer_cfg (lora.attach_adapters).
         logprobs=True: returns (images, TokenScores) as autoregressive_infer_cfg does; `sampled` is False at the kept tokens, which are scored too."""
         self._check_edit(label_B, cond_type, more_smooth)
+        if cfg is None:
+            raise NotImplementedError(_NO_UNGUIDED.format('edit_infer_cfg'))
         pns = self.cfg.pyramid.patch_nums
         s_ctrl, k_ctrl = _edit_half('ctrl', src_ctrl, keep_ctrl, B, pns, self.cfg.vocab) if self.cfg.mask_factor == 2 else (None, None)
         s_img, k_img = _edit_half('img', src_img, keep_img, B, pns, self.cfg.vocab)
@@ -2348,6 +2451,8 @@ class ControlVAR(nn.Module):
         if given not in (None, 'control', 'image'):
             raise ValueError(f"given={given!r}: None (the joint path), 'control' or 'image'")
         four_way, mf = given is not None, self.cfg.mask_factor
+        if cfg is None:
+            raise NotImplementedError(_NO_UNGUIDED.format('score_infer_cfg'))
         if four_way and mf != 2:
             raise NotImplementedError("score_infer_cfg(given=...) needs mask_factor == 2, as conditional_infer_cfg (control_var.py:333)")
         self._check_per_request(label_B, cond_type, four_way)
@@ -2384,6 +2489,8 @@ class ControlVAR(nn.Module):
         cfg / top_k / top_p given here are the defaults of run; each and g_seed is a scalar or per row.  Everything is validated on the host
         before the first static buffer is written: a refused run leaves the graph as it was.  Bidirectional models are refused as
         graphed_generator refuses them.  logprobs=True: run returns (images, TokenScores) as edit_infer_cfg(logprobs=True) does."""
+        if cfg is None:
+            raise NotImplementedError(_NO_UNGUIDED.format('graphed_edit_generator'))
         if self.sampler == 'torch':
             raise NotImplementedError("graphed_edit_generator captures the counter sampler only: sampler='torch' draws its noise with torch on model.rng "
                                       "between the launches; set model.sampler = 'counter' to capture")
@@ -2448,6 +2555,14 @@ class ControlVAR(nn.Module):
         """what the public generation calls return: the decoded images, or (images, scores) under logprobs=True"""
         return self._decode_pair(f_hat) if scores is None else (self._decode_pair(f_hat), scores)
 
+    def _results(self, B: int, out, logprobs: bool, targets: Optional[dict], sampled):
+        """_generate's result -> what the public call returns: images, (images, scores), and the DistillTargets behind them when asked for"""
+        images = self._images(*out) if logprobs else self._images(out)
+        if targets is None:
+            return images
+        t = self._distill_targets(targets, B, sampled)
+        return (*images, t) if logprobs else (images, t)
+
     def _decode_pair(self, f_hat: torch.Tensor) -> torch.Tensor:
         vae: VQVAE = self.vae_proxy[0]
         B, mf = f_hat.shape[:2]
@@ -2463,7 +2578,8 @@ class ControlVAR(nn.Module):
     # ---- public API
     @torch.no_grad()
     def autoregressive_infer_cfg(self, B: int, label_B, g_seed: Optional[int] = None, cfg=1.5, top_k=0, top_p=0.0,
-                                 more_smooth=False, cond_type=None, _force_idx=None, _trace=False, _gumbel=None, adapter=None, logprobs: bool = False):
+                                 more_smooth=False, cond_type=None, _force_idx=None, _trace=False, _gumbel=None, adapter=None, logprobs: bool = False,
+                                 distill_targets: bool = False):
         """control_var.py:356-565: returns (B, 3, 2 H, H) in [0,1] with H = 16 patch_nums[-1] - (B, 3, 512, 256) for the default list, (B, 3, 1024, 512) for
         PATCH_NUMS_512 (control image on top, RGB below).
         more_smooth: Gumbel-softmax soft code embeddings (:511-515); `_gumbel` (tests) injects the per-pass noise instead of drawing it.
@@ -2472,23 +2588,35 @@ class ControlVAR(nn.Module):
         logprobs=True (an addition of this library): returns (images, scores), scores a TokenScores - log-probability, entropy and rank of every
         token of the returned sample and the greedy id beside it, (B, L) each, from one more launch per scale (cvar_score_rows).  The
         log-probabilities are those of the UNFILTERED CFG-combined distribution: the top-k / top-p kept set is not renormalised over.  Selects the
-        per-request path as adapter= does (scalars are broadcast), so its refusals apply; ids and images are bit-identical with and without it."""
+        per-request path as adapter= does (scalars are broadcast), so its refusals apply; ids and images are bit-identical with and without it.
+        cfg=None (an addition of this library): generation WITHOUT guidance rows, for a guidance-distilled student - one transformer
+        row and one K/V arena row per sample instead of two; under deterministic_plan=True it returns the bits of cfg=0.0, which computes the
+        unconditional rows and weighs them by zero.  sampler='torch', the two-pass separate_decoding branch, separator models and adapters
+        are refused.
+        distill_targets=True (likewise): the call traces and additionally returns a DistillTargets as its last value - the ids and the guided
+        logits of the sample, in the forms Trainer.step_tokens(distill=...) takes.  more_smooth, separator and bidirectional models are refused."""
+        tg = {} if distill_targets else None
         out = self._generate(B, label_B, g_seed, cfg, top_k, top_p, more_smooth, cond_type, False, None, None, _force_idx, _trace, _gumbel, adapter=adapter,
-                             logprobs=logprobs)
-        return self._images(*out) if logprobs else self._images(out)
+                             logprobs=logprobs, targets=tg)
+        return self._results(B, out, logprobs, tg, self._sampled_pattern(False, None, None, _force_idx))
 
     @torch.no_grad()
     def conditional_infer_cfg(self, B: int, label_B, g_seed: Optional[int] = None, cfg=(1.5, 1.5, 1.5), top_k=0, top_p=0.0,
                               more_smooth=False, cond_type=None, c_mask=None, c_img=None, _force_idx=None, _trace=False, _gumbel=None,
-                              adapter=None, logprobs: bool = False):
+                              adapter=None, logprobs: bool = False, distill_targets: bool = False):
         """control_var.py:223-354: 4-branch CFG with teacher forcing of the control (c_mask) or image (c_img) ids.
         logprobs=True: returns (images, TokenScores) as autoregressive_infer_cfg does (the unfiltered combined distribution of the four branches;
-        tokens in control-first order); `sampled` is False along the teacher-forced half, which is scored too."""
+        tokens in control-first order); `sampled` is False along the teacher-forced half, which is scored too.
+        cfg=None: generation without guidance rows, as autoregressive_infer_cfg's - one row per sample instead of four, the given half
+        teacher-forced into it; the bits of cfg=(0, 0, 0) under deterministic_plan=True.
+        distill_targets=True: additionally returns a DistillTargets; its ids are those the first branch continued with (the given half where it
+        was forced), and `sampled` is False along that half."""
         if self.mask_factor != 2:
             raise NotImplementedError('conditional_infer_cfg needs mask_factor == 2 (control_var.py:333)')
+        tg = {} if distill_targets else None
         out = self._generate(B, label_B, g_seed, cfg, top_k, top_p, more_smooth, cond_type, True, c_mask, c_img, _force_idx, _trace, _gumbel, adapter=adapter,
-                             logprobs=logprobs)
-        return self._images(*out) if logprobs else self._images(out)
+                             logprobs=logprobs, targets=tg)
+        return self._results(B, out, logprobs, tg, self._sampled_pattern(True, c_mask, c_img, _force_idx))
 
     def forward(self, label_B: torch.LongTensor, x_BLCv_wo_first_l: torch.Tensor, cond_type=None, mask_first=True) -> torch.Tensor:
         """control_var.py:568-651 teacher-forced logits (B, L, V) fp32.  Under autograd (grad mode on and trainable
@@ -2554,11 +2682,13 @@ class VAR(ControlVAR):
 
     @torch.no_grad()
     def autoregressive_infer_cfg(self, B: int, label_B, g_seed: Optional[int] = None, cfg=1.5, top_k=0, top_p=0.0,
-                                 more_smooth=False, _force_idx=None, _trace=False, adapter=None, logprobs: bool = False):
+                                 more_smooth=False, _force_idx=None, _trace=False, adapter=None, logprobs: bool = False, distill_targets: bool = False):
         """var.py:143-207: returns (B, 3, H, H) in [0,1], H = 16 patch_nums[-1] (256, or 512 with PATCH_NUMS_512).
-        logprobs=True: (images, TokenScores), as ControlVAR.autoregressive_infer_cfg."""
-        out = self._generate(B, label_B, g_seed, cfg, top_k, top_p, more_smooth, None, False, None, None, _force_idx, _trace, adapter=adapter, logprobs=logprobs)
-        return self._images(*out) if logprobs else self._images(out)
+        logprobs=True: (images, TokenScores), as ControlVAR.autoregressive_infer_cfg; cfg=None and distill_targets=True likewise."""
+        tg = {} if distill_targets else None
+        out = self._generate(B, label_B, g_seed, cfg, top_k, top_p, more_smooth, None, False, None, None, _force_idx, _trace, adapter=adapter, logprobs=logprobs,
+                             targets=tg)
+        return self._results(B, out, logprobs, tg, self._sampled_pattern(False, None, None, _force_idx))
 
     @torch.no_grad()
     def edit_infer_cfg(self, B: int, label_B, *, src_img=None, keep_img=None, g_seed=None, cfg=1.5, top_k=0, top_p=0.0, trace: bool = False,

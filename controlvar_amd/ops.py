@@ -672,6 +672,13 @@ def pg_fwd_bwd(logits, target, adv, weight, old_lp, ref_lp, clip_lo, clip_hi, kl
                                       _ptr(dlogits), dt(dlogits) if dlogits is not None else CVAR_F32, M, V, _stream()), 'cvar_pg_fwd_bwd')
 
 
+def kd_fwd_bwd(logits, teacher, ldt, weight, gscale, loss_tok, dlogits, M, V):
+    """the soft-target loss on the rows cvar_ce_fwd_bwd takes (cvar_kd_fwd_bwd, include/cvar_distill.h): teacher logits [M][ldt] fp32 in the place
+    of the target ids; weight and dlogits may be None"""
+    check(_lib.load().cvar_kd_fwd_bwd(_ptr(logits), _ptr(teacher), int(ldt), _ptr(weight), float(gscale), _ptr(loss_tok), _ptr(dlogits),
+                                      dt(dlogits) if dlogits is not None else CVAR_F32, M, V, _stream()), 'cvar_kd_fwd_bwd')
+
+
 def scatter_add_rows(src, ld_src, idx, dst, n, Cdim, src_off: int = 0):
     check(_lib.load().cvar_scatter_add_rows(_ptr(src) + 4 * src_off, ld_src, _ptr(idx), _ptr(dst), n, Cdim, _stream()), 'cvar_scatter_add_rows')
 

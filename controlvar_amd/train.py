@@ -205,6 +205,47 @@ class PolicyLoss:
         return tuple(out)
 
 
+_NO_SEPARATOR = ('training on token ids: separator models are not offered (their label row carries special tokens between the '
+                 'halves, which the (B, L) token layout does not hold)')
+
+
+@dataclass
+class DistillLoss:
+    """The soft-target loss of a training step on token ids (cvar_kd_fwd_bwd, include/cvar_distill.h), in the place of the
+    cross-entropy: per token KL(softmax(teacher logits) || model), with gradient (p - q) * weight * gscale in the model's logits.
+    logits   (B, L, V) fp32 on the device: the teacher's logits of every token - for guidance distillation the guided combination
+             sum_k coef_k * logits_k a generation call returns as DistillTargets.logits - V == cfg.vocab;
+    weights  (B, L) token weights, or None = 1; they take ignore_mask's place (loss normalisation included), so the two exclude each other.
+    Both are in the token order of the training labels: per scale the two halves, control first when mask_first (TokenScores).
+    A student is trained with cond_drop_rate = 0: it learns the guided distribution of the condition it is given, and a dropped condition
+    would pair the teacher's guided row with an unconditional student row.
+    The types are checked on the host when the object is built, the shapes against the batch by check()."""
+    logits: torch.Tensor
+    weights: Optional[torch.Tensor] = None
+
+    def __post_init__(self):
+        t = self.logits
+        if not torch.is_tensor(t) or t.dtype != torch.float32:
+            raise ValueError(f'logits: expected a float32 tensor, got {type(t).__name__ if not torch.is_tensor(t) else t.dtype}')
+        if t.dim() != 3:
+            raise ValueError(f'logits: expected (B, L, V), got {tuple(t.shape)}')
+        w = self.weights
+        if w is not None:
+            if not torch.is_tensor(w) or w.dtype not in (torch.bool, torch.float32, torch.float64, torch.bfloat16, torch.float16):
+                raise ValueError(f'weights: expected a floating-point or bool tensor, got {type(w).__name__ if not torch.is_tensor(w) else w.dtype}')
+            if w.dim() != 2:
+                raise ValueError(f'weights: expected (B, L), got {tuple(w.shape)}')
+
+    def check(self, B: int, L: int, V: int, device=None):
+        """the shapes (and the device) against a batch of B samples of L tokens over V classes (host only)"""
+        if tuple(self.logits.shape) != (B, L, V):
+            raise ValueError(f'logits: expected shape {(B, L, V)}, got {tuple(self.logits.shape)}')
+        if device is not None and self.logits.device.type != torch.device(device).type:
+            raise ValueError(f'logits: expected on {device}, got {self.logits.device} (teacher logits are not copied between devices)')
+        if self.weights is not None and tuple(self.weights.shape) != (B, L):
+            raise ValueError(f'weights: expected shape {(B, L)}, got {tuple(self.weights.shape)}')
+
+
 def _ln_rows(C: int):
     """the adaLN forward of rows of C channels: above 2048 the entry point of include/cvar_wide.h; narrow models call ops.ln_modulate exactly as before"""
     return ops.ln_modulate_wide if C > 2048 else ops.ln_modulate
@@ -455,14 +496,30 @@ class TrainEngine:
     @torch.no_grad()
     def forward_backward(self, label_B: torch.Tensor, x_wo_first: torch.Tensor, cond_type: Optional[torch.Tensor], targets: torch.Tensor,
                          ignore_mask: Optional[torch.Tensor] = None, drop_seed: Optional[int] = None, mask_first: bool = True,
-                         accumulate: bool = False, policy: Optional[PolicyLoss] = None):
+                         accumulate: bool = False, policy: Optional[PolicyLoss] = None, distill: Optional[DistillLoss] = None):
         """-> (loss scalar tensor, per-token loss (B*L,)); gradients land in self.grads(): overwritten, or with accumulate=True added to what
         it holds - fp32(old + this micro-batch's plain gradient) per element, whatever the batch size of the earlier calls.  The loss and its
         1 / M scale are this micro-batch's own; the 1 / N of a window of N belongs to the optimizer's gradient scale (FusedAdamW.step).
         policy: the clipped policy-gradient loss in the place of the cross-entropy (PolicyLoss) - one other loss launch on the
-        same logits and dlogits, nothing else; the per-token logprob, ratio, clipped, kl and coef stay on the engine as self.policy_out."""
+        same logits and dlogits, nothing else; the per-token logprob, ratio, clipped, kl and coef stay on the engine as self.policy_out.
+        distill: the soft-target loss in the place of the cross-entropy (DistillLoss) - likewise one other loss launch; `targets`
+        is not read, distill.weights stands where ignore_mask stands, and the returned per-token loss is the token's KL(teacher || model)."""
         if policy is not None:
             policy.check(x_wo_first.shape[0], self.L)                 # refused before any device work
+        if distill is not None:                                      # likewise
+            if policy is not None:
+                raise ValueError('distill and policy: a step has one loss - the soft-target loss or the policy-gradient loss')
+            if not isinstance(distill, DistillLoss):
+                raise TypeError(f'distill: a DistillLoss, got {type(distill).__name__}')
+            if distill.weights is not None and ignore_mask is not None:
+                raise ValueError('distill.weights and ignore_mask: the weights take the place of ignore_mask - fold the two into one and pass it as weights')
+            if self.cfg.separator:
+                raise NotImplementedError(_NO_SEPARATOR)
+            if self.cfg.vocab != self.V:
+                raise NotImplementedError(f'distill: the head is {self.V} columns wide for a vocabulary of {self.cfg.vocab}; teacher logits are (B, L, vocab)')
+            distill.check(x_wo_first.shape[0], self.L, self.cfg.vocab, self.var.device)
+            if distill.weights is not None:
+                ignore_mask = distill.weights
         self.forward_train(label_B, x_wo_first, cond_type, drop_seed, mask_first)
         dev = self.var.device
         M, V = self.M, self.V
@@ -472,7 +529,9 @@ class TrainEngine:
             gscale = 1.0 / (M * (float(w.mean()) + 1e-6))
         else:
             w, gscale = None, 1.0 / M
-        if policy is None:
+        if distill is not None:
+            ops.kd_fwd_bwd(self.logits, distill.logits.contiguous(), V, w, gscale, self.loss_tok, self.dlogits, M, V)
+        elif policy is None:
             ops.ce_fwd_bwd(self.logits, tg, w, gscale, self.loss_tok, self.dlogits, M, V)
         else:
             adv, old, ref = policy.rows(self._saved['B'], self.L, dev)
@@ -1076,7 +1135,8 @@ class Trainer:
             mask_first = not (getattr(self.var, 'bidirectional', False) and random.random() < 0.5)
         return self._micro_batch(lambda: self.tokenize(images, masks, mask_first), cls, types, ignore_mask, drop_seed, mask_first)
 
-    def _micro_batch(self, inputs, cls, types, ignore_mask, drop_seed, mask_first: bool, policy: Optional[PolicyLoss] = None) -> Dict[str, object]:
+    def _micro_batch(self, inputs, cls, types, ignore_mask, drop_seed, mask_first: bool, policy: Optional[PolicyLoss] = None,
+                     distill: Optional[DistillLoss] = None) -> Dict[str, object]:
         """one micro-batch of the window on the (x, labels) that inputs() returns: schedule, forward + backward, and - when it closes the window -
         all-reduce, clipping, AdamW.  The body of step() and of step_tokens()"""
         micro, accumulate, sync = self.window.begin()
@@ -1091,7 +1151,7 @@ class Trainer:
             self.engine.reducer = self._reducer
         else:
             self.engine.reducer = None
-        loss, _ = self.engine.forward_backward(cls, x, types, labels, ignore_mask, drop_seed, mask_first, accumulate=accumulate, policy=policy)
+        loss, _ = self.engine.forward_backward(cls, x, types, labels, ignore_mask, drop_seed, mask_first, accumulate=accumulate, policy=policy, distill=distill)
         extra = self._policy_report(x.shape[0], ignore_mask) if policy is not None else {}
         n = self.window.n
         if n > 1:
@@ -1126,8 +1186,7 @@ class Trainer:
         from .models import _check_index_range, _flat_ids
         cfg = self.var.cfg
         if cfg.separator:
-            raise NotImplementedError('training on token ids: separator models are not offered (their label row carries special tokens between the '
-                                      'halves, which the (B, L) token layout does not hold)')
+            raise NotImplementedError(_NO_SEPARATOR)
         bidir = bool(getattr(self.var, 'bidirectional', False))
         if mask_first is None:
             if bidir:
@@ -1162,13 +1221,17 @@ class Trainer:
 
     @torch.no_grad()
     def step_tokens(self, ids_img, ids_ctrl, cls, types, *, ignore_mask=None, policy: Optional[PolicyLoss] = None, drop_seed=None,
-                    mask_first: Optional[bool] = None) -> Dict[str, object]:
+                    mask_first: Optional[bool] = None, distill: Optional[DistillLoss] = None) -> Dict[str, object]:
         """step() on token ids instead of pixels: one micro-batch with step()'s window, schedule, all-reduce, clipping and return dict, without
         the tokenizer.  ids_img / ids_ctrl: each half's multi-scale ids in the forms score_infer_cfg takes - the list of (B, pn^2) tensors
         vae.img_to_idxBl returns or one (B, sum pn^2) tensor - so a sampled sequence or a pre-tokenised dataset trains as it is; ids_ctrl=None
         for a plain VAR.  On the ids of tokenize() the step equals step() on the pixels bit for bit.
         policy: a PolicyLoss replaces the cross-entropy by the clipped policy-gradient loss; the dict then also carries mean_ratio, clip_frac,
         mean_kl (device scalars over the tokens that count) and token_logprob (B, L) in TokenScores' token order.
+        distill: a DistillLoss replaces the cross-entropy by KL(teacher || model) on the teacher logits it carries; the ids
+        are then the model's inputs only, `loss` is the weighted mean KL, distill.weights stands where ignore_mask stands (not both) and
+        policy is excluded.  DistillTargets.loss() of a generation call with distill_targets=True is such an object; the student is trained
+        with cond_drop_rate = 0.
         Shapes and the id range are checked on the host before any device work.  Separator models are refused; a bidirectional model needs
         mask_first said (True: these ids go control first)."""
         both, B, mask_first = self._check_tokens(ids_img, ids_ctrl, cls, types, mask_first)
@@ -1176,9 +1239,19 @@ class Trainer:
             if not isinstance(policy, PolicyLoss):
                 raise TypeError(f'policy: a PolicyLoss, got {type(policy).__name__}')
             policy.check(B, self.var.cfg.pyramid.L)
+        if distill is not None:
+            if policy is not None:
+                raise ValueError('distill and policy: a step has one loss - the soft-target loss or the policy-gradient loss')
+            if not isinstance(distill, DistillLoss):
+                raise TypeError(f'distill: a DistillLoss, got {type(distill).__name__}')
+            if distill.weights is not None and ignore_mask is not None:
+                raise ValueError('distill.weights and ignore_mask: the weights take the place of ignore_mask - fold the two into one and pass it as weights')
+            if self.var.cfg.vocab != self.var.cfg.head_ld:
+                raise NotImplementedError(f'distill: the head is {self.var.cfg.head_ld} columns wide for a vocabulary of {self.var.cfg.vocab}; teacher logits are (B, L, vocab)')
+            distill.check(B, self.var.cfg.pyramid.L, self.var.cfg.vocab, self.var.device)
         if ignore_mask is not None and ignore_mask.numel() != B * self.var.cfg.pyramid.L:
             raise ValueError(f'ignore_mask: expected {B} x {self.var.cfg.pyramid.L} token weights, got {tuple(ignore_mask.shape)}')
-        return self._micro_batch(lambda: self._inputs_of(both, B, mask_first), cls, types, ignore_mask, drop_seed, mask_first, policy)
+        return self._micro_batch(lambda: self._inputs_of(both, B, mask_first), cls, types, ignore_mask, drop_seed, mask_first, policy, distill)
 
     @torch.no_grad()
     def token_logprobs(self, ids_img, ids_ctrl, cls, types, *, drop_seed=None, mask_first: Optional[bool] = None) -> torch.Tensor:
