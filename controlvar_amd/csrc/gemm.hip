@@ -1018,6 +1018,7 @@ __device__ __forceinline__ void cvar_gemm_tile(const GemmParams& p, const int vb
                     float x = v[e];
                     if (p.bias) x += p.bias[n + e];
                     if (p.C2) st_any(p.C2, ES == 2 ? CVAR_BF16 : CVAR_F32, cz + (long)m * p.ldc + n + e, x);
+                    if (scale_split) x *= p.split_alpha;         // a bias or batch stride off the 16-byte grid brings a split call here (cvar_gemm checks C, C_split and the widths only)
                     if (p.act == CVAR_ACT_GELU_TANH) x = gelu_tanh_f(x);
                     else if (p.act == CVAR_ACT_GELU_GRAD) x *= gelu_tanh_grad(ld_any(p.aux, p.out_dtype, cz + (long)m * p.ldc + n + e));
                     if (grow) x *= grow[n + e] * (p.gate_scale ? p.gate_scale[fast_div(m, p.gate_magic, p.gate_shift)] : 1.0f);
