@@ -1,4 +1,4 @@
-"""ctypes binding of libcvar_hip.so (include/cvar.h, include/cvar_serve.h, include/cvar_accum.h, include/cvar_kvcache.h, include/cvar_wide.h, include/cvar_policy.h, include/cvar_distill.h).  No torch types cross this boundary:
+"""ctypes binding of libcvar_hip.so (include/cvar.h, include/cvar_serve.h, include/cvar_accum.h, include/cvar_kvcache.h, include/cvar_wide.h, include/cvar_policy.h, include/cvar_distill.h, include/cvar_region.h).  No torch types cross this boundary:
 callers hand over raw device pointers (``tensor.data_ptr()``), sizes and the HIP stream handle.
 
 The library is mandatory on the product path: if it is missing or does not load, every op
@@ -169,6 +169,14 @@ DISTILL_SIGNATURES = {
     'cvar_kd_fwd_bwd': (c_i, [c_p, c_p, c_i, c_p, c_f, c_p, c_p, c_i, c_l, c_i, c_p]),
 }
 
+# include/cvar_region.h: regional guidance - the per-token weight table and the sampler / score launches that read it.  A table of its
+# own for the same reason; no signature of the other seven headers changed, so neither version moved
+REGION_SIGNATURES = {
+    'cvar_region_coef_table': (c_i, [c_p, c_p, c_p, C.POINTER(c_i), c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p]),
+    'cvar_cfg_sample_map': (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_p]),
+    'cvar_score_map': (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -192,7 +200,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
             pass
         lib = C.CDLL(path, mode=C.RTLD_GLOBAL)
         for name, (res, args) in (*SIGNATURES.items(), *SERVE_SIGNATURES.items(), *ACCUM_SIGNATURES.items(), *KVCACHE_SIGNATURES.items(),
-                                  *WIDE_SIGNATURES.items(), *POLICY_SIGNATURES.items(), *DISTILL_SIGNATURES.items()):
+                                  *WIDE_SIGNATURES.items(), *POLICY_SIGNATURES.items(), *DISTILL_SIGNATURES.items(), *REGION_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

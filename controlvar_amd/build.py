@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 OBJ = os.path.join(HERE, 'csrc', 'build')
 LIB = os.path.join(HERE, 'libcvar_hip.so')
-SOURCES = ['gemm.hip', 'gemm_conv.hip', 'gemm_f32.hip', 'gemm_skinny.hip', 'gemm_fp8.hip', 'conv_halo.hip', 'conv_c8.hip', 'gemm_tn.hip', 'ops.hip', 'attn.hip', 'sample.hip', 'edit.hip', 'msq.hip', 'train.hip', 'lora.hip', 'preproc.hip', 'probe.hip', 'kvcache.hip']
+SOURCES = ['gemm.hip', 'gemm_conv.hip', 'gemm_f32.hip', 'gemm_skinny.hip', 'gemm_fp8.hip', 'conv_halo.hip', 'conv_c8.hip', 'gemm_tn.hip', 'ops.hip', 'attn.hip', 'sample.hip', 'edit.hip', 'region.hip', 'msq.hip', 'train.hip', 'lora.hip', 'preproc.hip', 'probe.hip', 'kvcache.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off', '-Wno-unused-result']
 # per-source extras.  attn.hip: keep MFMA results in VGPRs - the softmax consumes every score with vector ALU ops, and the AGPR form
 # costs one v_accvgpr_read per score and tile (plus writes for the rescale)
@@ -54,7 +54,8 @@ def build_lib(force: bool = False, verbose: bool = True) -> str:
                                                          os.path.join(os.path.dirname(HERE), 'include', 'cvar_kvcache.h'),
                                                          os.path.join(os.path.dirname(HERE), 'include', 'cvar_wide.h'),
                                                          os.path.join(os.path.dirname(HERE), 'include', 'cvar_policy.h'),
-                                                         os.path.join(os.path.dirname(HERE), 'include', 'cvar_distill.h')]
+                                                         os.path.join(os.path.dirname(HERE), 'include', 'cvar_distill.h'),
+                                                         os.path.join(os.path.dirname(HERE), 'include', 'cvar_region.h')]
     stamp = os.path.join(OBJ, 'digest.txt')
     dig = _digest(deps)
     if not force and os.path.exists(LIB) and os.path.exists(stamp) and open(stamp).read() == dig:

@@ -7,9 +7,10 @@
 //            Exp(1) noise q, torch.multinomial's draw for one sample per row: argmax(p / q) over the softmax p of the masked logits.
 //   One text serves the scalar launch (cvar_cfg_sample: parameters in the kernel arguments) and the per-request launch (cvar_cfg_sample_rows: one
 //   parameter set per batch row in device tables): greedy_token and sample_token are templates on the parameter struct and reach whatever differs
-//   per row through the accessors below, nothing else.
+//   per row through the accessors below, nothing else.  A third form (cvar_cfg_sample_map, include/cvar_region.h) reads the combine weights per TOKEN.
 #include "cvar_common.h"
 #include "../../include/cvar_serve.h"
+#include "../../include/cvar_region.h"
 
 struct SampleParams {
     const float* logits;
@@ -53,12 +54,19 @@ struct RowSampleParams {
     int* kept;
 };
 
-// ---- what differs between the two forms: where a row's parameters come from, and which row keys the generator --------------------------------
+// Per-token form (include/cvar_region.h, regional guidance): the per-request form with the combine weights read per token (b, t) from this stage's
+// slice of a [B][L][4] table, row stride ldc tokens.  Still a block-uniform load: one workgroup per token.  Everything else is the base's.
+struct MapSampleParams : RowSampleParams {
+    long ldc;
+};
+
+// ---- what differs between the forms: where a row's parameters come from, and which row keys the generator --------------------------------
 // The per-request draw is keyed by (seed_b, stage, d, t) - the key the scalar form builds at B = 1, where d * 1 + 0 = d.  With everything else in
 // one text, row b of a per-request launch is bit for bit the scalar launch at B = 1 on that row's logits, whatever rides beside it.
 // seed_of is evaluated where a draw uses it, never handed down as a value: a by-value seed costs the SOFT instances 28 VGPRs and a wave per SIMD.
-__device__ __forceinline__ const float* coef_of(const SampleParams& p, long) { return p.coef; }
-__device__ __forceinline__ const float* coef_of(const RowSampleParams& p, long b) { return p.coef + b * 4; }
+__device__ __forceinline__ const float* coef_of(const SampleParams& p, long, long) { return p.coef; }
+__device__ __forceinline__ const float* coef_of(const RowSampleParams& p, long b, long) { return p.coef + b * 4; }
+__device__ __forceinline__ const float* coef_of(const MapSampleParams& p, long b, long t) { return p.coef + (b * p.ldc + t) * 4; }
 __device__ __forceinline__ int top_k_of(const SampleParams& p, long) { return p.top_k; }
 __device__ __forceinline__ int top_k_of(const RowSampleParams& p, long b) { return p.top_k[b]; }
 __device__ __forceinline__ float top_p_of(const SampleParams& p, long) { return p.top_p; }
@@ -79,7 +87,7 @@ template <class P>
 __device__ __forceinline__ float combine_logits(const P& p, long b, long t, int e) {
     const long rowstride = (long)p.l * p.ldv;
     const float* base = p.logits + (b * p.l + t) * p.ldv + e;
-    const float* cf = coef_of(p, b);
+    const float* cf = coef_of(p, b, t);
     float v = __fmul_rn(cf[0], base[0]);
     for (int r = 1; r < p.nrep; ++r) v = __fadd_rn(v, __fmul_rn(cf[r], base[(long)r * p.B * rowstride]));
     return v;
@@ -468,6 +476,24 @@ __global__ __launch_bounds__(256) void cfg_sample_edit_kernel(const RowSamplePar
     sample_token<false, false>(p);
 }
 
+// Regional guidance (include/cvar_region.h): the per-token form, with cfg_sample_edit_kernel's forcing when a table is given (forced == NULL: nothing
+// is forced).  A kernel of its own, so that the two above keep their argument blocks and instruction streams.
+__global__ __launch_bounds__(256) void cfg_sample_map_kernel(const MapSampleParams p, const int* __restrict__ forced, const int ldf) {
+    const long bt = blockIdx.x;
+    const long b = bt / p.l, t = bt % p.l;
+    const int id = forced ? forced[b * ldf + t] : -1;
+    if (id >= 0) {
+        if (threadIdx.x == 0) {
+            for (int d = 0; d < p.n_draw; ++d) p.idx_out[((long)d * p.B + b) * p.l + t] = id;
+            if (p.margin) p.margin[bt] = INFINITY;
+            if (p.kept) p.kept[bt] = 0;
+        }
+        return;
+    }
+    if (p.top_k[b] == 1) { greedy_token(p); return; }
+    sample_token<false, false>(p);
+}
+
 // ---- token log-probabilities (cvar_score_rows, include/cvar_serve.h) ------------------------------------------------------------------------
 // Scores a GIVEN id per token under the unfiltered CFG-combined distribution: log-probability, entropy, rank and the greedy id.  The combine is
 // combine_logits above (the sampler's text: `combined` and the argmax are the sampler's bits), the parameters of a row come from the same coef
@@ -485,11 +511,16 @@ struct ScoreParams {
     int* rank;
     int* argmax;
 };
-__device__ __forceinline__ const float* coef_of(const ScoreParams& p, long b) { return p.coef + b * 4; }
+struct MapScoreParams : ScoreParams {       // cvar_score_map (include/cvar_region.h): the weights per token, as MapSampleParams reads them
+    long ldc;
+};
+__device__ __forceinline__ const float* coef_of(const ScoreParams& p, long b, long) { return p.coef + b * 4; }
+__device__ __forceinline__ const float* coef_of(const MapScoreParams& p, long b, long t) { return p.coef + (b * p.ldc + t) * 4; }
 
-__global__ __launch_bounds__(256) void cfg_score_rows_kernel(const ScoreParams p) {
+template <class P>
+__device__ __forceinline__ void score_token(const P& p) {
     constexpr int EPT = 16;
-    __shared__ float sb1[4], sb2[4], ssum[4], sent[4];
+    __shared__ float sb1[4], ssum[4], sent[4];           // the second maximum feeds nothing here: it is not kept
     __shared__ int si1[4], scnt[4];
     const int tid = threadIdx.x;
     const long bt = blockIdx.x;
@@ -516,10 +547,10 @@ __global__ __launch_bounds__(256) void cfg_score_rows_kernel(const ScoreParams p
         other.b1 = __shfl_xor(best.b1, o, 64); other.i1 = __shfl_xor(best.i1, o, 64); other.b2 = __shfl_xor(best.b2, o, 64);
         best = merge_top2(best, other);
     }
-    if ((tid & 63) == 0) { sb1[tid >> 6] = best.b1; si1[tid >> 6] = best.i1; sb2[tid >> 6] = best.b2; }
+    if ((tid & 63) == 0) { sb1[tid >> 6] = best.b1; si1[tid >> 6] = best.i1; }
     __syncthreads();
-    Top2 r = {sb1[0], si1[0], sb2[0]};
-    for (int w = 1; w < 4; ++w) { Top2 o = {sb1[w], si1[w], sb2[w]}; r = merge_top2(r, o); }
+    Top2 r = {sb1[0], si1[0], -INFINITY};
+    for (int w = 1; w < 4; ++w) { Top2 o = {sb1[w], si1[w], -INFINITY}; r = merge_top2(r, o); }
     const float m = r.b1;
     // the target's value: every thread evaluates the combine at the target column (a block-uniform load) - the owning lane's bits
     const float xt = tgt >= 0 ? combine_logits(p, b, t, tgt) : 0.f;
@@ -555,6 +586,9 @@ __global__ __launch_bounds__(256) void cfg_score_rows_kernel(const ScoreParams p
         if (p.argmax) p.argmax[o] = r.i1;
     }
 }
+
+__global__ __launch_bounds__(256) void cfg_score_rows_kernel(const ScoreParams p) { score_token(p); }
+__global__ __launch_bounds__(256) void cfg_score_map_kernel(const MapScoreParams p) { score_token(p); }
 
 extern "C" int cvar_cfg_sample(const float* logits, int B, int nrep, int l, int V, const float* coef_host,
                                int top_k, float top_p, uint64_t seed, const uint64_t* seed_dev, int stage, int n_draw,
@@ -634,6 +668,43 @@ extern "C" int cvar_cfg_sample_edit(const float* logits, int B, int nrep, int l,
     p.stage = stage; p.n_draw = n_draw;
     p.idx_out = idx_out; p.combined = combined; p.margin = margin; p.kept = kept;
     hipLaunchKernelGGL(cfg_sample_edit_kernel, dim3((unsigned)((long)B * l)), dim3(256), 0, as_stream(stream), p, (const int*)forced, ldf);
+    CVAR_CHECK_LAUNCH();
+    return CVAR_OK;
+}
+
+// ---- regional guidance (include/cvar_region.h): the sampler and the score launch with per-token combine weights ---------------------------------
+extern "C" int cvar_cfg_sample_map(const float* logits, int B, int nrep, int l, int V, const float* coef, int ldc, const int32_t* top_k,
+                                   const float* top_p, const int64_t* seed, int stage, int n_draw, int32_t* idx_out, float* combined,
+                                   float* margin, int32_t* kept, int ldv, const float* expo, float* soft_out, const int32_t* forced, int ldf,
+                                   void* stream) {
+    if (!logits || !coef || !top_k || !top_p || !seed || !idx_out || B <= 0 || l <= 0 || V <= 1) return CVAR_EINVAL;
+    if (ldc < l || (forced && ldf < l)) return CVAR_EINVAL;
+    if (nrep < 1 || nrep > 4 || n_draw < 1 || n_draw > 4 || V > 4096) return CVAR_EUNSUPPORTED;
+    if (ldv != 0 && ldv < V) return CVAR_EINVAL;
+    if (expo || soft_out) return CVAR_EUNSUPPORTED;                // as the per-row form: no caller-drawn noise, no more_smooth
+    MapSampleParams p;
+    p.logits = logits; p.B = B; p.nrep = nrep; p.l = l; p.V = V; p.ldv = ldv ? ldv : V;
+    p.coef = coef; p.top_k = (const int*)top_k; p.top_p = top_p; p.seed = (const unsigned long long*)seed;
+    p.stage = stage; p.n_draw = n_draw;
+    p.idx_out = idx_out; p.combined = combined; p.margin = margin; p.kept = kept;
+    p.ldc = ldc;
+    hipLaunchKernelGGL(cfg_sample_map_kernel, dim3((unsigned)((long)B * l)), dim3(256), 0, as_stream(stream), p, (const int*)forced, ldf);
+    CVAR_CHECK_LAUNCH();
+    return CVAR_OK;
+}
+
+extern "C" int cvar_score_map(const float* logits, int B, int nrep, int l, int V, const float* coef, int ldc, const int32_t* target, int ldt,
+                              float* combined, float* logprob, float* entropy, int32_t* rank, int32_t* argmax, int ldo, int ldv, void* stream) {
+    if (!logits || !coef || !target || B <= 0 || l <= 0 || V < 1 || ldt < l || ldc < l || (ldo != 0 && ldo < l)) return CVAR_EINVAL;
+    if (!combined && !logprob && !entropy && !rank && !argmax) return CVAR_EINVAL;
+    if (nrep < 1 || nrep > 4 || V > 4096) return CVAR_EUNSUPPORTED;
+    if (ldv != 0 && ldv < V) return CVAR_EINVAL;
+    MapScoreParams p;
+    p.logits = logits; p.B = B; p.nrep = nrep; p.l = l; p.V = V; p.ldv = ldv ? ldv : V;
+    p.coef = coef; p.target = (const int*)target; p.ldt = ldt; p.ldo = ldo ? ldo : l;
+    p.combined = combined; p.logprob = logprob; p.entropy = entropy; p.rank = (int*)rank; p.argmax = (int*)argmax;
+    p.ldc = ldc;
+    hipLaunchKernelGGL(cfg_score_map_kernel, dim3((unsigned)((long)B * l)), dim3(256), 0, as_stream(stream), p);
     CVAR_CHECK_LAUNCH();
     return CVAR_OK;
 }

@@ -949,6 +949,89 @@ def _edit_half(half: str, src, keep, B: int, pns, vocab: int, pixels: bool = Fal
     return _flat_ids(f'src_{half}', src, B, pns, vocab), mask
 
 
+# ---- regional guidance (an addition of this library; include/cvar_region.h) ------------------------------------------------
+REGION_MAX_LABELS = 3          # K conditional rows + the unconditional one fill the sampler's four weight slots
+
+
+def region_coef_reference(regions, strength, cfg, patch_nums, mask_factor: int) -> np.ndarray:
+    """The weight rule of regional guidance on the host, in float64: regions (B, K, S, S) fp32, strength (B, S, S) fp32 or None, cfg (B, K) ->
+    (B, L, 4) fp32, L = sum mask_factor pn^2 in the token order of generation (both halves of a scale read the same maps, so the order of the
+    halves changes no value).  Per latent cell c: n_k(c) = w_k(c) / sum_k w_k(c); per token, over its area-pooling bin (edit_keep_cells' bins):
+    wbar_k = mean n_k, gbar = mean strength; t_k = (cfg_k gbar) si / (n - 1); weights wbar_k (1 + t_k) for the K labels, -(sum_k wbar_k t_k)
+    for the unconditional row, 0 above - each rounded to fp32 once.  With K = 1 and no strength this is _request_table's [1 + t, -t] bit for
+    bit.  cvar_region_coef_table is the device form of this function (it sums the means in another order: within 1 fp32 ulp)."""
+    w = np.asarray(regions, dtype=np.float32).astype(np.float64)
+    g = None if strength is None else np.asarray(strength, dtype=np.float32).astype(np.float64)
+    cf = np.asarray(cfg, dtype=np.float64)
+    B, K, S = w.shape[0], w.shape[1], w.shape[-1]
+    pns = [int(p) for p in patch_nums]
+    nrm = w / w.sum(axis=1, keepdims=True)
+    out = np.zeros((B, mask_factor * sum(p * p for p in pns), 4), dtype=np.float32)
+    o = 0
+    for si, pn in enumerate(pns):
+        ratio = si / (len(pns) - 1)
+        for i in range(pn):
+            r0, r1 = i * S // pn, -((-(i + 1) * S) // pn)
+            for j in range(pn):
+                c0, c1 = j * S // pn, -((-(j + 1) * S) // pn)
+                n = (r1 - r0) * (c1 - c0)
+                for b in range(B):
+                    gbar = 1.0 if g is None else float(g[b, r0:r1, c0:c1].sum()) / n
+                    neg, row = 0.0, [0.0] * 4
+                    for k in range(K):
+                        wbar = float(nrm[b, k, r0:r1, c0:c1].sum()) / n
+                        t = (float(cf[b, k]) * gbar) * ratio
+                        row[k] = wbar * (1 + t)
+                        neg += wbar * t
+                    row[K] = -neg
+                    for h in range(mask_factor):
+                        out[b, o + h * pn * pn + i * pn + j] = row
+        o += mask_factor * pn * pn
+    return out
+
+
+def _region_request(B: int, labels, regions, cfg, strength, S: int, num_classes: int):
+    """one regional request, checked on the host before anything is written -> (labels (B, K) int64, regions (B, K, S, S) fp32, strength
+    (B, S, S) fp32 or None, cfg (B, K) float64), host tensors / arrays"""
+    lab = torch.as_tensor(_host_array(labels))
+    if lab.dim() != 2 or lab.shape[0] != B or lab.is_floating_point() or lab.dtype == torch.bool:
+        raise ValueError(f'labels: integer class labels of shape ({B}, K) expected (K labels per sample), got '
+                         f'{str(lab.dtype)[6:]} {tuple(lab.shape)}')
+    K = int(lab.shape[1])
+    if not 1 <= K <= REGION_MAX_LABELS:
+        raise ValueError(f'labels: K = {K} labels per sample - 1 to {REGION_MAX_LABELS} are offered (K conditional rows and the unconditional one '
+                         "fill the sampler's four weight slots)")
+    _check_index_range(lab, 0, num_classes, 'labels')
+    if not torch.is_tensor(regions) or tuple(regions.shape) != (B, K, S, S) or not regions.is_floating_point():
+        raise ValueError(f'regions: a floating-point tensor of shape ({B}, {K}, {S}, {S}) (one non-negative weight map per label at latent resolution) '
+                         f'expected, got {(str(regions.dtype)[6:] + " " + str(tuple(regions.shape))) if torch.is_tensor(regions) else type(regions).__name__}')
+    reg = regions.detach().to(device='cpu', dtype=torch.float32).contiguous()
+    if not torch.isfinite(reg).all() or (reg < 0).any():
+        raise ValueError('regions: finite, non-negative weights expected')
+    if (reg.double().sum(dim=1) <= 0).any():
+        raise ValueError('regions: a latent cell whose weights sum to 0 belongs to no label - give every cell a positive weight for at least one label')
+    st = None
+    if strength is not None:
+        if not torch.is_tensor(strength) or tuple(strength.shape) != (B, S, S) or not strength.is_floating_point():
+            raise ValueError(f'strength: None or a floating-point tensor of shape ({B}, {S}, {S}) expected, got '
+                             f'{(str(strength.dtype)[6:] + " " + str(tuple(strength.shape))) if torch.is_tensor(strength) else type(strength).__name__}')
+        st = strength.detach().to(device='cpu', dtype=torch.float32).contiguous()
+        if not torch.isfinite(st).all() or (st < 0).any():
+            raise ValueError('strength: finite, non-negative factors expected')
+    c = _host_array(cfg)
+    if c.dtype == object or c.dtype.kind not in 'iuf':
+        raise ValueError(f'cfg: numbers expected, got {c.dtype}')
+    c = c.astype(np.float64)
+    if c.ndim == 1 and c.shape == (B,):
+        c = c[:, None]
+    if c.ndim != 0 and c.shape not in ((B, 1), (B, K)):
+        raise ValueError(f'cfg: a scalar, shape ({B},) (one per batch row) or ({B}, {K}) (one per row and label) expected, got {c.shape}')
+    c = np.array(np.broadcast_to(c, (B, K)))                          # a copy: contiguous and writable
+    if not np.isfinite(c).all():
+        raise ValueError('cfg: finite guidance scales expected')
+    return lab.to(torch.int64), reg, st, c
+
+
 class _ScalarDraw(NamedTuple):
     """how the scale loops draw a scale on the scalar path: one cfg (a triple on the four-branch path), top_k, top_p and seed for the batch.
     seed_dev: the seed as a device scalar (graphs).  draws (sampler='torch'): the noise of each sampling call comes from the caller's
@@ -973,12 +1056,16 @@ class _RowDraw(NamedTuple):
     (ops.score_rows) behind the sampling launch and the overwrites by force_idx / c_mask / c_img / the edit table: it scores the ids of rows
     0 .. B-1 - the sample f_hat[:B] returns - under this scale's combine weights rows[3][si] and writes this scale's columns
     sample=False (score_infer_cfg; with score and force_idx, (n_draw B, l) int32 device ids per scale): no sampling launch at all - the score
-    launch is the only consumer of the logits, and the last scale's ids feed nothing"""
+    launch is the only consumer of the logits, and the last scale's ids feed nothing
+    coef_map (regional guidance): device (B, L, 4) fp32, the combine weights of every token (ops.region_coef_table); the sampling and the score
+    launch of every scale then read their columns of it instead of rows[3][si] (ops.cfg_sample_map / ops.score_map), the sample's nrep = K + 1
+    rows are [label_0 ; ... ; label_{K-1} ; unconditional], and ONE id row is drawn and fed to all of them"""
     rows: Any
     forced: Optional[torch.Tensor] = None
     ad: Any = None
     score: Any = None
     sample: bool = True
+    coef_map: Optional[torch.Tensor] = None
 
 
 GEMM_PRECISIONS = (None, 'bf16x3', 'fp8')
@@ -1721,19 +1808,23 @@ class ControlVAR(nn.Module):
         return cond_type.to(device=dev, dtype=torch.int32)
 
     @torch.no_grad()
-    def _prepare_rows(self, B, label_B, cond_type, four_way, seed, nrep: Optional[int] = None):
+    def _prepare_rows(self, B, label_B, cond_type, four_way, seed, nrep: Optional[int] = None, K: int = 0):
         """labels / condition types of all CFG rows: [cond ; uncond] or the 4-branch layout (control_var.py:252-263,381-400); nrep == 1
-        (cfg=None): the conditional rows alone"""
+        (cfg=None): the conditional rows alone.  K > 0 (regional guidance): label_B is (B, K) and the rows are [label_0 ; ... ; label_{K-1} ;
+        uncond], each block B rows, the sample's condition type on the K conditional blocks and 4 on the last"""
         cfg = self.cfg
         labels = self._as_labels(B, label_B, seed)
-        empty = torch.full_like(labels, self.num_classes)
-        nrep = self._guidance_rows(four_way) if nrep is None else nrep
-        labels_all = torch.cat([labels] + [empty] * (nrep - 1)).contiguous()
+        if K:
+            labels = labels.t().reshape(-1)                              # (B, K) -> [label_0 rows ; ... ; label_{K-1} rows]
+        empty = torch.full((B,), self.num_classes, device=labels.device, dtype=labels.dtype)
+        nrep = (K + 1 if K else self._guidance_rows(four_way)) if nrep is None else nrep
+        labels_all = torch.cat([labels] + [empty] * (1 if K else nrep - 1)).contiguous()
         types_all = None
         if cfg.mask_factor == 2:
             types = self._as_types(B, cond_type, seed)
             e4 = torch.full_like(types, 4)
-            types_all = (types if nrep == 1 else torch.cat([types, types, e4, e4]) if four_way else torch.cat([types, e4])).contiguous()
+            types_all = (torch.cat([types] * K + [e4]) if K else types if nrep == 1 else torch.cat([types, types, e4, e4]) if four_way
+                         else torch.cat([types, e4])).contiguous()
         return labels_all, types_all
 
     @staticmethod
@@ -1869,7 +1960,7 @@ class ControlVAR(nn.Module):
                                        logprobs=logprobs, sampled=self._sampled_pattern(four_way, c_mask, c_img, force_idx), nrep=nrep, targets=targets)
         return (f_hat, scores) if logprobs else f_hat
 
-    def _row_state(self, B: int, table: _RequestTable, logprobs: bool, forced=None, sample: bool = True):
+    def _row_state(self, B: int, table: _RequestTable, logprobs: bool, forced=None, sample: bool = True, coef_map=None):
         """the device state of one batch of requests -> (the table's device buffer, the _RowDraw over it).  The request table and the
         adapter slots are one upload; a graph builds this once and refreshes the buffer."""
         tab_dev = table.host.to(self.device)
@@ -1877,20 +1968,23 @@ class ControlVAR(nn.Module):
         if table.n_seq:
             from . import lora
             ad = (lora.bank_pack(self), table.slot_view(tab_dev))
-        return tab_dev, _RowDraw(table.views(tab_dev), forced, ad, _score_buffers(B, self.cfg.pyramid.L, self.device) if logprobs else None, sample)
+        return tab_dev, _RowDraw(table.views(tab_dev), forced, ad, _score_buffers(B, self.cfg.pyramid.L, self.device) if logprobs else None, sample, coef_map)
 
     @torch.no_grad()
     def _run_rows(self, B, label_B, cond_type, four_way, table: _RequestTable, *, c_mask=None, c_img=None, force_idx=None, trace: bool = False,
-                  logprobs: bool = False, sampled=None, mask_first: Optional[bool] = None, edit=None, score_halves=None, nrep: Optional[int] = None, targets: Optional[dict] = None):
+                  logprobs: bool = False, sampled=None, mask_first: Optional[bool] = None, edit=None, score_halves=None, nrep: Optional[int] = None, targets: Optional[dict] = None,
+                  region=None):
         """the per-request runner behind _generate_rows, edit_infer_cfg and score_infer_cfg: the validated table and the entry point's own extras
         -> (f_hat, TokenScores or None).  mask_first=None draws the (control, image) order (one per call, as the scalar path).
         edit: the host halves (src_ctrl, keep_ctrl, src_img, keep_img) of _edit_half - the forced-token table is built for the drawn order.
-        score_halves: the flat ids of the halves in token order, checked by _flat_ids - teacher-forced along, scored, nothing sampled."""
+        score_halves: the flat ids of the halves in token order, checked by _flat_ids - teacher-forced along, scored, nothing sampled.
+        region: the host (regions, strength, cfg) of _region_request - label_B is then (B, K), nrep = K + 1, and the weight table is built here."""
         self._pack(check=True); self.vae_proxy[0]._pack(check=True)
         for name, ids in (('c_mask', c_mask), ('c_img', c_img), ('_force_idx', force_idx)):
             if ids is not None:
                 _check_index_range(torch.cat([t.reshape(-1) for t in ids]), 0, self.cfg.vocab - 1, name)
-        labels_all, types_all = self._prepare_rows(B, label_B, cond_type, four_way, 0, nrep)
+        K = 0 if region is None else int(region[0].shape[1])
+        labels_all, types_all = self._prepare_rows(B, label_B, cond_type, four_way, 0, nrep, K=K)
         if mask_first is None:
             mask_first = self._draw_order(four_way)
         if self.cfg.separator and four_way:
@@ -1907,10 +2001,15 @@ class ControlVAR(nn.Module):
                 ids = torch.cat([h[:, o:o + pn * pn] for h in halves], dim=1)
                 force_idx.append((ids.repeat(4, 1) if four_way else ids).contiguous())
                 o += pn * pn
-        _, how = self._row_state(B, table, logprobs or score_halves is not None, forced, sample=score_halves is None)
+        coef_map = None
+        if region is not None:
+            coef_map = self._region_table(B, K, *[None if t is None else torch.as_tensor(t).to(dev) for t in region], mask_first)
+        _, how = self._row_state(B, table, logprobs or score_halves is not None, forced, sample=score_halves is None, coef_map=coef_map)
         f_hat = self._generate_core(B, labels_all, types_all, four_way, how, c_mask, c_img, force_idx, trace, mask_first, nrep=nrep, targets=targets)
         if trace and forced is not None:
             self.last_trace['forced'] = forced
+        if trace and coef_map is not None:
+            self.last_trace['coef'] = coef_map
         return f_hat, (self._token_scores(how.score, mask_first, sampled, forced) if how.score is not None else None)
 
     def _check_logprobs(self):
@@ -1967,7 +2066,8 @@ class ControlVAR(nn.Module):
         _RowDraw) -> (idx (n_draw B, l) int32, the soft embeddings of more_smooth or None).  cols: this scale's columns of the (B, L) tables.
         tr: the trace to append to.  force_idx (tests, score_infer_cfg) replaces the drawn ids."""
         cfg, dev = self.cfg, logits.device
-        n_draw = 4 if nrep == 4 else 1
+        mapped = isinstance(how, _RowDraw) and how.coef_map is not None  # regional guidance: nrep = K + 1 rows share ONE drawn id row
+        n_draw = 4 if nrep == 4 and not mapped else 1
         idx = torch.empty(n_draw * B, l, device=dev, dtype=torch.int32)
         comb = torch.empty(B, l, cfg.vocab, device=dev, dtype=torch.float32) if tr is not None else None
         mg = torch.empty(B, l, device=dev, dtype=torch.float32) if tr is not None else None
@@ -1976,6 +2076,11 @@ class ControlVAR(nn.Module):
             seed, top_k, top_p, coef = how.rows                          # _request_table built the weights with the expressions below
             if not how.sample:
                 pass                                                     # nothing is drawn: the ids are force_idx's, taken below
+            elif mapped:
+                ops.cfg_sample_map(logits, B, nrep, l, cfg.vocab, how.coef_map[:, cols], top_k, top_p, seed, si, n_draw, idx,
+                                   None if how.forced is None else how.forced[:, cols], comb, mg, ldv=ldv)
+                if tr is not None:                                       # the head's rows beside their combination (the tests of locality read both)
+                    tr.setdefault('rows', []).append(logits.view(nrep * B, l, ldv)[:, :, :cfg.vocab].clone())
             elif how.forced is not None:
                 ops.cfg_sample_edit(logits, B, nrep, l, cfg.vocab, coef[si], top_k, top_p, seed, si, n_draw, idx, how.forced[:, cols], comb, mg, ldv=ldv)
             else:
@@ -2056,7 +2161,10 @@ class ControlVAR(nn.Module):
                     idx[:nf * B, pn * pn:] = c_img[si].to(device=dev, dtype=torch.int32).repeat(nf, 1)
             if targets is not None:
                 targets['ids'].append(idx[:B].clone())
-            if score is not None:
+            if score is not None and how.coef_map is not None:
+                ops.score_map(logits, B, nrep, l, cfg.vocab, how.coef_map[:, cols], idx[:B], None, score[0][:, cols], score[1][:, cols], score[2][:, cols],
+                              score[3][:, cols], ldv=cfg.head_ld)
+            elif score is not None:
                 ops.score_rows(logits, B, nrep, l, cfg.vocab, how.rows[3][si], idx[:B], None, score[0][:, cols], score[1][:, cols], score[2][:, cols],
                                score[3][:, cols], ldv=cfg.head_ld)
                 if not how.sample and si == nstage - 1:
@@ -2169,7 +2277,8 @@ class ControlVAR(nn.Module):
 
     @torch.no_grad()
     def _graph_runner(self, B, four_way, labels_all, types_all, cfg, top_k, top_p, finish, *, per_request: bool, adapters: bool = False,
-                      logprobs: bool = False, forced=None, teach=None, refresh=None, prologue=None, sampled=None, check_rows: bool = True):
+                      logprobs: bool = False, forced=None, teach=None, refresh=None, prologue=None, sampled=None, check_rows: bool = True,
+                      K: int = 0, coef_map=None):
         """The graphed generators: capture prologue() (inside the graph, before the scale loop), the scale loop and finish() over the static
         label / type rows, and return replay(label_B, cond_type, given, g_seed, request) -> images, with .graph and .owned.
         The sampling state lives in a device seed scalar (scalar graphs: cfg, top_k, top_p are baked in and replay refuses every request
@@ -2180,14 +2289,16 @@ class ControlVAR(nn.Module):
         and request['adapter'] chooses (None: every row on the base model)
         logprobs=True: the score launch of every scale is captured too, the (B, L) score buffers are static outputs of the graph, and replay
         returns (images, TokenScores) - copies, as the images are.  sampled: the (L,) host pattern of the sampled tokens (None: all); an edit
-        graph (forced, the forced-token table) reads it off that table instead"""
+        graph (forced, the forced-token table) reads it off that table instead
+        K > 0 with coef_map (regional guidance): label_B is (B, K), the rows are _prepare_rows' K-label layout and the scale loop reads its combine
+        weights from the static (B, L, 4) table that prologue() fills inside the graph"""
         dev, vocab, nstage = self.device, self.cfg.vocab, len(self.cfg.pyramid.patch_nums)
         unguided = cfg is None                               # captured without guidance rows: labels_all / types_all hold B rows, and so does every replay
-        nrep = self._guidance_rows(four_way, unguided)
+        nrep = K + 1 if K else self._guidance_rows(four_way, unguided)
         if per_request:
             slots0 = self._adapter_slots(-1, B, nrep) if adapters else None
             table0 = _request_table(B, cfg, top_k, top_p, 0, four_way, vocab, nstage, slots=slots0)     # also validates the defaults
-            state, how = self._row_state(B, table0, logprobs, forced)
+            state, how = self._row_state(B, table0, logprobs, forced, coef_map=coef_map)
         else:
             state = torch.zeros(1, device=dev, dtype=torch.int64)
             how = _ScalarDraw(cfg, top_k, top_p, 0, seed_dev=state)
@@ -2200,9 +2311,9 @@ class ControlVAR(nn.Module):
         graph, out, owned = self._capture(body)
 
         def check_shapes(label_B, cond_type):
-            for name, v in (('label_B', label_B), ('cond_type', cond_type)):
-                if torch.is_tensor(v) and tuple(v.shape) != (B,):
-                    raise ValueError(f'{name}: expected shape ({B},), got {tuple(v.shape)}')
+            for name, v, want in (('label_B', label_B, (B, K) if K else (B,)), ('cond_type', cond_type, (B,))):
+                if torch.is_tensor(v) and tuple(v.shape) != want:
+                    raise ValueError(f'{name}: expected shape {want}, got {tuple(v.shape)}')
 
         def replay(label_B, cond_type, given, g_seed, request):
             # everything that can refuse runs before the first static buffer is written
@@ -2218,7 +2329,7 @@ class ControlVAR(nn.Module):
                 slots = self._adapter_slots(-1 if adapter is None else adapter, B, nrep) if adapters else None
                 check_shapes(label_B, cond_type)
                 table = _request_table(B, request['cfg'], request['top_k'], request['top_p'], g_seed, four_way, vocab, nstage, slots=slots)
-                la, ta = self._prepare_rows(B, label_B, cond_type, four_way, 0, nrep)
+                la, ta = self._prepare_rows(B, label_B, cond_type, four_way, 0, nrep, K=K)
                 copy_given = refresh(given) if refresh is not None else None
             else:
                 _refuse_request_keywords(g_seed, request)
@@ -2489,10 +2600,16 @@ class ControlVAR(nn.Module):
         cfg / top_k / top_p given here are the defaults of run; each and g_seed is a scalar or per row.  Everything is validated on the host
         before the first static buffer is written: a refused run leaves the graph as it was.  Bidirectional models are refused as
         graphed_generator refuses them.  logprobs=True: run returns (images, TokenScores) as edit_infer_cfg(logprobs=True) does."""
+        return self._graphed_edit('graphed_edit_generator', B, source, cfg, top_k, top_p, decode, adapters, logprobs)
+
+    @torch.no_grad()
+    def _graphed_edit(self, what: str, B: int, source: str, cfg, top_k, top_p, decode: str, adapters: bool, logprobs: bool, K: int = 0):
+        """the capture behind graphed_edit_generator and, with K > 0 labels per sample, graphed_region_generator: the latter adds the static region
+        maps, strength, guidance scales and the (B, L, 4) weight table, whose launch joins the forced-token table's in the prologue"""
         if cfg is None:
-            raise NotImplementedError(_NO_UNGUIDED.format('graphed_edit_generator'))
+            raise NotImplementedError(_NO_UNGUIDED.format(what))
         if self.sampler == 'torch':
-            raise NotImplementedError("graphed_edit_generator captures the counter sampler only: sampler='torch' draws its noise with torch on model.rng "
+            raise NotImplementedError(f"{what} captures the counter sampler only: sampler='torch' draws its noise with torch on model.rng "
                                       "between the launches; set model.sampler = 'counter' to capture")
         if self.bidirectional:
             raise NotImplementedError('the captured generator fixes the (control, image) order; bidirectional models draw it per call')
@@ -2504,28 +2621,42 @@ class ControlVAR(nn.Module):
             raise ValueError(f'B={B!r}: a positive batch size')
         mf = self.cfg.mask_factor
         lab0 = torch.zeros(B, dtype=torch.int64)
-        self._check_edit(lab0, lab0)
+        if K:
+            self._check_region(lab0, lab0)
+        else:
+            self._check_edit(lab0, lab0)
         dev = self.device
         vae: VQVAE = self.vae_proxy[0]
         pns = self.cfg.pyramid.patch_nums
         S, Lsrc, pixels = pns[-1], sum(pn * pn for pn in pns), source == 'pixels'
-        labels_all, types_all = self._prepare_rows(B, lab0, lab0 if mf == 2 else None, False, 0)
+        labels_all, types_all = self._prepare_rows(B, torch.zeros(B, K, dtype=torch.int64) if K else lab0, lab0 if mf == 2 else None, False, 0, K=K)
         halves = ('ctrl', 'img') if mf == 2 else ('img',)
         keep_buf = {h: torch.zeros(B, S, S, device=dev, dtype=torch.uint8) for h in halves}
         ids_buf = {h: torch.zeros(B, Lsrc, device=dev, dtype=torch.int32) for h in halves}
         pix_buf = {h: torch.zeros(B, 3, 16 * S, 16 * S, device=dev, dtype=torch.float32) for h in halves} if pixels else None
         forced = torch.full((B, self.cfg.pyramid.L), -1, device=dev, dtype=torch.int32)
+        # regional guidance: uniform maps, strength 1 (a mean of ones is exactly 1: the bits of strength=None) and cfg 0 until the first replay
+        reg_buf = (torch.ones(B, K, S, S, device=dev), torch.ones(B, S, S, device=dev), torch.zeros(B, K, device=dev, dtype=torch.float64)) if K else None
+        coef_map = torch.zeros(B, self.cfg.pyramid.L, 4, device=dev) if K else None
 
         def prologue():
             if pixels:
                 for h in halves:                            # each half as its own batch of B: the calls of img_to_idxBl
                     ids_buf[h].copy_(vae._ms_encode(vae._encode_f(pix_buf[h]))[0])
             self._edit_table(B, ids_buf.get('ctrl'), keep_buf.get('ctrl'), ids_buf['img'], keep_buf['img'], True, forced)
+            if K:
+                self._region_table(B, K, *reg_buf, True, coef_map)
 
         def refresh(request):
             checked = {h: _edit_half(h, request.get('src_' + h), request.get('keep_' + h), B, pns, self.cfg.vocab, pixels) for h in halves}
+            region = _region_request(B, request['labels'], request['regions'], request['cfg'], request['strength'], S, self.num_classes)[1:] if K else ()
 
             def copy():
+                for buf, v in zip(reg_buf or (), region):
+                    if v is None:
+                        buf.fill_(1.0)
+                    else:
+                        buf.copy_(torch.as_tensor(v))
                 for h, (src, mask) in checked.items():
                     if src is not None:
                         (pix_buf if pixels else ids_buf)[h].copy_(src)
@@ -2535,10 +2666,23 @@ class ControlVAR(nn.Module):
                         keep_buf[h].copy_(mask)
             return copy
 
-        inner = self._graph_runner(B, False, labels_all, types_all, cfg, top_k, top_p, self._finisher(decode, mf - 1), per_request=True, adapters=adapters,
-                                   logprobs=logprobs, forced=forced, refresh=refresh, prologue=prologue)
+        inner = self._graph_runner(B, False, labels_all, types_all, 0.0 if K else cfg, top_k, top_p, self._finisher(decode, mf - 1), per_request=True,
+                                   adapters=adapters, logprobs=logprobs, forced=forced, refresh=refresh, prologue=prologue, K=K, coef_map=coef_map)
 
-        if mf == 2:
+        if K:
+            # the guidance scales travel with the maps (cfg_buf); the request table's own weights are not read, so its cfg is a constant 0
+            def run(labels, cond_type=None, *, regions, cfg=cfg, strength=None, src_img=None, keep_img=None, src_ctrl=None, keep_ctrl=None, g_seed=None,
+                    top_k=top_k, top_p=top_p, adapter=None):
+                if mf == 1 and (src_ctrl is not None or keep_ctrl is not None):
+                    raise ValueError('src_ctrl / keep_ctrl: a plain VAR has the image half only')
+                labels = torch.as_tensor(_host_array(labels))
+                if labels.dim() != 2:
+                    raise ValueError(f'labels: shape ({B}, {K}) expected, got {tuple(labels.shape)}')
+                return inner(labels, cond_type if mf == 2 else None,
+                             dict(src_img=src_img, keep_img=keep_img, src_ctrl=src_ctrl, keep_ctrl=keep_ctrl, labels=labels, regions=regions, cfg=cfg,
+                                  strength=strength), g_seed, dict(cfg=0.0, top_k=top_k, top_p=top_p, adapter=adapter))
+            run.coef = lambda: coef_map.clone()                              # the weight table of the last replay
+        elif mf == 2:
             def run(label_B, cond_type, *, src_img=None, keep_img=None, src_ctrl=None, keep_ctrl=None, g_seed=None, cfg=cfg, top_k=top_k, top_p=top_p,
                     adapter=None):
                 return inner(label_B, cond_type, dict(src_img=src_img, keep_img=keep_img, src_ctrl=src_ctrl, keep_ctrl=keep_ctrl), g_seed,
@@ -2550,6 +2694,77 @@ class ControlVAR(nn.Module):
         run.ids = lambda: tuple(ids_buf[h].clone() for h in halves)          # the sources of the last replay ('pixels': what the tokeniser produced)
         run.forced = lambda: forced.clone()                                  # ... and its forced-token table
         return run
+
+    # ---- regional guidance
+    def _check_region(self, label_B, cond_type, more_smooth=False, given=None, cfg=0.0):
+        """what region_infer_cfg / graphed_region_generator do not offer, said on the host before any device work"""
+        if cfg is None:
+            raise NotImplementedError(_NO_UNGUIDED.format('region_infer_cfg'))
+        if given is not None:
+            raise NotImplementedError('regional guidance: the four-branch conditional call (given=) is not offered - its four weight slots hold the '
+                                      'branches of conditional_infer_cfg, which leaves none for a second label; keep the given half with src_ctrl / keep_ctrl=True')
+        if more_smooth:
+            raise NotImplementedError('regional guidance: more_smooth is not offered (the soft-embedding kernel has no per-token form); pass more_smooth=False')
+        if self.cfg.separator:
+            raise NotImplementedError('regional guidance: separator models are not offered (their scales carry special tokens between the halves, '
+                                      'which the per-token weight table does not lay out)')
+        if self.cfg.separate_decoding:
+            raise NotImplementedError('regional guidance: separate_decoding models are not offered (the two-pass branch (control_var.py:428-485) has no '
+                                      'per-token sampler, and the K-label rows are not laid out for the training mask of indep)')
+        self._check_per_request(label_B, cond_type, False, more_smooth)
+
+    def _region_table(self, B, K, regions, strength, cfg, mask_first, coef=None):
+        """device maps (fp32), strength (fp32 or None) and guidance scales (float64 (B, K)) -> coef (B, L, 4) fp32, one launch"""
+        if coef is None:
+            coef = torch.empty(B, self.cfg.pyramid.L, 4, device=self.device, dtype=torch.float32)
+        return ops.region_coef_table(regions, strength, cfg, self.cfg.pyramid.patch_nums, B, K, mask_first, self.cfg.mask_factor, coef)
+
+    @torch.no_grad()
+    def region_infer_cfg(self, B: int, labels, cond_type, *, regions, cfg=1.5, strength=None, top_k=0, top_p=0.0, g_seed=None,
+                         src_img=None, keep_img=None, src_ctrl=None, keep_ctrl=None, adapter=None, logprobs: bool = False, trace: bool = False,
+                         more_smooth: bool = False, given: Optional[str] = None):
+        """Regional guidance (an addition of this library): several class labels per sample, each weighing the guidance where its
+        latent-resolution map says so - "class A on the left, class B on the right", "class X inside this box", "guide harder in this region".
+        Returns what autoregressive_infer_cfg returns.
+        labels: (B, K) class labels, 1 <= K <= 3.  The sample runs K conditional transformer rows and one unconditional row (nrep = K + 1), all fed
+        the one drawn id row; cond_type is the sample's on the conditional rows.
+        regions: (B, K, S, S) non-negative weights at latent resolution (S = patch_nums[-1]), normalised per latent cell over the labels; every cell
+        needs a positive weight somewhere.  cfg: a scalar, (B,) or (B, K) guidance scales.  strength: None or (B, S, S) >= 0, a factor on the
+        guidance scale per latent cell.  A token's four combine weights are region_coef_reference's: its bin's mean normalised weight w_k times
+        (1 + t_k) per label, -(sum_k w_k t_k) on the unconditional row, t_k = cfg_k strength ratio.  Both halves of a ControlVAR sample use the
+        same maps.  With K = 1, uniform maps and no strength the call is autoregressive_infer_cfg in per-request mode, bit for bit.
+        top_k / top_p / g_seed: a scalar or one value per row.  src_* / keep_*: edit_infer_cfg's - kept tokens carry the source ids, the others are
+        sampled under the regional weights.  adapter, logprobs, trace: as edit_infer_cfg's; trace also leaves last_trace['coef'], the (B, L, 4)
+        weight table, and last_trace['rows'], per scale the head's (nrep B, l, V) rows behind the combined logits.
+        more_smooth, given= (the four-branch call), cfg=None, sampler='torch', separator and separate_decoding models are refused; what the
+        maps do to image quality has not been judged (no published checkpoint is loaded here) - the contract is the weights above."""
+        self._check_region(labels, cond_type, more_smooth, given, cfg)
+        if logprobs:
+            self._check_logprobs()
+        pns, mf = self.cfg.pyramid.patch_nums, self.cfg.mask_factor
+        lab, reg, st, c = _region_request(B, labels, regions, cfg, strength, pns[-1], self.num_classes)
+        K = int(lab.shape[1])
+        edit = None
+        if any(v is not None for v in (src_img, keep_img, src_ctrl, keep_ctrl)):
+            s_ctrl, k_ctrl = _edit_half('ctrl', src_ctrl, keep_ctrl, B, pns, self.cfg.vocab) if mf == 2 else (None, None)
+            edit = (s_ctrl, k_ctrl, *_edit_half('img', src_img, keep_img, B, pns, self.cfg.vocab))
+        # the request table carries seeds, top_k, top_p and the adapter slots; its own combine weights are not read (cfg 0: a constant)
+        table = _request_table(B, 0.0, top_k, top_p, g_seed, False, self.cfg.vocab, len(pns), slots=self._adapter_slots(adapter, B, K + 1))
+        f_hat, scores = self._run_rows(B, lab, cond_type, False, table, trace=trace, logprobs=logprobs, edit=edit, nrep=K + 1, region=(reg, st, c))
+        return self._images(f_hat, scores)
+
+    @torch.no_grad()
+    def graphed_region_generator(self, B: int, K: int, source: str = 'ids', top_k=0, top_p=0.0, decode: str = 'both', adapters: bool = False,
+                                 logprobs: bool = False):
+        """Capture one full `region_infer_cfg` with K labels per sample in a HIP graph and return
+        ``run(labels, cond_type, *, regions, cfg=1.5, strength=None, src_img=None, keep_img=None, src_ctrl=None, keep_ctrl=None, g_seed=None, top_k=...,
+        top_p=..., adapter=None) -> images``.  Labels, maps, strength, guidance scales, keep masks, sources and the request table live in static
+        device buffers refreshed before each replay; the graph holds the launches of the weight table and of the forced-token table, so new maps
+        need no recapture.  source / decode / adapters / logprobs: graphed_edit_generator's.  Everything is validated on the host before the first
+        static buffer is written.  ``run.coef()`` returns the (B, L, 4) weight table of the last replay.  Bidirectional models are refused."""
+        if int(K) != K or not 1 <= K <= REGION_MAX_LABELS:
+            raise ValueError(f'K={K!r}: 1 to {REGION_MAX_LABELS} labels per sample')
+        return self._graphed_edit('graphed_region_generator', B, source, 1.5, top_k, top_p, decode, adapters, logprobs, K=int(K))
 
     def _images(self, f_hat: torch.Tensor, scores: Optional[TokenScores] = None):
         """what the public generation calls return: the decoded images, or (images, scores) under logprobs=True"""
@@ -2696,6 +2911,13 @@ class VAR(ControlVAR):
         """ControlVAR.edit_infer_cfg for the one half a plain VAR has: returns (B, 3, H, H) as autoregressive_infer_cfg"""
         return super().edit_infer_cfg(B, label_B, None, src_img=src_img, keep_img=keep_img, g_seed=g_seed, cfg=cfg, top_k=top_k, top_p=top_p, trace=trace,
                                       more_smooth=more_smooth, adapter=adapter, logprobs=logprobs)
+
+    @torch.no_grad()
+    def region_infer_cfg(self, B: int, labels, *, regions, cfg=1.5, strength=None, top_k=0, top_p=0.0, g_seed=None, src_img=None, keep_img=None,
+                         adapter=None, logprobs: bool = False, trace: bool = False, more_smooth: bool = False):
+        """ControlVAR.region_infer_cfg for the one half a plain VAR has: returns (B, 3, H, H) as autoregressive_infer_cfg"""
+        return super().region_infer_cfg(B, labels, None, regions=regions, cfg=cfg, strength=strength, top_k=top_k, top_p=top_p, g_seed=g_seed,
+                                        src_img=src_img, keep_img=keep_img, adapter=adapter, logprobs=logprobs, trace=trace, more_smooth=more_smooth)
 
     @torch.no_grad()
     def score_infer_cfg(self, B: int, label_B, *, ids_img, cfg=0.0, adapter=None) -> 'TokenScores':

@@ -498,6 +498,81 @@ def edit_force_table(keep_ctrl: Optional[torch.Tensor], keep_img: Optional[torch
     return forced
 
 
+def region_coef_table(regions: torch.Tensor, strength: Optional[torch.Tensor], cfg: torch.Tensor, patch_nums: Sequence[int], B: int, K: int,
+                      mask_first: bool, mask_factor: int, coef: torch.Tensor):
+    """The per-token combine weights of every scale in one launch (cvar_region_coef_table, include/cvar_region.h).  regions (B, K, S, S) float32,
+    strength (B, S, S) float32 or None, cfg (B, K) float64, coef (B, mask_factor * sum pn^2, 4) float32, all contiguous on one device;
+    S = patch_nums[-1].  The values in the maps are not checked here (they are on the device): the caller validates them on the host."""
+    pns = [int(p) for p in patch_nums]
+    S, L = pns[-1], mask_factor * sum(p * p for p in pns)
+    for name, t, dtype, shape in (('regions', regions, torch.float32, (B, K, S, S)), ('strength', strength, torch.float32, (B, S, S)),
+                                  ('cfg', cfg, torch.float64, (B, K)), ('coef', coef, torch.float32, (B, L, 4))):
+        if t is not None and (not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous()
+                              or (coef is not None and t.device != coef.device)):
+            raise ValueError(f'region_coef_table: {name} must be a contiguous {str(dtype)[6:]} {shape} tensor' + (f' on {coef.device}' if coef is not None else ''))
+    arr = (C.c_int * len(pns))(*pns)
+    check(_lib.load().cvar_region_coef_table(_ptr(regions), _ptr(strength), _ptr(cfg), arr, len(pns), B, K, S, int(bool(mask_first)), int(mask_factor),
+                                             _ptr(coef), _stream()), 'cvar_region_coef_table')
+    return coef
+
+
+def _coef_slice(what: str, coef, B: int, l: int, dev) -> int:
+    """this stage's slice (B, l, 4) of a (B, L, 4) weight table, a view of it will do -> its row stride in tokens (ldc)"""
+    if (not torch.is_tensor(coef) or coef.dtype != torch.float32 or tuple(coef.shape) != (B, l, 4) or coef.stride(2) != 1 or coef.stride(1) != 4
+            or coef.stride(0) % 4 != 0 or (B > 1 and coef.stride(0) < 4 * l) or coef.device != dev):
+        raise ValueError(f'{what}: coef must be a float32 ({B}, {l}, 4) tensor on {dev}, dense along its last two dimensions')
+    return coef.stride(0) // 4 if B > 1 else max(coef.stride(0) // 4, l)
+
+
+def cfg_sample_map(logits: torch.Tensor, B: int, nrep: int, l: int, V: int, coef: torch.Tensor, top_k: torch.Tensor, top_p: torch.Tensor,
+                   seed: torch.Tensor, stage: int, n_draw: int, idx_out: torch.Tensor, forced: Optional[torch.Tensor] = None,
+                   combined: Optional[torch.Tensor] = None, margin: Optional[torch.Tensor] = None, kept: Optional[torch.Tensor] = None, ldv: int = 0,
+                   expo: Optional[torch.Tensor] = None, soft_out: Optional[torch.Tensor] = None):
+    """cfg_sample_rows with the combine weights read per token (cvar_cfg_sample_map, include/cvar_region.h).  coef: (B, l, 4) float32 - this stage's
+    columns of the (B, L, 4) table, a view of it will do (its row stride is handed on as ldc).  forced: as cfg_sample_edit takes it, or None (nothing
+    is forced).  top_k / top_p / seed stay per batch row.  A token equals what cfg_sample_rows gives it with its four weights as the row's."""
+    for name, t, dtype, shape in (('top_k', top_k, torch.int32, (B,)), ('top_p', top_p, torch.float32, (B,)), ('seed', seed, torch.int64, (B,))):
+        if t is not None and (not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != logits.device):
+            raise ValueError(f'cfg_sample_map: {name} must be a contiguous {str(dtype)[6:]} {shape} tensor on {logits.device}')
+    ldc = _coef_slice('cfg_sample_map', coef, B, l, logits.device) if coef is not None else 0
+    ldf = 0
+    if forced is not None:
+        if (not torch.is_tensor(forced) or forced.dtype != torch.int32 or tuple(forced.shape) != (B, l) or forced.stride(1) != 1
+                or (B > 1 and forced.stride(0) < l) or forced.device != logits.device):
+            raise ValueError(f'cfg_sample_map: forced must be an int32 ({B}, {l}) tensor on {logits.device} with unit stride along the tokens')
+        ldf = forced.stride(0) if B > 1 else max(forced.stride(0), l)
+    check(_lib.load().cvar_cfg_sample_map(_ptr(logits), B, nrep, l, V, _ptr(coef), int(ldc), _ptr(top_k), _ptr(top_p), _ptr(seed), stage, n_draw,
+                                          _ptr(idx_out), _ptr(combined), _ptr(margin), _ptr(kept), int(ldv), _ptr(expo), _ptr(soft_out),
+                                          _ptr(forced), int(ldf), _stream()), 'cvar_cfg_sample_map')
+    return idx_out
+
+
+def score_map(logits: torch.Tensor, B: int, nrep: int, l: int, V: int, coef: torch.Tensor, target: torch.Tensor,
+              combined: Optional[torch.Tensor] = None, logprob: Optional[torch.Tensor] = None, entropy: Optional[torch.Tensor] = None,
+              rank: Optional[torch.Tensor] = None, argmax: Optional[torch.Tensor] = None, ldv: int = 0):
+    """score_rows with the combine weights read per token (cvar_score_map, include/cvar_region.h): coef as cfg_sample_map takes it, everything else
+    as score_rows."""
+    dev = logits.device
+    ldc = _coef_slice('score_map', coef, B, l, dev) if coef is not None else 0
+
+    def row_stride(name, t, dtype):
+        if (not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != (B, l) or t.stride(1) != 1 or (B > 1 and t.stride(0) < l) or t.device != dev):
+            raise ValueError(f'score_map: {name} must be {"an" if dtype == torch.int32 else "a"} {str(dtype)[6:]} ({B}, {l}) tensor on {dev} with unit stride '
+                             'along the tokens')
+        return t.stride(0) if B > 1 else max(t.stride(0), l)
+
+    ldt = row_stride('target', target, torch.int32) if target is not None else 0
+    if combined is not None and (not torch.is_tensor(combined) or combined.dtype != torch.float32 or tuple(combined.shape) != (B, l, V)
+                                 or not combined.is_contiguous() or combined.device != dev):
+        raise ValueError(f'score_map: combined must be a contiguous float32 ({B}, {l}, {V}) tensor on {dev}')
+    ldo = {row_stride(name, t, dtype) for name, t, dtype in (('logprob', logprob, torch.float32), ('entropy', entropy, torch.float32),
+                                                             ('rank', rank, torch.int32), ('argmax', argmax, torch.int32)) if t is not None}
+    if len(ldo) > 1:
+        raise ValueError(f'score_map: logprob / entropy / rank / argmax must share one row stride, got {sorted(ldo)}')
+    check(_lib.load().cvar_score_map(_ptr(logits), B, nrep, l, V, _ptr(coef), int(ldc), _ptr(target), int(ldt), _ptr(combined), _ptr(logprob),
+                                     _ptr(entropy), _ptr(rank), _ptr(argmax), int(ldo.pop()) if ldo else 0, int(ldv), _stream()), 'cvar_score_map')
+
+
 def ms_next_input(idx: torch.Tensor, codebook, phi_w, phi_b, up, down, f_hat, tok_out, nb, nmaps, pn, pn_next, S, Cvae,
                   phi_k: int, up_off: int, down_off: int):
     lib = _lib.load()
