@@ -8,7 +8,8 @@ and the pure-host modules (spec, synth) work everywhere.
 from . import spec  # noqa: F401
 from .spec import DEFAULT_PATCH_NUMS, PATCH_NUMS_512  # noqa: F401  (the 256 x 256 and the 512 x 512 scale lists)
 
-__all__ = ['VQVAE', 'VAR', 'ControlVAR', 'build_var', 'build_control_var', 'build_vae', 'spec', 'register_torch_ops', 'DEFAULT_PATCH_NUMS', 'PATCH_NUMS_512']
+__all__ = ['VQVAE', 'VAR', 'ControlVAR', 'build_var', 'build_control_var', 'build_vae', 'spec', 'register_torch_ops', 'DEFAULT_PATCH_NUMS', 'PATCH_NUMS_512',
+           'TokenScores', 'SparseDistillTargets', 'SparseDistillLoss']
 
 
 def register_torch_ops():
@@ -22,4 +23,10 @@ def __getattr__(name):
     if name in ('VQVAE', 'VAR', 'ControlVAR', 'build_var', 'build_control_var', 'build_vae'):
         from . import models as _m
         return getattr(_m, name)
+    if name in ('TokenScores', 'SparseDistillTargets'):          # top-N alternatives and sparse distillation targets
+        from . import models as _m
+        return getattr(_m, name)
+    if name == 'SparseDistillLoss':
+        from . import train as _t
+        return _t.SparseDistillLoss
     raise AttributeError(name)

@@ -1,4 +1,4 @@
-"""ctypes binding of libcvar_hip.so (include/cvar.h, include/cvar_serve.h, include/cvar_accum.h, include/cvar_kvcache.h, include/cvar_wide.h, include/cvar_policy.h, include/cvar_distill.h, include/cvar_region.h).  No torch types cross this boundary:
+"""ctypes binding of libcvar_hip.so (include/cvar.h, include/cvar_serve.h, include/cvar_accum.h, include/cvar_kvcache.h, include/cvar_wide.h, include/cvar_policy.h, include/cvar_distill.h, include/cvar_region.h, include/cvar_topn.h).  No torch types cross this boundary:
 callers hand over raw device pointers (``tensor.data_ptr()``), sizes and the HIP stream handle.
 
 The library is mandatory on the product path: if it is missing or does not load, every op
@@ -177,6 +177,14 @@ REGION_SIGNATURES = {
     'cvar_score_map': (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p]),
 }
 
+# include/cvar_topn.h: the N most likely codes beside cvar_score_rows and the sparse soft-target loss beside cvar_kd_fwd_bwd (DESIGN.md
+# 8e).  A table of its own for the same reason; no signature of the other eight headers changed, so neither version moved
+TOPN_MAX = 64
+TOPN_SIGNATURES = {
+    'cvar_score_topn': (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_p]),
+    'cvar_kd_topn_fwd_bwd': (c_i, [c_p, c_p, c_p, c_p, c_i, c_p, c_f, c_p, c_p, c_i, c_l, c_i, c_p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -200,7 +208,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
             pass
         lib = C.CDLL(path, mode=C.RTLD_GLOBAL)
         for name, (res, args) in (*SIGNATURES.items(), *SERVE_SIGNATURES.items(), *ACCUM_SIGNATURES.items(), *KVCACHE_SIGNATURES.items(),
-                                  *WIDE_SIGNATURES.items(), *POLICY_SIGNATURES.items(), *DISTILL_SIGNATURES.items(), *REGION_SIGNATURES.items()):
+                                  *WIDE_SIGNATURES.items(), *POLICY_SIGNATURES.items(), *DISTILL_SIGNATURES.items(), *REGION_SIGNATURES.items(), *TOPN_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -55,7 +55,8 @@ def build_lib(force: bool = False, verbose: bool = True) -> str:
                                                          os.path.join(os.path.dirname(HERE), 'include', 'cvar_wide.h'),
                                                          os.path.join(os.path.dirname(HERE), 'include', 'cvar_policy.h'),
                                                          os.path.join(os.path.dirname(HERE), 'include', 'cvar_distill.h'),
-                                                         os.path.join(os.path.dirname(HERE), 'include', 'cvar_region.h')]
+                                                         os.path.join(os.path.dirname(HERE), 'include', 'cvar_region.h'),
+                                                         os.path.join(os.path.dirname(HERE), 'include', 'cvar_topn.h')]
     stamp = os.path.join(OBJ, 'digest.txt')
     dig = _digest(deps)
     if not force and os.path.exists(LIB) and os.path.exists(stamp) and open(stamp).read() == dig:

@@ -11,6 +11,7 @@
 #include "cvar_common.h"
 #include "../../include/cvar_serve.h"
 #include "../../include/cvar_region.h"
+#include "../../include/cvar_topn.h"
 
 struct SampleParams {
     const float* logits;
@@ -92,6 +93,11 @@ __device__ __forceinline__ float combine_logits(const P& p, long b, long t, int 
     for (int r = 1; r < p.nrep; ++r) v = __fadd_rn(v, __fmul_rn(cf[r], base[(long)r * p.B * rowstride]));
     return v;
 }
+
+// the rank order of the greedy id and of cvar_score_rows - value descending (floats compared as floats), id ascending - for the top-N rounds.  It restates
+// merge_top2's predicate on purpose: merge_top2 written through this helper compiled cfg_greedy_kernel to 13 VGPRs instead of 11 and the two score kernels to
+// 50 instead of 48, and the resource lines of the existing kernels are kept as they are
+__device__ __forceinline__ bool rank_before(float a, int ia, float b, int ib) { return (a > b) || (a == b && ia < ib); }
 
 struct Top2 { float b1; int i1; float b2; };
 __device__ __forceinline__ Top2 merge_top2(Top2 a, Top2 b) {
@@ -517,6 +523,16 @@ struct MapScoreParams : ScoreParams {       // cvar_score_map (include/cvar_regi
 __device__ __forceinline__ const float* coef_of(const ScoreParams& p, long b, long) { return p.coef + b * 4; }
 __device__ __forceinline__ const float* coef_of(const MapScoreParams& p, long b, long t) { return p.coef + (b * p.ldc + t) * 4; }
 
+// The fixed order of S, shared by score_token and the top-N kernel so that their bits cannot drift apart: a term is expf(x - m) with the difference
+// rounded first; a wave adds its lanes' partials over the xor tree; the four wave partials are added in order 0..3; logprob = (x - m) - logf(S).
+__device__ __forceinline__ float score_wave_sum(float s) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s = __fadd_rn(s, __shfl_xor(s, o, 64));
+    return s;
+}
+__device__ __forceinline__ float score_waves_0123(const float* w) { return __fadd_rn(__fadd_rn(__fadd_rn(w[0], w[1]), w[2]), w[3]); }
+__device__ __forceinline__ float score_logprob(float x, float m, float logS) { return __fsub_rn(__fsub_rn(x, m), logS); }
+
 template <class P>
 __device__ __forceinline__ void score_token(const P& p) {
     constexpr int EPT = 16;
@@ -567,20 +583,18 @@ __device__ __forceinline__ void score_token(const P& p) {
             cnt += (v[j] > xt || (v[j] == xt && e < tgt)) ? 1 : 0;
         }
     }
+    s = score_wave_sum(s);
+    u = score_wave_sum(u);
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        s = __fadd_rn(s, __shfl_xor(s, o, 64));
-        u = __fadd_rn(u, __shfl_xor(u, o, 64));
-        cnt += __shfl_xor(cnt, o, 64);
-    }
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
     if ((tid & 63) == 0) { ssum[tid >> 6] = s; sent[tid >> 6] = u; scnt[tid >> 6] = cnt; }
     __syncthreads();
     if (tid == 0) {
-        const float S = __fadd_rn(__fadd_rn(__fadd_rn(ssum[0], ssum[1]), ssum[2]), ssum[3]);
-        const float U = __fadd_rn(__fadd_rn(__fadd_rn(sent[0], sent[1]), sent[2]), sent[3]);
+        const float S = score_waves_0123(ssum);
+        const float U = score_waves_0123(sent);
         const float logS = logf(S);
         const long o = b * p.ldo + t;
-        if (p.logprob) p.logprob[o] = tgt >= 0 ? __fsub_rn(__fsub_rn(xt, m), logS) : 0.f;
+        if (p.logprob) p.logprob[o] = tgt >= 0 ? score_logprob(xt, m, logS) : 0.f;
         if (p.entropy) p.entropy[o] = __fsub_rn(logS, __fdiv_rn(U, S));
         if (p.rank) p.rank[o] = tgt >= 0 ? (scnt[0] + scnt[1]) + (scnt[2] + scnt[3]) : -1;
         if (p.argmax) p.argmax[o] = r.i1;
@@ -589,6 +603,103 @@ __device__ __forceinline__ void score_token(const P& p) {
 
 __global__ __launch_bounds__(256) void cfg_score_rows_kernel(const ScoreParams p) { score_token(p); }
 __global__ __launch_bounds__(256) void cfg_score_map_kernel(const MapScoreParams p) { score_token(p); }
+
+// ---- the N most likely codes (cvar_score_topn, include/cvar_topn.h) --------------------------------------------------------------------------
+// score_token's row in score_token's registers (combine_logits, thread-strided ownership), then N rounds of a block arg-max in score_token's
+// rank order - value descending, id ascending, floats compared as floats - over the elements no earlier round took.  A thread keeps the best of
+// its own sixteen and rescans them only after it owned a winner, so a round is one 64-lane tree, one barrier (the wave slots are double-buffered
+// on the round's parity) and a four-way merge.  The order is rank_before, merge_top2's predicate restated (see there), so round 0's winner is score_token's maximum, bits
+// included; S goes through score_token's own helpers (score_wave_sum, score_waves_0123, score_logprob), and the tail sum runs in the same order over
+// the elements left.
+struct TopnParams {
+    const float* logits;
+    int B, nrep, l, V, ldv;
+    const float* coef;                      // [B][4] fp32: the table cvar_score_rows reads
+    int N, ldo;
+    int* top_id;
+    float* top_logprob;
+    float* tail_logprob;
+};
+__device__ __forceinline__ const float* coef_of(const TopnParams& p, long b, long) { return p.coef + b * 4; }
+
+__global__ __launch_bounds__(256) void cfg_score_topn_kernel(const TopnParams p) {
+    constexpr int EPT = 16;
+    constexpr int NONE = 0x7fffffff;                               // loses every tie: a real -inf element ranks ahead of "nothing left"
+    __shared__ float swv[2][4], sel_v[64], ssum[4], stail[4];
+    __shared__ int swi[2][4], sel_i[64];
+    const int tid = threadIdx.x;
+    const long bt = blockIdx.x;
+    const long b = bt / p.l, t = bt % p.l;
+    float v[EPT];
+#pragma unroll
+    for (int j = 0; j < EPT; ++j) {
+        const int e = j * 256 + tid;
+        v[j] = e < p.V ? combine_logits(p, b, t, e) : -INFINITY;
+    }
+    unsigned taken = 0u;
+    float lv = -INFINITY;
+    int li = NONE;
+#pragma unroll
+    for (int j = 0; j < EPT; ++j) {
+        const int e = j * 256 + tid;
+        if (e < p.V && rank_before(v[j], e, lv, li)) { lv = v[j]; li = e; }
+    }
+    for (int r = 0; r < p.N; ++r) {
+        float wv = lv;
+        int wi = li;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ov = __shfl_xor(wv, o, 64);
+            const int oi = __shfl_xor(wi, o, 64);
+            if (rank_before(ov, oi, wv, wi)) { wv = ov; wi = oi; }
+        }
+        if ((tid & 63) == 0) { swv[r & 1][tid >> 6] = wv; swi[r & 1][tid >> 6] = wi; }
+        __syncthreads();
+        wv = swv[r & 1][0]; wi = swi[r & 1][0];
+        for (int w = 1; w < 4; ++w)
+            if (rank_before(swv[r & 1][w], swi[r & 1][w], wv, wi)) { wv = swv[r & 1][w]; wi = swi[r & 1][w]; }
+        if (tid == 0) { sel_v[r] = wv; sel_i[r] = wi; }
+        if (wi < p.V && (wi & 255) == tid) {                       // the owner strikes it and rescans its sixteen
+            taken |= 1u << (wi >> 8);
+            lv = -INFINITY; li = NONE;
+#pragma unroll
+            for (int j = 0; j < EPT; ++j) {
+                const int e = j * 256 + tid;
+                if (e < p.V && !((taken >> j) & 1u) && rank_before(v[j], e, lv, li)) { lv = v[j]; li = e; }
+            }
+        }
+    }
+    __syncthreads();
+    const float m = sel_v[0];
+    float s = 0.f, st = 0.f;
+#pragma unroll
+    for (int j = 0; j < EPT; ++j) {
+        const int e = j * 256 + tid;
+        if (e < p.V) {
+            const float d = __fsub_rn(v[j], m);
+            const float ex = expf(d);
+            s = __fadd_rn(s, ex);
+            if (!((taken >> j) & 1u)) st = __fadd_rn(st, ex);
+        }
+    }
+    s = score_wave_sum(s);
+    st = score_wave_sum(st);
+    if ((tid & 63) == 0) { ssum[tid >> 6] = s; stail[tid >> 6] = st; }
+    __syncthreads();
+    const float S = score_waves_0123(ssum);
+    const float logS = logf(S);
+    const long o = b * p.ldo + t;
+    if (tid < p.N) {
+        const int id = sel_i[tid];
+        const bool real = id < p.V;
+        if (p.top_id) p.top_id[o * p.N + tid] = real ? id : -1;
+        if (p.top_logprob) p.top_logprob[o * p.N + tid] = real ? score_logprob(sel_v[tid], m, logS) : -INFINITY;
+    }
+    if (p.tail_logprob && tid == 0) {
+        const float St = score_waves_0123(stail);
+        p.tail_logprob[o] = St > 0.f ? __fsub_rn(logf(St), logS) : -INFINITY;
+    }
+}
 
 extern "C" int cvar_cfg_sample(const float* logits, int B, int nrep, int l, int V, const float* coef_host,
                                int top_k, float top_p, uint64_t seed, const uint64_t* seed_dev, int stage, int n_draw,
@@ -705,6 +816,22 @@ extern "C" int cvar_score_map(const float* logits, int B, int nrep, int l, int V
     p.combined = combined; p.logprob = logprob; p.entropy = entropy; p.rank = (int*)rank; p.argmax = (int*)argmax;
     p.ldc = ldc;
     hipLaunchKernelGGL(cfg_score_map_kernel, dim3((unsigned)((long)B * l)), dim3(256), 0, as_stream(stream), p);
+    CVAR_CHECK_LAUNCH();
+    return CVAR_OK;
+}
+
+// ---- the N most likely codes (include/cvar_topn.h): cvar_score_rows' launch shape and refusals ---------------------------------------------------
+extern "C" int cvar_score_topn(const float* logits, int B, int nrep, int l, int V, const float* coef, int N, int32_t* top_id, float* top_logprob,
+                               float* tail_logprob, int ldo, int ldv, void* stream) {
+    if (!logits || !coef || B <= 0 || l <= 0 || V < 1 || (ldo != 0 && ldo < l)) return CVAR_EINVAL;
+    if (!top_id && !top_logprob) return CVAR_EINVAL;
+    if (nrep < 1 || nrep > 4 || V > 4096 || N < 1 || N > 64) return CVAR_EUNSUPPORTED;
+    if (ldv != 0 && ldv < V) return CVAR_EINVAL;
+    TopnParams p;
+    p.logits = logits; p.B = B; p.nrep = nrep; p.l = l; p.V = V; p.ldv = ldv ? ldv : V;
+    p.coef = coef; p.N = N; p.ldo = ldo ? ldo : l;
+    p.top_id = (int*)top_id; p.top_logprob = top_logprob; p.tail_logprob = tail_logprob;
+    hipLaunchKernelGGL(cfg_score_topn_kernel, dim3((unsigned)((long)B * l)), dim3(256), 0, as_stream(stream), p);
     CVAR_CHECK_LAUNCH();
     return CVAR_OK;
 }

@@ -6,6 +6,7 @@
 #include "../../include/cvar_accum.h"
 #include "../../include/cvar_policy.h"
 #include "../../include/cvar_distill.h"
+#include "../../include/cvar_topn.h"
 
 constexpr int RED_S = 8;      // row segments of the per-sequence column reductions (scalar fallbacks)
 // The vector kernels split every sequence into red_segments(R, l) row segments so that R * segments blocks fill the chip
@@ -834,6 +835,86 @@ extern "C" int cvar_kd_fwd_bwd(const float* logits, const float* teacher, int ld
     dim3 grid((unsigned)M), block(256);
     if (!dlogits || out_dtype == CVAR_F32) hipLaunchKernelGGL(kd_kernel<float>, grid, block, 0, as_stream(stream), logits, teacher, (long)ldt, weight, gscale, loss_tok, (float*)dlogits, V);
     else hipLaunchKernelGGL(kd_kernel<bf16_t>, grid, block, 0, as_stream(stream), logits, teacher, (long)ldt, weight, gscale, loss_tok, (bf16_t*)dlogits, V);
+    CVAR_CHECK_LAUNCH();
+    return CVAR_OK;
+}
+
+// ---- sparse soft-target loss forward + backward (include/cvar_topn.h): kd_kernel's row pass over the student row (mx, se), a teacher
+// of N listed codes (id, log-probability) plus the log of the mass on all the others.  slot_of[v] in LDS is 0 for an unlisted code and j + 1 for the
+// code slot j lists (distinct ids: plain stores); the listed terms of the KL sit one per lane in wave 0, the tail cell's term is added last
+template <typename TO>
+__global__ __launch_bounds__(256) void kd_topn_kernel(const float* __restrict__ logits, const int* __restrict__ t_id, const float* __restrict__ t_lp,
+                                                     const float* __restrict__ t_tail, int N, const float* __restrict__ weight, float gscale,
+                                                     float* __restrict__ loss_tok, TO* __restrict__ dlogits, int V) {
+    extern __shared__ unsigned char slot_of[];                      // [V]
+    __shared__ float red[4], sq[64];
+    const long m = blockIdx.x;
+    const float* lr = logits + m * V;
+    for (int v = threadIdx.x; v < V; v += 256) slot_of[v] = 0;
+    __syncthreads();
+    int id = -1;
+    float tl = 0.f, q = 0.f;
+    if (threadIdx.x < N) {
+        id = t_id[m * N + threadIdx.x];
+        if (id >= V) id = -1;                                       // out of contract: nothing outside the row is touched
+        if (id >= 0) { tl = t_lp[m * N + threadIdx.x]; q = __expf(tl); slot_of[id] = (unsigned char)(threadIdx.x + 1); }
+    }
+    if (threadIdx.x < 64) sq[threadIdx.x] = q;
+    float mx = -INFINITY;
+    for (int v = threadIdx.x; v < V; v += 256) mx = fmaxf(mx, lr[v]);
+    mx = wave_max(mx);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    __syncthreads();
+    float se = 0.f;
+    for (int v = threadIdx.x; v < V; v += 256) se += __expf(lr[v] - mx);
+    se = wave_sum(se);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = se;
+    __syncthreads();
+    se = (red[0] + red[1]) + (red[2] + red[3]);
+    __syncthreads();
+    const float lse_x = logf(se) + mx;
+    const float g = (weight ? weight[m] : 1.0f) * gscale;
+    const float inv = 1.0f / se;
+    const float tt = t_tail ? t_tail[m] : -INFINITY;
+    const float r = (tt > -INFINITY && tt < INFINITY) ? __expf(tt) : 0.f;
+    float f = 1.0f, tail_term = 0.f;
+    if (r > 0.f) {                                                  // block-uniform
+        float pt = 0.f;
+        for (int v = threadIdx.x; v < V; v += 256)
+            if (!slot_of[v]) pt += __expf(lr[v] - mx) * inv;
+        pt = wave_sum(pt);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = pt;
+        __syncthreads();
+        pt = (red[0] + red[1]) + (red[2] + red[3]);
+        f = 1.0f - r / pt;
+        tail_term = r * (tt - logf(pt));
+    }
+    if (threadIdx.x < 64) {
+        float kl = id >= 0 ? q * (tl - (lr[id] - lse_x)) : 0.f;
+        kl = wave_sum(kl);
+        if (threadIdx.x == 0) loss_tok[m] = r > 0.f ? kl + tail_term : kl;
+    }
+    if (dlogits) {
+        for (int v = threadIdx.x; v < V; v += 256) {
+            const float pr = __expf(lr[v] - mx) * inv;
+            const int s = slot_of[v];
+            Elem<TO>::st(dlogits + m * V + v, s ? (pr - sq[s - 1]) * g : (pr * f) * g);
+        }
+    }
+}
+extern "C" int cvar_kd_topn_fwd_bwd(const float* logits, const int32_t* t_id, const float* t_lp, const float* t_tail, int N, const float* weight,
+                                    float gscale, float* loss_tok, void* dlogits, int out_dtype, int64_t M, int V, void* stream) {
+    if (!logits || !t_id || !t_lp || !loss_tok || M <= 0 || V <= 1) return CVAR_EINVAL;
+    if (out_dtype != CVAR_F32 && out_dtype != CVAR_BF16) return CVAR_EUNSUPPORTED;
+    if (N < 1 || N > 64 || V > 32768) return CVAR_EUNSUPPORTED;
+    dim3 grid((unsigned)M), block(256);
+    const size_t lds = (size_t)((V + 15) & ~15);
+    if (!dlogits || out_dtype == CVAR_F32)
+        hipLaunchKernelGGL(kd_topn_kernel<float>, grid, block, lds, as_stream(stream), logits, (const int*)t_id, t_lp, t_tail, N, weight, gscale, loss_tok, (float*)dlogits, V);
+    else
+        hipLaunchKernelGGL(kd_topn_kernel<bf16_t>, grid, block, lds, as_stream(stream), logits, (const int*)t_id, t_lp, t_tail, N, weight, gscale, loss_tok, (bf16_t*)dlogits, V);
     CVAR_CHECK_LAUNCH();
     return CVAR_OK;
 }

@@ -796,10 +796,17 @@ class TokenScores:
       rank     int32  the number of codes ahead of the id (0 = the greedy id, lowest index on ties)
       argmax   int32  the greedy id
       sampled  bool   False where the token was teacher-forced or kept by an edit; those tokens are scored too (the head computes their
-                      logits anyway)"""
+                      logits anyway)
+    and, under ``top_logprobs=N`` (None without it; include/cvar_topn.h: cvar_score_topn, one more launch per scale):
+      top_ids       (B, L, N) int32  the N most likely codes of that distribution in rank order (top_ids[..., rank] is the token's id where
+                                     rank < N, top_ids[..., 0] is argmax); -1 past the vocabulary
+      top_logprobs  (B, L, N) fp32   their log-probabilities, the bits `logprob` holds for that code; -inf past the vocabulary
+      tail_logprob  (B, L) fp32      the log of the mass of all the other codes; -inf when there is none"""
 
-    def __init__(self, logprob, entropy, rank, argmax, patch_nums, mask_factor: int, mask_first: bool, sampled=None, forced=None):
+    def __init__(self, logprob, entropy, rank, argmax, patch_nums, mask_factor: int, mask_first: bool, sampled=None, forced=None, top_ids=None,
+                 top_logprobs=None, tail_logprob=None):
         self.logprob, self.entropy, self.rank, self.argmax = logprob, entropy, rank, argmax
+        self.top_ids, self.top_logprobs, self.tail_logprob = top_ids, top_logprobs, tail_logprob
         self.patch_nums, self.mask_factor, self.mask_first = tuple(int(p) for p in patch_nums), int(mask_factor), bool(mask_first)
         self._sampled, self._forced = sampled, forced          # a (B, L) / (L,) bool pattern, or the forced-token table (>= 0: not sampled)
 
@@ -841,8 +848,23 @@ class TokenScores:
     def per_scale(self):
         """one TokenScores per scale, its fields the (B, mask_factor pn^2) column views of this one's"""
         s = self.sampled
+        cut = lambda t, b, e: None if t is None else t[:, b:e]
         return [TokenScores(self.logprob[:, b:e], self.entropy[:, b:e], self.rank[:, b:e], self.argmax[:, b:e], (pn,), self.mask_factor, self.mask_first,
-                            sampled=s[:, b:e]) for (b, e), pn in zip(self._bounds(), self.patch_nums)]
+                            sampled=s[:, b:e], top_ids=cut(self.top_ids, b, e), top_logprobs=cut(self.top_logprobs, b, e),
+                            tail_logprob=cut(self.tail_logprob, b, e)) for (b, e), pn in zip(self._bounds(), self.patch_nums)]
+
+    def _without_alternatives(self) -> 'TokenScores':
+        """these scores with the three top-N fields left out (the other fields shared, `sampled` as evaluated so far)"""
+        return TokenScores(self.logprob, self.entropy, self.rank, self.argmax, self.patch_nums, self.mask_factor, self.mask_first, sampled=self._sampled,
+                           forced=self._forced)
+
+    def sparse_loss(self, weights=None):
+        """the SparseDistillLoss of a training step along these tokens: the N most likely codes and the tail mass as the teacher -
+        with score_infer_cfg(..., top_logprobs=N) a sparse guided teacher along DATASET tokens.  weights: (B, L) token weights or None"""
+        if self.top_ids is None:
+            raise ValueError('sparse_loss: these scores hold no alternatives - ask for them with top_logprobs=N')
+        from .train import SparseDistillLoss
+        return SparseDistillLoss(self.top_ids, self.top_logprobs, self.tail_logprob, weights=weights)
 
     def total(self, half: Optional[str] = None, sampled_only: bool = False) -> torch.Tensor:
         """(B,) float64: the sum of the log-probabilities over all tokens, or over one half ('control' / 'image'); sampled_only leaves out
@@ -874,6 +896,51 @@ class DistillTargets(NamedTuple):
         """the DistillLoss of a training step on this batch: the guided logits as soft targets, the teacher-forced tokens weighted 0"""
         from .train import DistillLoss
         return DistillLoss(self.logits, weights=self.sampled)
+
+
+class SparseDistillTargets(NamedTuple):
+    """What a generation call returns beside its images under ``distill_topn=N``: DistillTargets with the guided distribution of
+    every token as its N most likely codes and the mass of the rest - N x 8 + 4 bytes per token instead of 4 V, never materialised as (B, L, V) -
+        trainer.step_tokens(t.ids_img, t.ids_ctrl, cls, types, distill=t.loss(), mask_first=t.mask_first)
+      ids_img, ids_ctrl  as DistillTargets'
+      top_ids, top_logprobs, tail_logprob   (B, L, N) int32, (B, L, N) fp32, (B, L) fp32: TokenScores' fields of the same names
+      sampled, mask_first                   as DistillTargets'"""
+    ids_img: torch.Tensor
+    ids_ctrl: Optional[torch.Tensor]
+    top_ids: torch.Tensor
+    top_logprobs: torch.Tensor
+    tail_logprob: torch.Tensor
+    sampled: torch.Tensor
+    mask_first: bool
+
+    def loss(self):
+        """the SparseDistillLoss of a training step on this batch, the teacher-forced tokens weighted 0"""
+        from .train import SparseDistillLoss
+        return SparseDistillLoss(self.top_ids, self.top_logprobs, self.tail_logprob, weights=self.sampled)
+
+
+TOPN_MAX = 64                                        # cvar_score_topn's N (include/cvar_topn.h)
+
+
+def _top_n(what: str, n, logprobs: bool = True) -> Optional[int]:
+    """top_logprobs= / distill_topn= -> N, or None when it is not given; refused in words on the host"""
+    if n is None:
+        return None
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= int(n) <= TOPN_MAX:
+        raise ValueError(f'{what}={n!r}: an integer from 1 to {TOPN_MAX} (the number of most likely codes reported per token)')
+    if not logprobs:
+        raise ValueError(f'{what}={n!r} needs logprobs=True: the alternatives are fields of the TokenScores that logprobs=True returns')
+    return int(n)
+
+
+_NO_REGION_TOPN = ('{}: top_logprobs is not offered under regional guidance - the alternatives are ranked under ONE weight row per request, and a form that '
+                   'reads the per-token weight map is not built; score the sample with logprobs=True alone')
+
+
+def _topn_buffers(B: int, L: int, N: int, dev):
+    """(top_ids, top_logprobs, tail_logprob) device buffers (B, L, N) / (B, L) that the top-N launch of every scale writes its columns of"""
+    return (torch.empty(B, L, N, device=dev, dtype=torch.int32), torch.empty(B, L, N, device=dev, dtype=torch.float32),
+            torch.empty(B, L, device=dev, dtype=torch.float32))
 
 
 def _score_buffers(B: int, L: int, dev):
@@ -1059,13 +1126,16 @@ class _RowDraw(NamedTuple):
     launch is the only consumer of the logits, and the last scale's ids feed nothing
     coef_map (regional guidance): device (B, L, 4) fp32, the combine weights of every token (ops.region_coef_table); the sampling and the score
     launch of every scale then read their columns of it instead of rows[3][si] (ops.cfg_sample_map / ops.score_map), the sample's nrep = K + 1
-    rows are [label_0 ; ... ; label_{K-1} ; unconditional], and ONE id row is drawn and fed to all of them"""
+    rows are [label_0 ; ... ; label_{K-1} ; unconditional], and ONE id row is drawn and fed to all of them
+    topn (top_logprobs=N, with score): device (top_ids, top_logprobs, tail_logprob) buffers (B, L, N) / (B, L, N) / (B, L); every scale then
+    issues ops.score_topn next to its ops.score_rows, with that launch's logits, weights and strides"""
     rows: Any
     forced: Optional[torch.Tensor] = None
     ad: Any = None
     score: Any = None
     sample: bool = True
     coef_map: Optional[torch.Tensor] = None
+    topn: Any = None
 
 
 GEMM_PRECISIONS = (None, 'bf16x3', 'fp8')
@@ -1848,19 +1918,22 @@ class ControlVAR(nn.Module):
 
     @torch.no_grad()
     def _generate(self, B, label_B, g_seed, cfg_scale, top_k, top_p, more_smooth, cond_type, four_way, c_mask, c_img,
-                  force_idx=None, trace: bool = False, gumbel=None, adapter=None, logprobs: bool = False, targets: Optional[dict] = None):
+                  force_idx=None, trace: bool = False, gumbel=None, adapter=None, logprobs: bool = False, targets: Optional[dict] = None,
+                  topn: Optional[int] = None):
         """-> f_hat, or (f_hat, TokenScores) with logprobs=True.  cfg_scale=None: generation without guidance rows (nrep == 1).
-        targets (distill_targets=True): the dict _generate_core fills; the call then traces (last_trace holds the combined logits)"""
+        targets (distill_targets=True): the dict _generate_core fills; the call then traces (last_trace holds the combined logits) - unless
+        the dict says 'topn' (distill_topn=N): the sparse targets come from the score buffers, and nothing (B, L, V) is kept.
+        topn (top_logprobs=N / distill_topn=N, with logprobs): the N most likely codes beside every score"""
         if cfg_scale is None:
             self._check_unguided(four_way, adapter)
         if targets is not None:
             self._check_distill_targets(four_way, more_smooth)
-            trace = True
+            trace = trace or 'topn' not in targets
         nrep = self._guidance_rows(four_way, cfg_scale is None)
         # adapter= and logprobs=True select the per-request path, as a per-row cfg does
         if adapter is not None or logprobs or _per_request(cfg_scale, top_k, top_p, g_seed, four_way):
             return self._generate_rows(B, label_B, g_seed, cfg_scale, top_k, top_p, more_smooth, cond_type, four_way, c_mask, c_img, force_idx, trace,
-                                       adapter=adapter, logprobs=logprobs, targets=targets)
+                                       adapter=adapter, logprobs=logprobs, targets=targets, topn=topn)
         if four_way and cfg_scale is not None:
             cfg_scale = tuple(cfg_scale)
         if top_k > self.cfg.vocab:                     # helpers.py:8-10: torch.topk raises on k > V; top_k <= 0 means no top-k filter
@@ -1944,7 +2017,7 @@ class ControlVAR(nn.Module):
 
     @torch.no_grad()
     def _generate_rows(self, B, label_B, g_seed, cfg_scale, top_k, top_p, more_smooth, cond_type, four_way, c_mask, c_img, force_idx=None, trace: bool = False,
-                       adapter=None, logprobs: bool = False, targets: Optional[dict] = None):
+                       adapter=None, logprobs: bool = False, targets: Optional[dict] = None, topn: Optional[int] = None):
         """per-request mode (an addition of this library): any of cfg / top_k / top_p / g_seed given per batch row.  Row b produces exactly
         what the scalar call produces at B = 1 with (label_b, cond_type_b, cfg_b, top_k_b, top_p_b, g_seed = seed_b): combined logits, kept-set
         size, margin, ids and image - bit for bit under deterministic_plan=True (the sampler always is; the plan makes the logits independent
@@ -1957,10 +2030,11 @@ class ControlVAR(nn.Module):
         slots = self._adapter_slots(adapter, B, nrep)
         table = _request_table(B, cfg_scale, top_k, top_p, g_seed, four_way, self.cfg.vocab, len(self.cfg.pyramid.patch_nums), slots=slots)
         f_hat, scores = self._run_rows(B, label_B, cond_type, four_way, table, c_mask=c_mask, c_img=c_img, force_idx=force_idx, trace=trace,
-                                       logprobs=logprobs, sampled=self._sampled_pattern(four_way, c_mask, c_img, force_idx), nrep=nrep, targets=targets)
+                                       logprobs=logprobs, sampled=self._sampled_pattern(four_way, c_mask, c_img, force_idx), nrep=nrep, targets=targets,
+                                       topn=topn)
         return (f_hat, scores) if logprobs else f_hat
 
-    def _row_state(self, B: int, table: _RequestTable, logprobs: bool, forced=None, sample: bool = True, coef_map=None):
+    def _row_state(self, B: int, table: _RequestTable, logprobs: bool, forced=None, sample: bool = True, coef_map=None, topn: Optional[int] = None):
         """the device state of one batch of requests -> (the table's device buffer, the _RowDraw over it).  The request table and the
         adapter slots are one upload; a graph builds this once and refreshes the buffer."""
         tab_dev = table.host.to(self.device)
@@ -1968,12 +2042,13 @@ class ControlVAR(nn.Module):
         if table.n_seq:
             from . import lora
             ad = (lora.bank_pack(self), table.slot_view(tab_dev))
-        return tab_dev, _RowDraw(table.views(tab_dev), forced, ad, _score_buffers(B, self.cfg.pyramid.L, self.device) if logprobs else None, sample, coef_map)
+        return tab_dev, _RowDraw(table.views(tab_dev), forced, ad, _score_buffers(B, self.cfg.pyramid.L, self.device) if logprobs else None, sample, coef_map,
+                                 _topn_buffers(B, self.cfg.pyramid.L, topn, self.device) if logprobs and topn else None)
 
     @torch.no_grad()
     def _run_rows(self, B, label_B, cond_type, four_way, table: _RequestTable, *, c_mask=None, c_img=None, force_idx=None, trace: bool = False,
                   logprobs: bool = False, sampled=None, mask_first: Optional[bool] = None, edit=None, score_halves=None, nrep: Optional[int] = None, targets: Optional[dict] = None,
-                  region=None):
+                  region=None, topn: Optional[int] = None):
         """the per-request runner behind _generate_rows, edit_infer_cfg and score_infer_cfg: the validated table and the entry point's own extras
         -> (f_hat, TokenScores or None).  mask_first=None draws the (control, image) order (one per call, as the scalar path).
         edit: the host halves (src_ctrl, keep_ctrl, src_img, keep_img) of _edit_half - the forced-token table is built for the drawn order.
@@ -2004,13 +2079,13 @@ class ControlVAR(nn.Module):
         coef_map = None
         if region is not None:
             coef_map = self._region_table(B, K, *[None if t is None else torch.as_tensor(t).to(dev) for t in region], mask_first)
-        _, how = self._row_state(B, table, logprobs or score_halves is not None, forced, sample=score_halves is None, coef_map=coef_map)
+        _, how = self._row_state(B, table, logprobs or score_halves is not None, forced, sample=score_halves is None, coef_map=coef_map, topn=topn)
         f_hat = self._generate_core(B, labels_all, types_all, four_way, how, c_mask, c_img, force_idx, trace, mask_first, nrep=nrep, targets=targets)
         if trace and forced is not None:
             self.last_trace['forced'] = forced
         if trace and coef_map is not None:
             self.last_trace['coef'] = coef_map
-        return f_hat, (self._token_scores(how.score, mask_first, sampled, forced) if how.score is not None else None)
+        return f_hat, (self._token_scores(how.score, mask_first, sampled, forced, how.topn) if how.score is not None else None)
 
     def _check_logprobs(self):
         """what logprobs=True / score_infer_cfg do not offer beyond _check_per_request's list, said on the host before any device work"""
@@ -2018,8 +2093,9 @@ class ControlVAR(nn.Module):
             raise NotImplementedError('token log-probabilities: separator models are not offered (their scales carry special tokens between the halves, '
                                       'which the (B, L) score layout does not hold)')
 
-    def _token_scores(self, score, mask_first: bool, sampled=None, forced=None) -> TokenScores:
-        return TokenScores(*score, self.cfg.pyramid.patch_nums, self.cfg.mask_factor, mask_first, sampled=sampled, forced=forced)
+    def _token_scores(self, score, mask_first: bool, sampled=None, forced=None, topn=None) -> TokenScores:
+        top = dict(zip(('top_ids', 'top_logprobs', 'tail_logprob'), topn)) if topn is not None else {}
+        return TokenScores(*score, self.cfg.pyramid.patch_nums, self.cfg.mask_factor, mask_first, sampled=sampled, forced=forced, **top)
 
     def _sampled_pattern(self, four_way: bool, c_mask, c_img, force_idx) -> Optional[torch.Tensor]:
         """(L,) bool on the host: which tokens of a generation are sampled (None: all).  The four-branch path lays control first."""
@@ -2050,16 +2126,19 @@ class ControlVAR(nn.Module):
         if self.cfg.separate_decoding and not self.cfg.indep and not four_way:
             raise NotImplementedError('distill_targets: the two-pass separate_decoding branch (control_var.py:428-485) is not offered')
 
-    def _distill_targets(self, targets: dict, B: int, sampled) -> DistillTargets:
-        """the filled dict of _generate_core and the trace of the same call -> DistillTargets"""
+    def _distill_targets(self, targets: dict, B: int, sampled, scores: Optional[TokenScores] = None):
+        """the filled dict of _generate_core and the trace of the same call -> DistillTargets; with the dict's 'topn' (distill_topn=N) the
+        top-N fields of the same call's scores -> SparseDistillTargets"""
         mf, pns, L = self.cfg.mask_factor, self.cfg.pyramid.patch_nums, self.cfg.pyramid.L
         ids, mask_first = targets['ids'], targets['mask_first']
         first = torch.cat([i[:, :pn * pn] for i, pn in zip(ids, pns)], dim=1).contiguous()
         second = torch.cat([i[:, pn * pn:] for i, pn in zip(ids, pns)], dim=1).contiguous() if mf == 2 else None
         ids_img, ids_ctrl = (first, None) if mf == 1 else (second, first) if mask_first else (first, second)
-        logits = torch.cat(self.last_trace['logits'], dim=1)
         col = torch.ones(L, dtype=torch.bool) if sampled is None else sampled
-        return DistillTargets(ids_img, ids_ctrl, logits, col.to(self.device)[None].expand(B, -1).contiguous(), mask_first)
+        col = col.to(self.device)[None].expand(B, -1).contiguous()
+        if 'topn' in targets:
+            return SparseDistillTargets(ids_img, ids_ctrl, scores.top_ids, scores.top_logprobs, scores.tail_logprob, col, mask_first)
+        return DistillTargets(ids_img, ids_ctrl, torch.cat(self.last_trace['logits'], dim=1), col, mask_first)
 
     def _draw_scale(self, how, logits, B: int, nrep: int, l: int, si: int, ratio: float, ldv: int, cols, tr, force_idx):
         """draw the ids of one scale (sampling call si, at `ratio` of the way through the scales) from its logits, as `how` says (_ScalarDraw /
@@ -2123,6 +2202,8 @@ class ControlVAR(nn.Module):
             raise ValueError('score_only: score buffers and force_idx are required')
         if row and how.forced is not None and (how.rows is None or four_way):
             raise ValueError('forced: the per-request joint path only (rows given, two branches)')
+        if row and how.topn is not None and (how.score is None or how.coef_map is not None):
+            raise ValueError('topn: beside the score launch of the per-request table only (score buffers given, no weight map)')
         ad, score = (how.ad, how.score) if row else (None, None)
         cfg, P = self.cfg, self._pack()
         vae: VQVAE = self.vae_proxy[0]
@@ -2167,6 +2248,9 @@ class ControlVAR(nn.Module):
             elif score is not None:
                 ops.score_rows(logits, B, nrep, l, cfg.vocab, how.rows[3][si], idx[:B], None, score[0][:, cols], score[1][:, cols], score[2][:, cols],
                                score[3][:, cols], ldv=cfg.head_ld)
+                if how.topn is not None:
+                    ops.score_topn(logits, B, nrep, l, cfg.vocab, how.rows[3][si], int(how.topn[0].shape[2]), how.topn[0][:, cols], how.topn[1][:, cols],
+                                   how.topn[2][:, cols], ldv=cfg.head_ld)
                 if not how.sample and si == nstage - 1:
                     break
             if cfg.separator and py.sp(si):
@@ -2278,7 +2362,7 @@ class ControlVAR(nn.Module):
     @torch.no_grad()
     def _graph_runner(self, B, four_way, labels_all, types_all, cfg, top_k, top_p, finish, *, per_request: bool, adapters: bool = False,
                       logprobs: bool = False, forced=None, teach=None, refresh=None, prologue=None, sampled=None, check_rows: bool = True,
-                      K: int = 0, coef_map=None):
+                      K: int = 0, coef_map=None, topn: Optional[int] = None):
         """The graphed generators: capture prologue() (inside the graph, before the scale loop), the scale loop and finish() over the static
         label / type rows, and return replay(label_B, cond_type, given, g_seed, request) -> images, with .graph and .owned.
         The sampling state lives in a device seed scalar (scalar graphs: cfg, top_k, top_p are baked in and replay refuses every request
@@ -2291,14 +2375,16 @@ class ControlVAR(nn.Module):
         returns (images, TokenScores) - copies, as the images are.  sampled: the (L,) host pattern of the sampled tokens (None: all); an edit
         graph (forced, the forced-token table) reads it off that table instead
         K > 0 with coef_map (regional guidance): label_B is (B, K), the rows are _prepare_rows' K-label layout and the scale loop reads its combine
-        weights from the static (B, L, 4) table that prologue() fills inside the graph"""
+        weights from the static (B, L, 4) table that prologue() fills inside the graph
+        topn (top_logprobs=N, with logprobs): the top-N launch of every scale is captured beside the score launch, its (B, L, N) / (B, L) buffers are
+        static outputs too, and the TokenScores replay returns carries copies of them"""
         dev, vocab, nstage = self.device, self.cfg.vocab, len(self.cfg.pyramid.patch_nums)
         unguided = cfg is None                               # captured without guidance rows: labels_all / types_all hold B rows, and so does every replay
         nrep = K + 1 if K else self._guidance_rows(four_way, unguided)
         if per_request:
             slots0 = self._adapter_slots(-1, B, nrep) if adapters else None
             table0 = _request_table(B, cfg, top_k, top_p, 0, four_way, vocab, nstage, slots=slots0)     # also validates the defaults
-            state, how = self._row_state(B, table0, logprobs, forced, coef_map=coef_map)
+            state, how = self._row_state(B, table0, logprobs, forced, coef_map=coef_map, topn=topn)
         else:
             state = torch.zeros(1, device=dev, dtype=torch.int64)
             how = _ScalarDraw(cfg, top_k, top_p, 0, seed_dev=state)
@@ -2350,7 +2436,8 @@ class ControlVAR(nn.Module):
             graph.replay()
             if logprobs:
                 return out.clone(), self._token_scores([t.clone() for t in how.score], True, sampled=sampled,
-                                                       forced=forced.clone() if forced is not None else None)
+                                                       forced=forced.clone() if forced is not None else None,
+                                                       topn=[t.clone() for t in how.topn] if how.topn is not None else None)
             return out.clone()
 
         replay.graph = graph
@@ -2363,14 +2450,16 @@ class ControlVAR(nn.Module):
             return self._decode_pair
         return lambda f_hat: self.vae_proxy[0]._decode(f_hat[:, generated].contiguous(), lo=-1.0, hi=1.0, mul=0.5, add=0.5)
 
-    def _check_graph_logprobs(self, per_request: bool, logprobs: bool, four_way: bool):
-        """logprobs=True of the graphed generators: refused in words before anything is captured"""
+    def _check_graph_logprobs(self, per_request: bool, logprobs: bool, four_way: bool, top_logprobs=None) -> Optional[int]:
+        """logprobs=True / top_logprobs=N of the graphed generators: refused in words before anything is captured -> N or None"""
+        n = _top_n('top_logprobs', top_logprobs, logprobs)
         if not logprobs:
-            return
+            return None
         if not per_request:
             raise ValueError('logprobs=True needs per_request=True: the score launch reads the combine weights of the per-request table')
         self._check_logprobs()
         self._check_per_request_mode(four_way)
+        return n
 
     def _check_graph_adapters(self, per_request: bool, adapters: bool):
         if not adapters:
@@ -2384,7 +2473,7 @@ class ControlVAR(nn.Module):
 
     @torch.no_grad()
     def graphed_generator(self, B: int, cfg=1.5, top_k: int = 0, top_p: float = 0.0, per_request: bool = False, adapters: bool = False,
-                          logprobs: bool = False):
+                          logprobs: bool = False, top_logprobs: Optional[int] = None):
         """Capture one full `autoregressive_infer_cfg` (10 scales x depth blocks + both VQVAE decodes, ~2.5k launches) in a
         HIP graph and return ``run(label_B, cond_type=None, g_seed=None) -> images``.  Labels, condition types and the
         sampling seed live in static device buffers that are refreshed before each replay, so every call draws new samples.
@@ -2395,12 +2484,13 @@ class ControlVAR(nn.Module):
         what autoregressive_infer_cfg(B, ...) gives in per-request mode; everything is validated on the host before a buffer is touched.
         adapters=True (with per_request=True, on a model with an adapter bank): run also takes adapter=, one id per row or one int.
         logprobs=True (with per_request=True): the graph holds the score launches and the (B, L) score buffers, and run returns
-        (images, TokenScores) as autoregressive_infer_cfg(logprobs=True) does."""
+        (images, TokenScores) as autoregressive_infer_cfg(logprobs=True) does.  top_logprobs=N (with logprobs=True): the top-N launches and their
+        static buffers join the graph, and the TokenScores carry top_ids / top_logprobs / tail_logprob."""
         four_way = False
         if cfg is None:                                     # cfg=None: the captured loop runs B rows, as autoregressive_infer_cfg(cfg=None); run takes cfg=None only
             self._check_unguided(four_way, True if adapters else None, 'graphed_generator(cfg=None)')
         self._check_graph_adapters(per_request, adapters)
-        self._check_graph_logprobs(per_request, logprobs, four_way)
+        topn = self._check_graph_logprobs(per_request, logprobs, four_way, top_logprobs)
         if self.sampler == 'torch':
             raise NotImplementedError("graphed_generator captures the counter sampler only: sampler='torch' draws its noise with torch on model.rng "
                                       "between the launches; set model.sampler = 'counter' to capture, or call autoregressive_infer_cfg")
@@ -2410,7 +2500,7 @@ class ControlVAR(nn.Module):
         ty0 = torch.zeros(B, dtype=torch.int64) if self.cfg.mask_factor == 2 else None
         labels_all, types_all = self._prepare_rows(B, lab0, ty0, four_way, 0, self._guidance_rows(four_way, cfg is None))
         inner = self._graph_runner(B, four_way, labels_all, types_all, cfg, top_k, top_p, self._decode_pair, per_request=per_request, adapters=adapters,
-                                   logprobs=logprobs, check_rows=False)
+                                   logprobs=logprobs, check_rows=False, topn=topn)
         if per_request:
             def run(label_B, cond_type=None, g_seed=None, cfg=cfg, top_k=top_k, top_p=top_p, adapter=None):
                 return inner(label_B, cond_type, None, g_seed, dict(cfg=cfg, top_k=top_k, top_p=top_p, adapter=adapter))
@@ -2422,7 +2512,8 @@ class ControlVAR(nn.Module):
 
     @torch.no_grad()
     def graphed_conditional_generator(self, B: int, given: str = 'control', cfg=(1.5, 1.5, 1.5), top_k: int = 0, top_p: float = 0.0,
-                                      source: str = 'ids', decode: str = 'both', per_request: bool = False, adapters: bool = False, logprobs: bool = False):
+                                      source: str = 'ids', decode: str = 'both', per_request: bool = False, adapters: bool = False, logprobs: bool = False,
+                                      top_logprobs: Optional[int] = None):
         """Capture one full `conditional_infer_cfg` in a HIP graph - control in, image out (given='control': the control ids are teacher-forced
         as `c_mask=`, the image is generated) or image in, control out (given='image', `c_img=`) - and return
         ``run(label_B, cond_type, given_half, g_seed=None) -> images``.
@@ -2436,13 +2527,14 @@ class ControlVAR(nn.Module):
         four-branch path never draws the order).
         per_request=True: as graphed_generator's - ``run(label_B, cond_type, given_half, g_seed=None, cfg=..., top_k=..., top_p=...)`` with each of
         g_seed / cfg / top_k / top_p a scalar (cfg: one triple) or per row (cfg: (B, 3)); those given here are the defaults of run.
-        logprobs=True (with per_request=True): run returns (images, TokenScores) as conditional_infer_cfg(logprobs=True) does."""
+        logprobs=True (with per_request=True): run returns (images, TokenScores) as conditional_infer_cfg(logprobs=True) does; top_logprobs=N
+        as graphed_generator's."""
         if self.mask_factor != 2:
             raise NotImplementedError('graphed_conditional_generator needs mask_factor == 2 (control_var.py:333)')
         if cfg is None:                                     # cfg=None: the captured loop runs B rows, as conditional_infer_cfg(cfg=None)
             self._check_unguided(True, True if adapters else None, 'graphed_conditional_generator(cfg=None)')
         self._check_graph_adapters(per_request, adapters)
-        self._check_graph_logprobs(per_request, logprobs, True)
+        topn = self._check_graph_logprobs(per_request, logprobs, True, top_logprobs)
         if self.sampler == 'torch':
             raise NotImplementedError("graphed_conditional_generator captures the counter sampler only: sampler='torch' draws its noise with torch on "
                                       "model.rng between the launches; set model.sampler = 'counter' to capture, or call conditional_infer_cfg")
@@ -2489,7 +2581,7 @@ class ControlVAR(nn.Module):
 
         inner = self._graph_runner(B, True, labels_all, types_all, cfg, top_k, top_p, self._finisher(decode, 1 if given == 'control' else 0),
                                    per_request=per_request, adapters=adapters, logprobs=logprobs, teach={arg: ids_Bl}, refresh=refresh, prologue=tokenise,
-                                   sampled=self._sampled_pattern(True, *((ids_Bl, None) if given == 'control' else (None, ids_Bl)), None))
+                                   sampled=self._sampled_pattern(True, *((ids_Bl, None) if given == 'control' else (None, ids_Bl)), None), topn=topn)
         if per_request:
             def run(label_B, cond_type, given_half, g_seed=None, cfg=cfg, top_k=top_k, top_p=top_p, adapter=None):
                 return inner(label_B, cond_type, given_half, g_seed, dict(cfg=cfg, top_k=top_k, top_p=top_p, adapter=adapter))
@@ -2518,7 +2610,8 @@ class ControlVAR(nn.Module):
 
     @torch.no_grad()
     def edit_infer_cfg(self, B: int, label_B, cond_type, *, src_img=None, keep_img=None, src_ctrl=None, keep_ctrl=None, g_seed=None, cfg=1.5,
-                       top_k=0, top_p=0.0, trace: bool = False, more_smooth: bool = False, adapter=None, logprobs: bool = False):
+                       top_k=0, top_p=0.0, trace: bool = False, more_smooth: bool = False, adapter=None, logprobs: bool = False,
+                       top_logprobs: Optional[int] = None):
         """Region-constrained generation (an addition of this library): keep the source's tokens where a mask says "keep", sample the others in
         their context - in-painting, out-painting, editing under a control map (keep_ctrl=True, the image partly kept), or a consistent joint
         edit (the same region of both halves free).  Returns what autoregressive_infer_cfg returns.
@@ -2532,7 +2625,9 @@ class ControlVAR(nn.Module):
         identical results).  label_B and cond_type are given per row.  trace=True leaves last_trace as _trace does, 'idx' holding the ids
         AFTER forcing, plus last_trace['forced'], the table.  more_smooth, sampler='torch', the two-pass separate_decoding branch and
         separator models are refused.  adapter: one adapter id per row or one int, as in autoregressive_infer_cfg (lora.attach_adapters).
-        logprobs=True: returns (images, TokenScores) as autoregressive_infer_cfg does; `sampled` is False at the kept tokens, which are scored too."""
+        logprobs=True: returns (images, TokenScores) as autoregressive_infer_cfg does; `sampled` is False at the kept tokens, which are scored too.
+        top_logprobs=N (with logprobs=True): as autoregressive_infer_cfg's."""
+        topn = _top_n('top_logprobs', top_logprobs, logprobs)
         self._check_edit(label_B, cond_type, more_smooth)
         if cfg is None:
             raise NotImplementedError(_NO_UNGUIDED.format('edit_infer_cfg'))
@@ -2540,13 +2635,13 @@ class ControlVAR(nn.Module):
         s_ctrl, k_ctrl = _edit_half('ctrl', src_ctrl, keep_ctrl, B, pns, self.cfg.vocab) if self.cfg.mask_factor == 2 else (None, None)
         s_img, k_img = _edit_half('img', src_img, keep_img, B, pns, self.cfg.vocab)
         table = _request_table(B, cfg, top_k, top_p, g_seed, False, self.cfg.vocab, len(pns), slots=self._adapter_slots(adapter, B, 2))
-        f_hat, scores = self._run_rows(B, label_B, cond_type, False, table, trace=trace, logprobs=logprobs, edit=(s_ctrl, k_ctrl, s_img, k_img))
+        f_hat, scores = self._run_rows(B, label_B, cond_type, False, table, trace=trace, logprobs=logprobs, edit=(s_ctrl, k_ctrl, s_img, k_img), topn=topn)
         return self._images(f_hat, scores)
 
     # ---- token log-probabilities of given tokens
     @torch.no_grad()
     def score_infer_cfg(self, B: int, label_B, cond_type, *, ids_img, ids_ctrl=None, given: Optional[str] = None, cfg=0.0, adapter=None,
-                        mask_first: bool = True) -> TokenScores:
+                        mask_first: bool = True, top_logprobs: Optional[int] = None) -> TokenScores:
         """The likelihood of GIVEN tokens (an addition of this library): teacher-force the whole sample along its ids and score every token
         under the distribution a generation would have drawn it from.  No sampling launch and no decoder pass is issued: per scale the
         transformer, the head and one score launch (cvar_score_rows), the only consumer of the logits.  Returns a TokenScores whose `sampled`
@@ -2558,7 +2653,10 @@ class ControlVAR(nn.Module):
         cfg = 0 scores under the conditional model alone; a per-row cfg scores under what a generation with that guidance draws from.
         label_B and cond_type are given per row; adapter as in autoregressive_infer_cfg.  A bidirectional model takes the (control, image)
         order as mask_first= here instead of drawing it.  Id range and shapes are checked on the host before any device work; more_smooth has
-        no meaning here, and sampler='torch', the two-pass separate_decoding branch and separator models are refused."""
+        no meaning here, and sampler='torch', the two-pass separate_decoding branch and separator models are refused.
+        top_logprobs=N: the scores also carry the N most likely codes of every token's distribution (cvar_score_topn, one more launch per
+        scale) - with a guidance scale in cfg, sparse_loss() of the result is a sparse guided teacher along these given tokens."""
+        topn = _top_n('top_logprobs', top_logprobs)
         if given not in (None, 'control', 'image'):
             raise ValueError(f"given={given!r}: None (the joint path), 'control' or 'image'")
         four_way, mf = given is not None, self.cfg.mask_factor
@@ -2584,11 +2682,11 @@ class ControlVAR(nn.Module):
         table = _request_table(B, cfg, 0, 0.0, 0, four_way, vocab, len(pns), slots=self._adapter_slots(adapter, B, nrep))
         halves = [img] if mf == 1 else ([ctrl, img] if mask_first else [img, ctrl])
         return self._run_rows(B, label_B, cond_type, four_way, table, sampled=torch.zeros(self.cfg.pyramid.L, dtype=torch.bool), mask_first=mask_first,
-                              score_halves=halves)[1]
+                              score_halves=halves, topn=topn)[1]
 
     @torch.no_grad()
     def graphed_edit_generator(self, B: int, source: str = 'ids', cfg=1.5, top_k=0, top_p=0.0, decode: str = 'both', adapters: bool = False,
-                               logprobs: bool = False):
+                               logprobs: bool = False, top_logprobs: Optional[int] = None):
         """Capture one full `edit_infer_cfg` in a HIP graph and return
         ``run(label_B, cond_type, *, src_img=None, keep_img=None, src_ctrl=None, keep_ctrl=None, g_seed=None, cfg=..., top_k=..., top_p=...) -> images``.
         The keep masks (uint8, all zero = nothing kept), the sources and the request table live in static device buffers refreshed before each
@@ -2599,11 +2697,14 @@ class ControlVAR(nn.Module):
         decode='both': what edit_infer_cfg returns; decode='generated': the image map only, (B, 3, H, H), one decoder pass of B images.
         cfg / top_k / top_p given here are the defaults of run; each and g_seed is a scalar or per row.  Everything is validated on the host
         before the first static buffer is written: a refused run leaves the graph as it was.  Bidirectional models are refused as
-        graphed_generator refuses them.  logprobs=True: run returns (images, TokenScores) as edit_infer_cfg(logprobs=True) does."""
-        return self._graphed_edit('graphed_edit_generator', B, source, cfg, top_k, top_p, decode, adapters, logprobs)
+        graphed_generator refuses them.  logprobs=True: run returns (images, TokenScores) as edit_infer_cfg(logprobs=True) does; top_logprobs=N
+        as graphed_generator's."""
+        return self._graphed_edit('graphed_edit_generator', B, source, cfg, top_k, top_p, decode, adapters, logprobs,
+                                  topn=_top_n('top_logprobs', top_logprobs, logprobs))
 
     @torch.no_grad()
-    def _graphed_edit(self, what: str, B: int, source: str, cfg, top_k, top_p, decode: str, adapters: bool, logprobs: bool, K: int = 0):
+    def _graphed_edit(self, what: str, B: int, source: str, cfg, top_k, top_p, decode: str, adapters: bool, logprobs: bool, K: int = 0,
+                      topn: Optional[int] = None):
         """the capture behind graphed_edit_generator and, with K > 0 labels per sample, graphed_region_generator: the latter adds the static region
         maps, strength, guidance scales and the (B, L, 4) weight table, whose launch joins the forced-token table's in the prologue"""
         if cfg is None:
@@ -2667,7 +2768,7 @@ class ControlVAR(nn.Module):
             return copy
 
         inner = self._graph_runner(B, False, labels_all, types_all, 0.0 if K else cfg, top_k, top_p, self._finisher(decode, mf - 1), per_request=True,
-                                   adapters=adapters, logprobs=logprobs, forced=forced, refresh=refresh, prologue=prologue, K=K, coef_map=coef_map)
+                                   adapters=adapters, logprobs=logprobs, forced=forced, refresh=refresh, prologue=prologue, K=K, coef_map=coef_map, topn=topn)
 
         if K:
             # the guidance scales travel with the maps (cfg_buf); the request table's own weights are not read, so its cfg is a constant 0
@@ -2722,7 +2823,7 @@ class ControlVAR(nn.Module):
     @torch.no_grad()
     def region_infer_cfg(self, B: int, labels, cond_type, *, regions, cfg=1.5, strength=None, top_k=0, top_p=0.0, g_seed=None,
                          src_img=None, keep_img=None, src_ctrl=None, keep_ctrl=None, adapter=None, logprobs: bool = False, trace: bool = False,
-                         more_smooth: bool = False, given: Optional[str] = None):
+                         more_smooth: bool = False, given: Optional[str] = None, top_logprobs: Optional[int] = None):
         """Regional guidance (an addition of this library): several class labels per sample, each weighing the guidance where its
         latent-resolution map says so - "class A on the left, class B on the right", "class X inside this box", "guide harder in this region".
         Returns what autoregressive_infer_cfg returns.
@@ -2737,7 +2838,10 @@ class ControlVAR(nn.Module):
         sampled under the regional weights.  adapter, logprobs, trace: as edit_infer_cfg's; trace also leaves last_trace['coef'], the (B, L, 4)
         weight table, and last_trace['rows'], per scale the head's (nrep B, l, V) rows behind the combined logits.
         more_smooth, given= (the four-branch call), cfg=None, sampler='torch', separator and separate_decoding models are refused; what the
-        maps do to image quality has not been judged (no published checkpoint is loaded here) - the contract is the weights above."""
+        maps do to image quality has not been judged (no published checkpoint is loaded here) - the contract is the weights above.
+        top_logprobs is refused: a top-N form that reads the per-token weight map is not built."""
+        if top_logprobs is not None:
+            raise NotImplementedError(_NO_REGION_TOPN.format('region_infer_cfg'))
         self._check_region(labels, cond_type, more_smooth, given, cfg)
         if logprobs:
             self._check_logprobs()
@@ -2755,13 +2859,16 @@ class ControlVAR(nn.Module):
 
     @torch.no_grad()
     def graphed_region_generator(self, B: int, K: int, source: str = 'ids', top_k=0, top_p=0.0, decode: str = 'both', adapters: bool = False,
-                                 logprobs: bool = False):
+                                 logprobs: bool = False, top_logprobs: Optional[int] = None):
         """Capture one full `region_infer_cfg` with K labels per sample in a HIP graph and return
         ``run(labels, cond_type, *, regions, cfg=1.5, strength=None, src_img=None, keep_img=None, src_ctrl=None, keep_ctrl=None, g_seed=None, top_k=...,
         top_p=..., adapter=None) -> images``.  Labels, maps, strength, guidance scales, keep masks, sources and the request table live in static
         device buffers refreshed before each replay; the graph holds the launches of the weight table and of the forced-token table, so new maps
         need no recapture.  source / decode / adapters / logprobs: graphed_edit_generator's.  Everything is validated on the host before the first
-        static buffer is written.  ``run.coef()`` returns the (B, L, 4) weight table of the last replay.  Bidirectional models are refused."""
+        static buffer is written.  ``run.coef()`` returns the (B, L, 4) weight table of the last replay.  Bidirectional models are refused, and so
+        is top_logprobs (region_infer_cfg)."""
+        if top_logprobs is not None:
+            raise NotImplementedError(_NO_REGION_TOPN.format('graphed_region_generator'))
         if int(K) != K or not 1 <= K <= REGION_MAX_LABELS:
             raise ValueError(f'K={K!r}: 1 to {REGION_MAX_LABELS} labels per sample')
         return self._graphed_edit('graphed_region_generator', B, source, 1.5, top_k, top_p, decode, adapters, logprobs, K=int(K))
@@ -2770,12 +2877,28 @@ class ControlVAR(nn.Module):
         """what the public generation calls return: the decoded images, or (images, scores) under logprobs=True"""
         return self._decode_pair(f_hat) if scores is None else (self._decode_pair(f_hat), scores)
 
-    def _results(self, B: int, out, logprobs: bool, targets: Optional[dict], sampled):
-        """_generate's result -> what the public call returns: images, (images, scores), and the DistillTargets behind them when asked for"""
-        images = self._images(*out) if logprobs else self._images(out)
-        if targets is None:
+    def _distill_request(self, logprobs: bool, top_logprobs, distill_targets: bool, distill_topn):
+        """the scoring keywords of a generation call, checked on the host -> (the targets dict or None, score?, the launch's N or None)"""
+        n, dn = _top_n('top_logprobs', top_logprobs, logprobs), _top_n('distill_topn', distill_topn)
+        if dn is not None and distill_targets:
+            raise ValueError('distill_targets=True and distill_topn=N: one form of targets per call - the dense logits or their N most likely codes')
+        if dn is not None and n is not None and n != dn:
+            raise ValueError(f'top_logprobs={n} and distill_topn={dn}: one top-N launch per scale serves both - pass the same N')
+        tg = {'topn': dn} if dn is not None else ({} if distill_targets else None)
+        return tg, bool(logprobs) or dn is not None, (n if n is not None else dn)
+
+    def _results(self, B: int, out, logprobs: bool, targets: Optional[dict], sampled, top_logprobs=None):
+        """_generate's result -> what the public call returns: images, (images, scores), and the DistillTargets / SparseDistillTargets behind
+        them when asked for.  distill_topn=N scores the call whether logprobs is said or not; the scores are returned only when it is, and
+        carry the alternatives only under top_logprobs"""
+        sparse = targets is not None and 'topn' in targets
+        scores = out[1] if logprobs or sparse else None
+        t = self._distill_targets(targets, B, sampled, scores) if targets is not None else None
+        if sparse and top_logprobs is None:
+            scores = scores._without_alternatives()
+        images = self._images(out[0], scores) if logprobs else self._images(out[0] if sparse else out)
+        if t is None:
             return images
-        t = self._distill_targets(targets, B, sampled)
         return (*images, t) if logprobs else (images, t)
 
     def _decode_pair(self, f_hat: torch.Tensor) -> torch.Tensor:
@@ -2794,7 +2917,7 @@ class ControlVAR(nn.Module):
     @torch.no_grad()
     def autoregressive_infer_cfg(self, B: int, label_B, g_seed: Optional[int] = None, cfg=1.5, top_k=0, top_p=0.0,
                                  more_smooth=False, cond_type=None, _force_idx=None, _trace=False, _gumbel=None, adapter=None, logprobs: bool = False,
-                                 distill_targets: bool = False):
+                                 distill_targets: bool = False, top_logprobs: Optional[int] = None, distill_topn: Optional[int] = None):
         """control_var.py:356-565: returns (B, 3, 2 H, H) in [0,1] with H = 16 patch_nums[-1] - (B, 3, 512, 256) for the default list, (B, 3, 1024, 512) for
         PATCH_NUMS_512 (control image on top, RGB below).
         more_smooth: Gumbel-softmax soft code embeddings (:511-515); `_gumbel` (tests) injects the per-pass noise instead of drawing it.
@@ -2809,29 +2932,39 @@ class ControlVAR(nn.Module):
         unconditional rows and weighs them by zero.  sampler='torch', the two-pass separate_decoding branch, separator models and adapters
         are refused.
         distill_targets=True (likewise): the call traces and additionally returns a DistillTargets as its last value - the ids and the guided
-        logits of the sample, in the forms Trainer.step_tokens(distill=...) takes.  more_smooth, separator and bidirectional models are refused."""
-        tg = {} if distill_targets else None
+        logits of the sample, in the forms Trainer.step_tokens(distill=...) takes.  more_smooth, separator and bidirectional models are refused.
+        top_logprobs=N (with logprobs=True; 1 <= N <= 64): the scores also carry top_ids / top_logprobs (B, L, N), the N most likely codes of every
+        token's distribution in rank order with the bits `logprob` would hold for them, and tail_logprob (B, L), the log of the mass of all the
+        others - one more launch per scale (cvar_score_topn) beside the score launch; ids, images and the other fields are unchanged.
+        distill_topn=N: additionally returns a SparseDistillTargets as the last value - DistillTargets with the guided distribution in that
+        sparse form, never materialised as (B, L, V); it follows distill_targets' refusals.  One difference to distill_targets=True: it selects the
+        per-request path as logprobs=True does, so label_B (and cond_type) must be given, and a scalar g_seed is broadcast as that path broadcasts
+        it - every row draws under the key the scalar call builds at B = 1, so from B = 2 on the ids are those of distill_targets=True called with
+        g_seed=[s] * B, not those of its scalar-seed call."""
+        tg, score, topn = self._distill_request(logprobs, top_logprobs, distill_targets, distill_topn)
         out = self._generate(B, label_B, g_seed, cfg, top_k, top_p, more_smooth, cond_type, False, None, None, _force_idx, _trace, _gumbel, adapter=adapter,
-                             logprobs=logprobs, targets=tg)
-        return self._results(B, out, logprobs, tg, self._sampled_pattern(False, None, None, _force_idx))
+                             logprobs=score, targets=tg, topn=topn)
+        return self._results(B, out, logprobs, tg, self._sampled_pattern(False, None, None, _force_idx), top_logprobs)
 
     @torch.no_grad()
     def conditional_infer_cfg(self, B: int, label_B, g_seed: Optional[int] = None, cfg=(1.5, 1.5, 1.5), top_k=0, top_p=0.0,
                               more_smooth=False, cond_type=None, c_mask=None, c_img=None, _force_idx=None, _trace=False, _gumbel=None,
-                              adapter=None, logprobs: bool = False, distill_targets: bool = False):
+                              adapter=None, logprobs: bool = False, distill_targets: bool = False, top_logprobs: Optional[int] = None,
+                              distill_topn: Optional[int] = None):
         """control_var.py:223-354: 4-branch CFG with teacher forcing of the control (c_mask) or image (c_img) ids.
         logprobs=True: returns (images, TokenScores) as autoregressive_infer_cfg does (the unfiltered combined distribution of the four branches;
         tokens in control-first order); `sampled` is False along the teacher-forced half, which is scored too.
         cfg=None: generation without guidance rows, as autoregressive_infer_cfg's - one row per sample instead of four, the given half
         teacher-forced into it; the bits of cfg=(0, 0, 0) under deterministic_plan=True.
         distill_targets=True: additionally returns a DistillTargets; its ids are those the first branch continued with (the given half where it
-        was forced), and `sampled` is False along that half."""
+        was forced), and `sampled` is False along that half.
+        top_logprobs=N, distill_topn=N: as autoregressive_infer_cfg's, under the combined distribution of the four branches."""
         if self.mask_factor != 2:
             raise NotImplementedError('conditional_infer_cfg needs mask_factor == 2 (control_var.py:333)')
-        tg = {} if distill_targets else None
+        tg, score, topn = self._distill_request(logprobs, top_logprobs, distill_targets, distill_topn)
         out = self._generate(B, label_B, g_seed, cfg, top_k, top_p, more_smooth, cond_type, True, c_mask, c_img, _force_idx, _trace, _gumbel, adapter=adapter,
-                             logprobs=logprobs, targets=tg)
-        return self._results(B, out, logprobs, tg, self._sampled_pattern(True, c_mask, c_img, _force_idx))
+                             logprobs=score, targets=tg, topn=topn)
+        return self._results(B, out, logprobs, tg, self._sampled_pattern(True, c_mask, c_img, _force_idx), top_logprobs)
 
     def forward(self, label_B: torch.LongTensor, x_BLCv_wo_first_l: torch.Tensor, cond_type=None, mask_first=True) -> torch.Tensor:
         """control_var.py:568-651 teacher-forced logits (B, L, V) fp32.  Under autograd (grad mode on and trainable
@@ -2897,32 +3030,35 @@ class VAR(ControlVAR):
 
     @torch.no_grad()
     def autoregressive_infer_cfg(self, B: int, label_B, g_seed: Optional[int] = None, cfg=1.5, top_k=0, top_p=0.0,
-                                 more_smooth=False, _force_idx=None, _trace=False, adapter=None, logprobs: bool = False, distill_targets: bool = False):
+                                 more_smooth=False, _force_idx=None, _trace=False, adapter=None, logprobs: bool = False, distill_targets: bool = False,
+                                 top_logprobs: Optional[int] = None, distill_topn: Optional[int] = None):
         """var.py:143-207: returns (B, 3, H, H) in [0,1], H = 16 patch_nums[-1] (256, or 512 with PATCH_NUMS_512).
-        logprobs=True: (images, TokenScores), as ControlVAR.autoregressive_infer_cfg; cfg=None and distill_targets=True likewise."""
-        tg = {} if distill_targets else None
-        out = self._generate(B, label_B, g_seed, cfg, top_k, top_p, more_smooth, None, False, None, None, _force_idx, _trace, adapter=adapter, logprobs=logprobs,
-                             targets=tg)
-        return self._results(B, out, logprobs, tg, self._sampled_pattern(False, None, None, _force_idx))
+        logprobs=True: (images, TokenScores), as ControlVAR.autoregressive_infer_cfg; cfg=None, distill_targets=True, top_logprobs=N and
+        distill_topn=N likewise."""
+        tg, score, topn = self._distill_request(logprobs, top_logprobs, distill_targets, distill_topn)
+        out = self._generate(B, label_B, g_seed, cfg, top_k, top_p, more_smooth, None, False, None, None, _force_idx, _trace, adapter=adapter, logprobs=score,
+                             targets=tg, topn=topn)
+        return self._results(B, out, logprobs, tg, self._sampled_pattern(False, None, None, _force_idx), top_logprobs)
 
     @torch.no_grad()
     def edit_infer_cfg(self, B: int, label_B, *, src_img=None, keep_img=None, g_seed=None, cfg=1.5, top_k=0, top_p=0.0, trace: bool = False,
-                       more_smooth: bool = False, adapter=None, logprobs: bool = False):
+                       more_smooth: bool = False, adapter=None, logprobs: bool = False, top_logprobs: Optional[int] = None):
         """ControlVAR.edit_infer_cfg for the one half a plain VAR has: returns (B, 3, H, H) as autoregressive_infer_cfg"""
         return super().edit_infer_cfg(B, label_B, None, src_img=src_img, keep_img=keep_img, g_seed=g_seed, cfg=cfg, top_k=top_k, top_p=top_p, trace=trace,
-                                      more_smooth=more_smooth, adapter=adapter, logprobs=logprobs)
+                                      more_smooth=more_smooth, adapter=adapter, logprobs=logprobs, top_logprobs=top_logprobs)
 
     @torch.no_grad()
     def region_infer_cfg(self, B: int, labels, *, regions, cfg=1.5, strength=None, top_k=0, top_p=0.0, g_seed=None, src_img=None, keep_img=None,
-                         adapter=None, logprobs: bool = False, trace: bool = False, more_smooth: bool = False):
+                         adapter=None, logprobs: bool = False, trace: bool = False, more_smooth: bool = False, top_logprobs: Optional[int] = None):
         """ControlVAR.region_infer_cfg for the one half a plain VAR has: returns (B, 3, H, H) as autoregressive_infer_cfg"""
         return super().region_infer_cfg(B, labels, None, regions=regions, cfg=cfg, strength=strength, top_k=top_k, top_p=top_p, g_seed=g_seed,
-                                        src_img=src_img, keep_img=keep_img, adapter=adapter, logprobs=logprobs, trace=trace, more_smooth=more_smooth)
+                                        src_img=src_img, keep_img=keep_img, adapter=adapter, logprobs=logprobs, trace=trace, more_smooth=more_smooth,
+                                        top_logprobs=top_logprobs)
 
     @torch.no_grad()
-    def score_infer_cfg(self, B: int, label_B, *, ids_img, cfg=0.0, adapter=None) -> 'TokenScores':
+    def score_infer_cfg(self, B: int, label_B, *, ids_img, cfg=0.0, adapter=None, top_logprobs: Optional[int] = None) -> 'TokenScores':
         """ControlVAR.score_infer_cfg for the one half a plain VAR has"""
-        return super().score_infer_cfg(B, label_B, None, ids_img=ids_img, cfg=cfg, adapter=adapter)
+        return super().score_infer_cfg(B, label_B, None, ids_img=ids_img, cfg=cfg, adapter=adapter, top_logprobs=top_logprobs)
 
     def conditional_infer_cfg(self, *a, **k):
         raise NotImplementedError('plain VAR has no conditional_infer_cfg (var.py)')

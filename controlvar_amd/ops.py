@@ -479,6 +479,35 @@ def score_rows(logits: torch.Tensor, B: int, nrep: int, l: int, V: int, coef: to
                                       _ptr(rank), _ptr(argmax), int(ldo.pop()) if ldo else 0, int(ldv), _stream()), 'cvar_score_rows')
 
 
+def score_topn(logits: torch.Tensor, B: int, nrep: int, l: int, V: int, coef: torch.Tensor, N: int, top_id: Optional[torch.Tensor] = None,
+               top_logprob: Optional[torch.Tensor] = None, tail_logprob: Optional[torch.Tensor] = None, ldv: int = 0):
+    """The N most likely codes per token under the CFG-combined distribution (cvar_score_topn, include/cvar_topn.h), in cvar_score_rows' rank
+    order, with the log-probabilities score_rows would report for them and the log of the mass of all the other codes.  logits / coef as
+    score_rows takes them.  top_id int32 / top_logprob float32: (B, l, N) with unit stride along N and stride N along the tokens;
+    tail_logprob float32 (B, l) with unit stride along the tokens; ONE row stride in tokens for the three (handed on as ldo): the columns of
+    one scale in (B, L, N) / (B, L) buffers will do.  top_id and top_logprob are each optional, but not both None."""
+    dev = logits.device
+    if coef is not None and (not torch.is_tensor(coef) or coef.dtype != torch.float32 or tuple(coef.shape) != (B, 4) or not coef.is_contiguous()
+                             or coef.device != dev):
+        raise ValueError(f'score_topn: coef must be a contiguous float32 {(B, 4)} tensor on {dev}')
+    if not isinstance(N, int) or isinstance(N, bool) or not 1 <= N <= _lib.TOPN_MAX:
+        raise ValueError(f'score_topn: N must be an integer in 1..{_lib.TOPN_MAX}, got {N!r}')
+    ldo = set()
+    for name, t, dtype, shape in (('top_id', top_id, torch.int32, (B, l, N)), ('top_logprob', top_logprob, torch.float32, (B, l, N)),
+                                  ('tail_logprob', tail_logprob, torch.float32, (B, l))):
+        if t is None:
+            continue
+        per = N if len(shape) == 3 else 1
+        if (not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != shape or t.device != dev or t.stride(-1) != 1
+                or (len(shape) == 3 and l > 1 and t.stride(1) != N) or (B > 1 and (t.stride(0) % per or t.stride(0) < l * per))):
+            raise ValueError(f'score_topn: {name} must be a {str(dtype)[6:]} {shape} tensor on {dev}, dense along the tokens and the N entries')
+        ldo.add(t.stride(0) // per if B > 1 and t.stride(0) % per == 0 else l)
+    if len(ldo) > 1:
+        raise ValueError(f'score_topn: top_id / top_logprob / tail_logprob must share one row stride in tokens, got {sorted(ldo)}')
+    check(_lib.load().cvar_score_topn(_ptr(logits), B, nrep, l, V, _ptr(coef), N, _ptr(top_id), _ptr(top_logprob), _ptr(tail_logprob),
+                                      int(ldo.pop()) if ldo else 0, int(ldv), _stream()), 'cvar_score_topn')
+
+
 def edit_force_table(keep_ctrl: Optional[torch.Tensor], keep_img: Optional[torch.Tensor], src_ctrl: Optional[torch.Tensor],
                      src_img: Optional[torch.Tensor], patch_nums: Sequence[int], B: int, mask_first: bool, mask_factor: int, forced: torch.Tensor):
     """The forced-token table of every scale in one launch (cvar_edit_force_table, include/cvar_serve.h).  keep_*: (B, S, S) uint8 or None,
@@ -752,6 +781,14 @@ def kd_fwd_bwd(logits, teacher, ldt, weight, gscale, loss_tok, dlogits, M, V):
     of the target ids; weight and dlogits may be None"""
     check(_lib.load().cvar_kd_fwd_bwd(_ptr(logits), _ptr(teacher), int(ldt), _ptr(weight), float(gscale), _ptr(loss_tok), _ptr(dlogits),
                                       dt(dlogits) if dlogits is not None else CVAR_F32, M, V, _stream()), 'cvar_kd_fwd_bwd')
+
+
+def kd_topn_fwd_bwd(logits, t_id, t_lp, t_tail, N, weight, gscale, loss_tok, dlogits, M, V):
+    """the sparse soft-target loss on the rows cvar_ce_fwd_bwd takes (cvar_kd_topn_fwd_bwd, include/cvar_topn.h): the teacher as N listed codes per
+    row - t_id [M][N] int32 (< 0: unused), t_lp [M][N] fp32 - and the log of its mass on all the others, t_tail [M] fp32 (None: no tail mass);
+    weight and dlogits may be None"""
+    check(_lib.load().cvar_kd_topn_fwd_bwd(_ptr(logits), _ptr(t_id), _ptr(t_lp), _ptr(t_tail), int(N), _ptr(weight), float(gscale), _ptr(loss_tok),
+                                           _ptr(dlogits), dt(dlogits) if dlogits is not None else CVAR_F32, M, V, _stream()), 'cvar_kd_topn_fwd_bwd')
 
 
 def scatter_add_rows(src, ld_src, idx, dst, n, Cdim, src_off: int = 0):

@@ -246,6 +246,65 @@ class DistillLoss:
             raise ValueError(f'weights: expected shape {(B, L)}, got {tuple(self.weights.shape)}')
 
 
+@dataclass
+class SparseDistillLoss:
+    """The sparse form of DistillLoss (cvar_kd_topn_fwd_bwd, include/cvar_topn.h): the teacher of every token as its N most likely
+    codes, their log-probabilities and the log of the mass of all the other codes - what TokenScores carries under top_logprobs=N, and 63 times
+    smaller than the dense logits at N = 32.  The loss per token is KL(teacher || model) over the N + 1 cells {id_0}, .., {id_N-1}, {the rest}.
+    top_ids       (B, L, N) int32 on the device, 1 <= N <= 64; an entry < 0 is unused, the others are distinct per token and < cfg.vocab
+    top_logprobs  (B, L, N) fp32
+    tail_logprob  (B, L) fp32 or None: None or -inf = no tail mass
+    weights       (B, L) token weights, or None = 1; they take ignore_mask's place, as DistillLoss.weights do.
+    All in the token order of the training labels (TokenScores).  The types are checked on the host when the object is built, the shapes
+    against the batch by check(); distinct ids are the caller's contract (cvar_score_topn's output has them)."""
+    top_ids: torch.Tensor
+    top_logprobs: torch.Tensor
+    tail_logprob: Optional[torch.Tensor] = None
+    weights: Optional[torch.Tensor] = None
+
+    def __post_init__(self):
+        for name, t, dtype, dim, shape in (('top_ids', self.top_ids, torch.int32, 3, '(B, L, N)'), ('top_logprobs', self.top_logprobs, torch.float32, 3, '(B, L, N)'),
+                                           ('tail_logprob', self.tail_logprob, torch.float32, 2, '(B, L)')):
+            if t is None and name == 'tail_logprob':
+                continue
+            if not torch.is_tensor(t) or t.dtype != dtype:
+                raise ValueError(f'{name}: expected {"an" if dtype == torch.int32 else "a"} {str(dtype)[6:]} tensor, got '
+                                 f'{type(t).__name__ if not torch.is_tensor(t) else t.dtype}')
+            if t.dim() != dim:
+                raise ValueError(f'{name}: expected {shape}, got {tuple(t.shape)}')
+        if tuple(self.top_ids.shape) != tuple(self.top_logprobs.shape):
+            raise ValueError(f'top_ids and top_logprobs: one shape (B, L, N), got {tuple(self.top_ids.shape)} and {tuple(self.top_logprobs.shape)}')
+        if not 1 <= self.top_ids.shape[2] <= 64:
+            raise ValueError(f'top_ids: N = {self.top_ids.shape[2]} listed codes per token, 1 to 64 are offered')
+        w = self.weights
+        if w is not None:
+            if not torch.is_tensor(w) or w.dtype not in (torch.bool, torch.float32, torch.float64, torch.bfloat16, torch.float16):
+                raise ValueError(f'weights: expected a floating-point or bool tensor, got {type(w).__name__ if not torch.is_tensor(w) else w.dtype}')
+            if w.dim() != 2:
+                raise ValueError(f'weights: expected (B, L), got {tuple(w.shape)}')
+
+    @property
+    def N(self) -> int:
+        return int(self.top_ids.shape[2])
+
+    def check(self, B: int, L: int, V: int, device=None):
+        """the shapes (and the device) against a batch of B samples of L tokens over V classes (host only; the ids' range is the kernel's
+        contract: an id >= V counts as unused)"""
+        if tuple(self.top_ids.shape[:2]) != (B, L):
+            raise ValueError(f'top_ids: expected shape {(B, L, self.N)}, got {tuple(self.top_ids.shape)}')
+        if self.tail_logprob is not None and tuple(self.tail_logprob.shape) != (B, L):
+            raise ValueError(f'tail_logprob: expected shape {(B, L)}, got {tuple(self.tail_logprob.shape)}')
+        if device is not None:
+            for name, t in (('top_ids', self.top_ids), ('top_logprobs', self.top_logprobs), ('tail_logprob', self.tail_logprob)):
+                if t is not None and t.device.type != torch.device(device).type:
+                    raise ValueError(f'{name}: expected on {device}, got {t.device} (teacher targets are not copied between devices)')
+        if self.weights is not None and tuple(self.weights.shape) != (B, L):
+            raise ValueError(f'weights: expected shape {(B, L)}, got {tuple(self.weights.shape)}')
+
+
+_DISTILL_FORMS = (DistillLoss, SparseDistillLoss)
+
+
 def _ln_rows(C: int):
     """the adaLN forward of rows of C channels: above 2048 the entry point of include/cvar_wide.h; narrow models call ops.ln_modulate exactly as before"""
     return ops.ln_modulate_wide if C > 2048 else ops.ln_modulate
@@ -496,21 +555,22 @@ class TrainEngine:
     @torch.no_grad()
     def forward_backward(self, label_B: torch.Tensor, x_wo_first: torch.Tensor, cond_type: Optional[torch.Tensor], targets: torch.Tensor,
                          ignore_mask: Optional[torch.Tensor] = None, drop_seed: Optional[int] = None, mask_first: bool = True,
-                         accumulate: bool = False, policy: Optional[PolicyLoss] = None, distill: Optional[DistillLoss] = None):
+                         accumulate: bool = False, policy: Optional[PolicyLoss] = None, distill=None):
         """-> (loss scalar tensor, per-token loss (B*L,)); gradients land in self.grads(): overwritten, or with accumulate=True added to what
         it holds - fp32(old + this micro-batch's plain gradient) per element, whatever the batch size of the earlier calls.  The loss and its
         1 / M scale are this micro-batch's own; the 1 / N of a window of N belongs to the optimizer's gradient scale (FusedAdamW.step).
         policy: the clipped policy-gradient loss in the place of the cross-entropy (PolicyLoss) - one other loss launch on the
         same logits and dlogits, nothing else; the per-token logprob, ratio, clipped, kl and coef stay on the engine as self.policy_out.
         distill: the soft-target loss in the place of the cross-entropy (DistillLoss) - likewise one other loss launch; `targets`
-        is not read, distill.weights stands where ignore_mask stands, and the returned per-token loss is the token's KL(teacher || model)."""
+        is not read, distill.weights stands where ignore_mask stands, and the returned per-token loss is the token's KL(teacher || model).
+        A SparseDistillLoss (the teacher's N most likely codes and its tail mass) dispatches to cvar_kd_topn_fwd_bwd in the same place."""
         if policy is not None:
             policy.check(x_wo_first.shape[0], self.L)                 # refused before any device work
         if distill is not None:                                      # likewise
             if policy is not None:
                 raise ValueError('distill and policy: a step has one loss - the soft-target loss or the policy-gradient loss')
-            if not isinstance(distill, DistillLoss):
-                raise TypeError(f'distill: a DistillLoss, got {type(distill).__name__}')
+            if not isinstance(distill, _DISTILL_FORMS):
+                raise TypeError(f'distill: a DistillLoss or a SparseDistillLoss, got {type(distill).__name__}')
             if distill.weights is not None and ignore_mask is not None:
                 raise ValueError('distill.weights and ignore_mask: the weights take the place of ignore_mask - fold the two into one and pass it as weights')
             if self.cfg.separator:
@@ -529,7 +589,11 @@ class TrainEngine:
             gscale = 1.0 / (M * (float(w.mean()) + 1e-6))
         else:
             w, gscale = None, 1.0 / M
-        if distill is not None:
+        if isinstance(distill, SparseDistillLoss):
+            ops.kd_topn_fwd_bwd(self.logits, distill.top_ids.contiguous(), distill.top_logprobs.contiguous(),
+                                None if distill.tail_logprob is None else distill.tail_logprob.contiguous(), distill.N, w, gscale, self.loss_tok,
+                                self.dlogits, M, V)
+        elif distill is not None:
             ops.kd_fwd_bwd(self.logits, distill.logits.contiguous(), V, w, gscale, self.loss_tok, self.dlogits, M, V)
         elif policy is None:
             ops.ce_fwd_bwd(self.logits, tg, w, gscale, self.loss_tok, self.dlogits, M, V)
@@ -1221,7 +1285,7 @@ class Trainer:
 
     @torch.no_grad()
     def step_tokens(self, ids_img, ids_ctrl, cls, types, *, ignore_mask=None, policy: Optional[PolicyLoss] = None, drop_seed=None,
-                    mask_first: Optional[bool] = None, distill: Optional[DistillLoss] = None) -> Dict[str, object]:
+                    mask_first: Optional[bool] = None, distill=None) -> Dict[str, object]:
         """step() on token ids instead of pixels: one micro-batch with step()'s window, schedule, all-reduce, clipping and return dict, without
         the tokenizer.  ids_img / ids_ctrl: each half's multi-scale ids in the forms score_infer_cfg takes - the list of (B, pn^2) tensors
         vae.img_to_idxBl returns or one (B, sum pn^2) tensor - so a sampled sequence or a pre-tokenised dataset trains as it is; ids_ctrl=None
@@ -1231,7 +1295,8 @@ class Trainer:
         distill: a DistillLoss replaces the cross-entropy by KL(teacher || model) on the teacher logits it carries; the ids
         are then the model's inputs only, `loss` is the weighted mean KL, distill.weights stands where ignore_mask stands (not both) and
         policy is excluded.  DistillTargets.loss() of a generation call with distill_targets=True is such an object; the student is trained
-        with cond_drop_rate = 0.
+        with cond_drop_rate = 0.  A SparseDistillLoss (SparseDistillTargets.loss() of distill_topn=N, TokenScores.sparse_loss() of
+        top_logprobs=N) takes the same place with the teacher's N most likely codes and its tail mass.
         Shapes and the id range are checked on the host before any device work.  Separator models are refused; a bidirectional model needs
         mask_first said (True: these ids go control first)."""
         both, B, mask_first = self._check_tokens(ids_img, ids_ctrl, cls, types, mask_first)
@@ -1242,8 +1307,8 @@ class Trainer:
         if distill is not None:
             if policy is not None:
                 raise ValueError('distill and policy: a step has one loss - the soft-target loss or the policy-gradient loss')
-            if not isinstance(distill, DistillLoss):
-                raise TypeError(f'distill: a DistillLoss, got {type(distill).__name__}')
+            if not isinstance(distill, _DISTILL_FORMS):
+                raise TypeError(f'distill: a DistillLoss or a SparseDistillLoss, got {type(distill).__name__}')
             if distill.weights is not None and ignore_mask is not None:
                 raise ValueError('distill.weights and ignore_mask: the weights take the place of ignore_mask - fold the two into one and pass it as weights')
             if self.var.cfg.vocab != self.var.cfg.head_ld:
